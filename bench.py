@@ -36,7 +36,12 @@ Extra JSON fields:
                   second against the chip's wave64 VALU issue rate, which bounds it (instructions per
                   event from the PMC summary x events/s).
   cpu_baseline  — the reference-semantics CPU restatement (oracle/, ChaCha8 + first-reaction +
-                  BTPE, "port") on a bounded sample of the same workload, rank 0 at N=1 only.
+                  BTPE, "port") on a bounded sample of the same workload, rank 0 at N=1 only, and
+                  only with --full (null otherwise).
+
+A plain run sets up, warms up, times the steps and prints the line; --full adds the measurements that
+take runs of their own (the CPU baseline). --dump-outputs DIR saves what the last timed step computed
+(dump_outputs below).
 """
 import argparse
 import dataclasses
@@ -320,6 +325,40 @@ def cpu_baseline(threads: int, workload: str = "c3"):
                                   f"direct method, popcount binomial), {threads} threads"}
 
 
+DUMP_SAMPLE = 1 << 16  # replicates in the --dump-outputs sample of the per-replicate summaries
+DUMP_SEED = 20240  # fixes that sample
+SUMMARY_COLUMNS = ("global_id", "nminus", "nplus", "iters", "events_by_type0", "events_by_type1", "events_by_type2",
+                   "events_by_type3", "uneven", "time", "event_hash_hi32", "event_hash_lo32", "stop_reason", "error")
+
+
+def dump_outputs(directory: str, hist, totals, rp: RankParts, ctxs) -> None:
+    """--dump-outputs: what the last timed step computed, as float64 .npy files (every count is far below 2^53,
+    so the conversion is exact; the 64-bit event hash travels as two 32-bit halves).
+      hist.npy       [sets, hist_bins]  the copy-number histogram, reduced over the ranks
+      totals.npy     [sets, 16]         the ecdna_totals_t words, reduced over the ranks
+      summaries.npy  [m, 14]            rank 0's per-replicate summaries (columns SUMMARY_COLUMNS), the m =
+                                        min(shard, DUMP_SAMPLE) replicates of a fixed seeded sample in local order
+    The inputs are a function of the arguments alone (seed 42, global replicate ids), so two builds run with the
+    same arguments are comparable file for file."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    n_sets = len(rp.spec.rates)
+    np.save(os.path.join(directory, "hist.npy"), hist.cpu().numpy().astype(np.float64).reshape(n_sets, -1))
+    np.save(os.path.join(directory, "totals.npy"), totals.cpu().numpy().astype(np.float64).reshape(n_sets, 16))
+    summ = np.concatenate([c.download().summaries for c in ctxs])  # the parts follow the shard's local order
+    assert len(summ) == rp.reps
+    pick = np.arange(rp.reps)
+    if rp.reps > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(rp.reps, size=DUMP_SAMPLE, replace=False))
+    s = summ[pick]
+    cols = [rp.spec.replicate_ids()[pick], s["nminus"], s["nplus"], s["iters"],
+            *(s["events_by_type"][:, k] for k in range(4)), s["uneven"], s["time"], s["event_hash"] >> np.uint64(32),
+            s["event_hash"] & np.uint64(0xFFFFFFFF), s["stop_reason"], s["error"]]
+    assert len(cols) == len(SUMMARY_COLUMNS)
+    np.save(os.path.join(directory, "summaries.npy"), np.stack([np.asarray(c, dtype=np.float64) for c in cols], axis=1))
+
+
 def main():
     # exactly one JSON line on stdout: library chatter (e.g. RCCL's version banner, printed to fd 1 when a
     # communicator is created) goes to stderr; the result line is written to the saved stdout
@@ -330,7 +369,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (cpu_baseline field; "
+                         "N=1, rank 0). Off by default: a plain run sets up, warms up, times the steps and prints")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 saves what the last step computed as DIR/<name>.npy "
+                         "(float64: hist, totals, a seeded sample of the per-replicate summaries; dump_outputs)")
     ap.add_argument("--reps-per-gpu", type=int, default=REPS_PER_GPU)
     ap.add_argument("--store", choices=("bins", "rows"), default="bins")
     ap.add_argument("--bin-kmax", type=int, choices=(32, 64, 256), default=None,
@@ -353,8 +398,10 @@ def main():
                     help="reference: the Rust reference's own draws seed for seed (ECDNA_FLAG_REFERENCE_DRAWS, "
                          "DESIGN.md §4.1; row store only): the seed-for-seed mode's throughput, not the metric's")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the timed steps)")
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # under torchrun (even at one rank) the RCCL path runs: process group, all-reduce, barriers
@@ -469,6 +516,8 @@ def main():
         import numpy as np
 
         np.savez(args.dump_hist, hist=hist.cpu().numpy(), totals=tot_sets)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, hist, tot, rp, ctxs)
     if rank == 0:
         avg_kernel_s = sum(kernel_ms) / len(kernel_ms) * 1e-3
         achieved = local_alg / avg_kernel_s / 1e9
@@ -515,7 +564,7 @@ def main():
                         "event from the committed PMC summary, ceiling from tools/rmw_shapes.hip",
             }
         cpu = None
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             # every usable core, as the reference's rayon pool (src/main.rs:221-224)
             threads = int(os.environ.get("ECDNA_BENCH_CPU_THREADS", "0")) or usable_cores()
             cpu = cpu_baseline(threads, args.workload)

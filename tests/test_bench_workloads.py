@@ -141,3 +141,38 @@ def test_k0_split_refuses_a_shard_whose_heavy_sets_are_not_a_suffix():
     assert len(whole) == 1 and whole[0][0].bin_kmax == 64  # no heavy replicate: one part
     empty = shard.k0_split(abi.RunSpec(n_replicates=0, flags=abi.FLAG_BIN_STORE, bin_kmax=64), 1, 256, (1, 1))
     assert len(empty) == 1 and empty[0][0].n_replicates == 0  # (an empty shard stays one context)
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_shard(oracle_mod, tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs) with the oracle standing in for the engine's contexts: a C4-shaped shard in
+    two parts (the k0 split's local order), float64 files, the per-replicate sample the same ids on every call and
+    each row the summary of its global id."""
+    import types
+
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 16)
+    rp = bench.rank_parts("c4", 2, 1, total=1024 * 4)
+    assert len(rp.parts) == 2 and rp.reps == 2048
+    results = [oracle_mod.run(sp, mode="philox", n_threads=4) for sp, _ in rp.parts]
+    ctxs = [types.SimpleNamespace(download=lambda r=r: r) for r in results]
+    hist = torch.from_numpy(sum(r.hist.astype(np.int64) for r in results).reshape(-1))
+    tot = torch.from_numpy(sum(r.totals.view(np.uint64).astype(np.int64) for r in results).reshape(-1))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), hist, tot, rp, ctxs)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("hist", "totals", "summaries")}
+    for n, arr in a.items():
+        assert arr.dtype == np.float64
+        np.testing.assert_array_equal(arr, np.load(tmp_path / "b" / f"{n}.npy"))
+    assert a["hist"].shape == (1024, 1025) and a["totals"].shape == (1024, 16)
+    assert a["totals"][:, 0].sum() == 2048 and a["hist"].sum() == a["totals"][:, 7:9].sum()
+    assert a["summaries"].shape == (16, len(bench.SUMMARY_COLUMNS))
+    by_id = {}
+    for (sp, _), r in zip(rp.parts, results):
+        by_id.update(zip(sp.replicate_ids().tolist(), r.summaries))
+    col = dict(zip(bench.SUMMARY_COLUMNS, a["summaries"].T))
+    assert np.all(np.diff(col["global_id"]) > 0) and np.all(col["global_id"] % 2 == 1)
+    for i, gid in enumerate(col["global_id"].astype(np.int64).tolist()):
+        s = by_id[gid]
+        assert (col["nplus"][i], col["nminus"][i], col["iters"][i]) == (s["nplus"], s["nminus"], s["iters"])
+        assert col["time"][i] == s["time"] and col["stop_reason"][i] == s["stop_reason"]

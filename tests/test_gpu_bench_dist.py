@@ -79,6 +79,50 @@ def test_bench_distributed_paths_match_one_process(tmp_path):
     assert one["config"]["events_per_step"] == two["config"]["events_per_step"] == int(ref_tot[1])
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) skips the CPU baseline, times exactly --steps steps, and --dump-outputs saves what
+    the last step computed: the histogram, the totals and the seeded sample of per-replicate summaries equal one
+    engine run of the same ids, value for value (more replicates than bench.DUMP_SAMPLE, so the sample is a
+    proper subset)."""
+    sys.path.insert(0, REPO)
+    import bench
+    from ecdna_evo_amd import engine
+
+    n = bench.DUMP_SAMPLE + 4321
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--reps-per-gpu", str(n), "--dump-outputs", str(out_dir)]
+    out = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["cpu_baseline"] is None and line["steps"] == 3 and line["dtype"].startswith("u16+f32")
+    assert line["value"] == pytest.approx(line["config"]["events_per_step"] / (line["ms_per_step"] * 1e-3))
+
+    with engine.Context(bench.workload_spec(0, n, n)) as ctx:
+        ctx.launch()
+        ctx.sync()
+        res = ctx.download()
+    hist, totals, summ = (np.load(out_dir / f"{name}.npy") for name in ("hist", "totals", "summaries"))
+    assert sorted(os.listdir(out_dir)) == ["hist.npy", "summaries.npy", "totals.npy"]
+    assert hist.dtype == totals.dtype == summ.dtype == np.float64
+    np.testing.assert_array_equal(hist, res.hist.astype(np.float64))
+    np.testing.assert_array_equal(totals, res.totals.view(np.uint64).reshape(-1, 16).astype(np.float64))
+    assert summ.shape == (bench.DUMP_SAMPLE, len(bench.SUMMARY_COLUMNS))
+    ids = summ[:, 0].astype(np.int64)
+    assert np.all(np.diff(ids) > 0) and ids[0] >= 0 and ids[-1] < n
+    s = res.summaries[ids]
+    col = dict(zip(bench.SUMMARY_COLUMNS, summ.T))
+    for f in ("nminus", "nplus", "iters", "uneven", "time", "stop_reason", "error"):
+        np.testing.assert_array_equal(col[f], s[f].astype(np.float64), err_msg=f)
+    for k in range(4):
+        np.testing.assert_array_equal(col[f"events_by_type{k}"], s["events_by_type"][:, k].astype(np.float64))
+    np.testing.assert_array_equal(col["event_hash_hi32"] * 2.0 ** 32 + col["event_hash_lo32"],
+                                  s["event_hash"].astype(np.float64))
+
+
 # the strong-scaling lines BASELINE.json places on 8 GPUs (C4: the ABC sweep's interleaved shards with the cost
 # hint's start order; C5: the turnover run), scaled down: (total replicates, cell cap)
 STRONG = {"c4": (1024 * 16, None), "c5": (512, 20_000), "c2": (4096, 2_000)}

@@ -29,11 +29,13 @@
 #                (tools/probe_configs.py c5): the same-K strong-scaling curve
 #     pmc_ref    SQ counters (two passes) of one C3 step under the reference's own draws (ssa_stepper_refdraws)
 #   LIBS    prebuilt libraries ecdna-evo_amd/lib_ab/<name>/ (tools/ab_build.sh <ref|WORKTREE> <name>)
-#   TAG     prefix of the outputs under gpurun_out/
+#   OUT     directory of the outputs (default ./out)
+#   TAG     prefix of the outputs under $OUT/
 # Usage: STEPS=parity,ab_c3 LIBS="base new" TAG=r05x bash tools/gpu_session.sh
 set -euo pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+export OUT=${OUT:-out}
+mkdir -p "$OUT"
 STEPS=${STEPS:-suite,ab_c3,latency}
 LIBS=${LIBS:-}
 TAG=${TAG:-sess}
@@ -46,27 +48,27 @@ for step in ${STEPS//,/ }; do
   case $step in
     suite)
       timeout -k 10 700 python3 -u -m pytest tests/ -m gpu -x -q --timeout 300 --timeout-method thread \
-        > gpurun_out/${TAG}_gpu_suite.txt 2>&1 || { echo SUITE FAILED; tail -40 gpurun_out/${TAG}_gpu_suite.txt; exit 1; }
-      tail -1 gpurun_out/${TAG}_gpu_suite.txt ;;
+        > $OUT/${TAG}_gpu_suite.txt 2>&1 || { echo SUITE FAILED; tail -40 $OUT/${TAG}_gpu_suite.txt; exit 1; }
+      tail -1 $OUT/${TAG}_gpu_suite.txt ;;
     parity)
       timeout -k 10 600 python3 -u -m pytest tests/test_gpu_parity.py tests/test_gpu_random_parity.py \
         tests/test_gpu_rotation.py tests/test_gpu_drain.py tests/test_gpu_rare_channels.py -q -x --timeout 300 \
-        --timeout-method thread > gpurun_out/${TAG}_parity.txt 2>&1 || { echo PARITY FAILED; tail -30 gpurun_out/${TAG}_parity.txt; exit 1; }
-      tail -1 gpurun_out/${TAG}_parity.txt ;;
+        --timeout-method thread > $OUT/${TAG}_parity.txt 2>&1 || { echo PARITY FAILED; tail -30 $OUT/${TAG}_parity.txt; exit 1; }
+      tail -1 $OUT/${TAG}_parity.txt ;;
     ab_c3)
-      bash tools/ab_libs.sh $LIBS 2>&1 | grep "^{" | tee gpurun_out/${TAG}_ab_c3.txt ;;
+      bash tools/ab_libs.sh $LIBS 2>&1 | grep "^{" | tee $OUT/${TAG}_ab_c3.txt ;;
     latency)
-      bash tools/ab_latency.sh $LIBS 2>&1 | tail -$((6 * $(echo $LIBS | wc -w))) | tee gpurun_out/${TAG}_ab_latency.txt ;;
+      bash tools/ab_latency.sh $LIBS 2>&1 | tail -$((6 * $(echo $LIBS | wc -w))) | tee $OUT/${TAG}_ab_latency.txt ;;
     pmc)
       for n in $LIBS; do
         ECDNA_SSA_LIB=$L/$n/libecdna_ssa.so timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS \
-          SQ_WAVES SQ_BUSY_CYCLES -T --output-format csv -d gpurun_out/${TAG}_pmc_$n -o pmc -- python3 bench.py --steps 1 \
-          --warmup 0 --no-cpu-baseline > gpurun_out/${TAG}_pmc_$n.log 2>&1
-        python3 tools/ab_pmc_summary.py gpurun_out/${TAG}_pmc_$n gpurun_out/${TAG}_pmc_$n.log "$n" | tee -a gpurun_out/${TAG}_pmc.txt
+          SQ_WAVES SQ_BUSY_CYCLES -T --output-format csv -d $OUT/${TAG}_pmc_$n -o pmc -- python3 bench.py --steps 1 \
+          --warmup 0 --no-cpu-baseline > $OUT/${TAG}_pmc_$n.log 2>&1
+        python3 tools/ab_pmc_summary.py $OUT/${TAG}_pmc_$n $OUT/${TAG}_pmc_$n.log "$n" | tee -a $OUT/${TAG}_pmc.txt
       done ;;
     rcp)
-      rc=0; timeout -k 10 120 ecdna-evo_amd/bin/rcp_check > gpurun_out/${TAG}_rcp_check.json || rc=$?
-      cat gpurun_out/${TAG}_rcp_check.json; [ $rc -le 1 ] || exit 1 ;;  # (1: mismatches found, reported)
+      rc=0; timeout -k 10 120 ecdna-evo_amd/bin/rcp_check > $OUT/${TAG}_rcp_check.json || rc=$?
+      cat $OUT/${TAG}_rcp_check.json; [ $rc -le 1 ] || exit 1 ;;  # (1: mismatches found, reported)
     stall)  # the SQ wave-cycle split (waiting on waitcnt / issue-stalled / issuing) and the LDS, branch and fetch counters
       for n in $LIBS; do
         k=0
@@ -75,17 +77,17 @@ for step in ${STEPS//,/ }; do
                     "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_FLAT SQ_INST_CYCLES_SALU SQ_WAVES"; do
           k=$((k + 1))
           ECDNA_SSA_LIB=$L/$n/libecdna_ssa.so timeout -s KILL 300 rocprofv3 --pmc $pass -T --output-format csv \
-            -d gpurun_out/${TAG}_stall_${n}_$k -o pmc -- python3 bench.py ${STALL_ARGS:-} --steps 1 --warmup 0 --no-cpu-baseline \
-            > gpurun_out/${TAG}_stall_${n}_$k.log 2>&1
-          python3 tools/ab_pmc_summary.py gpurun_out/${TAG}_stall_${n}_$k gpurun_out/${TAG}_stall_${n}_$k.log "$n" all \
-            | tee -a gpurun_out/${TAG}_stall.txt
+            -d $OUT/${TAG}_stall_${n}_$k -o pmc -- python3 bench.py ${STALL_ARGS:-} --steps 1 --warmup 0 --no-cpu-baseline \
+            > $OUT/${TAG}_stall_${n}_$k.log 2>&1
+          python3 tools/ab_pmc_summary.py $OUT/${TAG}_stall_${n}_$k $OUT/${TAG}_stall_${n}_$k.log "$n" all \
+            | tee -a $OUT/${TAG}_stall.txt
         done
       done ;;
     c3s)
-      timeout -k 10 300 python3 -u tools/c3_strong.py > gpurun_out/${TAG}_c3_strong.jsonl 2> gpurun_out/${TAG}_c3_strong.err
-      grep makespan gpurun_out/${TAG}_c3_strong.jsonl ;;
+      timeout -k 10 300 python3 -u tools/c3_strong.py > $OUT/${TAG}_c3_strong.jsonl 2> $OUT/${TAG}_c3_strong.err
+      grep makespan $OUT/${TAG}_c3_strong.jsonl ;;
     c3s_knobs)
-      O=gpurun_out/${TAG}_c3_strong_knobs.txt; : > $O
+      O=$OUT/${TAG}_c3_strong_knobs.txt; : > $O
       knob() {  # label, env...
         local label=$1; shift
         env "$@" C3S_RANKS=0 C3S_REPS=3 timeout -k 10 200 python3 tools/c3_strong.py 2>/dev/null | python3 -c "
@@ -103,35 +105,35 @@ for l in sys.stdin:
       knob admit8 C3S_GPUS=2 ECDNA_SSA_ADMIT_X8=8
       cat $O ;;
     c4s)
-      bash tools/c4_shards.sh | tee gpurun_out/${TAG}_c4_shards.txt ;;
+      bash tools/c4_shards.sh | tee $OUT/${TAG}_c4_shards.txt ;;
     c4split)
-      timeout -k 10 600 python3 -u tools/c4_split.py > gpurun_out/${TAG}_c4_split.jsonl 2> gpurun_out/${TAG}_c4_split.err
-      cut -c1-200 gpurun_out/${TAG}_c4_split.jsonl ;;
+      timeout -k 10 600 python3 -u tools/c4_split.py > $OUT/${TAG}_c4_split.jsonl 2> $OUT/${TAG}_c4_split.err
+      cut -c1-200 $OUT/${TAG}_c4_split.jsonl ;;
     cyc)
       for n in $LIBS; do
         C=${CYC:-c3s8,c2,c3}
         for cfg in ${C//,/ }; do
-          ECDNA_SSA_LIB=$L/$n/libecdna_ssa.so timeout -k 10 300 python3 tools/cycle_stats.py $cfg | tee -a gpurun_out/${TAG}_cyc.jsonl
+          ECDNA_SSA_LIB=$L/$n/libecdna_ssa.so timeout -k 10 300 python3 tools/cycle_stats.py $cfg | tee -a $OUT/${TAG}_cyc.jsonl
         done
       done ;;
     ab_ref)
-      bash tools/ab_ref.sh $LIBS | tee gpurun_out/${TAG}_ab_ref.txt ;;
+      bash tools/ab_ref.sh $LIBS | tee $OUT/${TAG}_ab_ref.txt ;;
     cyc_ref)
       for n in $LIBS; do
-        ECDNA_SSA_LIB=$L/$n/libecdna_ssa.so timeout -k 10 300 python3 tools/cycle_stats_ref.py c3 | tee -a gpurun_out/${TAG}_cyc_ref.jsonl
-        ECDNA_SSA_LIB=$L/$n/libecdna_ssa.so timeout -k 10 300 python3 tools/cycle_stats_ref.py c2 | tee -a gpurun_out/${TAG}_cyc_ref.jsonl
+        ECDNA_SSA_LIB=$L/$n/libecdna_ssa.so timeout -k 10 300 python3 tools/cycle_stats_ref.py c3 | tee -a $OUT/${TAG}_cyc_ref.jsonl
+        ECDNA_SSA_LIB=$L/$n/libecdna_ssa.so timeout -k 10 300 python3 tools/cycle_stats_ref.py c2 | tee -a $OUT/${TAG}_cyc_ref.jsonl
       done ;;
     c5curve)
       for G in 8 4 2 1; do
         PROBE_FLAGS=0x20 PROBE_KMAX=64 PROBE_GPUS=$G timeout -k 10 200 python3 tools/probe_configs.py c5 2>/dev/null | \
-          python3 -c "import json,sys; d=json.loads(sys.stdin.read()); i=d['instance']; print('c5 G=$G rank0', round(d['stepper_ms'],1), 'ms', 'replicates', d['replicates'], 'events', d['events'], 'K', i['bin_kmax'], 'paired', i['paired'], 'schedule', i['schedule'], 'errors', d['errors'])" | tee -a gpurun_out/${TAG}_c5curve.txt
+          python3 -c "import json,sys; d=json.loads(sys.stdin.read()); i=d['instance']; print('c5 G=$G rank0', round(d['stepper_ms'],1), 'ms', 'replicates', d['replicates'], 'events', d['events'], 'K', i['bin_kmax'], 'paired', i['paired'], 'schedule', i['schedule'], 'errors', d['errors'])" | tee -a $OUT/${TAG}_c5curve.txt
       done ;;
     inject)
       for n in $LIBS; do
-        ECDNA_SSA_LIB=$L/$n/libecdna_ssa.so timeout -k 10 120 python3 tools/inject_check.py | tee -a gpurun_out/${TAG}_inject.jsonl
+        ECDNA_SSA_LIB=$L/$n/libecdna_ssa.so timeout -k 10 120 python3 tools/inject_check.py | tee -a $OUT/${TAG}_inject.jsonl
       done ;;
     pmc_ref)
-      O=gpurun_out/${TAG}_pmc_ref; mkdir -p $O
+      O=$OUT/${TAG}_pmc_ref; mkdir -p $O
       timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR \
         SQ_INSTS_BRANCH SQ_WAVES SQ_BUSY_CYCLES -T --output-format csv -d $O/p1 -o pmc -- python3 bench.py --store rows \
         --draws reference --steps 1 --warmup 0 --no-cpu-baseline > $O/p1.log 2>&1
@@ -146,22 +148,22 @@ for l in sys.stdin:
     prof_bins|prof_rows)
       bash tools/gpu_profile.sh ${TAG}_${step#prof_} ${step#prof_} ;;
     bench_ref)
-      timeout -k 10 600 python3 bench.py --store rows --draws reference > gpurun_out/${TAG}_bench_ref_c3.json \
-        2> gpurun_out/${TAG}_bench_ref_c3.err
-      cut -c1-300 gpurun_out/${TAG}_bench_ref_c3.json ;;
+      timeout -k 10 600 python3 bench.py --full --store rows --draws reference > $OUT/${TAG}_bench_ref_c3.json \
+        2> $OUT/${TAG}_bench_ref_c3.err
+      cut -c1-300 $OUT/${TAG}_bench_ref_c3.json ;;
     bench_c3)
-      timeout -k 10 600 python3 bench.py > gpurun_out/${TAG}_bench_c3.json 2> gpurun_out/${TAG}_bench_c3.err
-      cut -c1-300 gpurun_out/${TAG}_bench_c3.json ;;
+      timeout -k 10 600 python3 bench.py --full > $OUT/${TAG}_bench_c3.json 2> $OUT/${TAG}_bench_c3.err
+      cut -c1-300 $OUT/${TAG}_bench_c3.json ;;
     bench_rows)
-      timeout -k 10 600 python3 bench.py --store rows > gpurun_out/${TAG}_bench_rows_c3.json 2> gpurun_out/${TAG}_bench_rows_c3.err
-      cut -c1-300 gpurun_out/${TAG}_bench_rows_c3.json ;;
+      timeout -k 10 600 python3 bench.py --full --store rows > $OUT/${TAG}_bench_rows_c3.json 2> $OUT/${TAG}_bench_rows_c3.err
+      cut -c1-300 $OUT/${TAG}_bench_rows_c3.json ;;
     smoke)
-      timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.txt 2>&1
-      tail -3 gpurun_out/${TAG}_smoke.txt ;;
+      timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.txt 2>&1
+      tail -3 $OUT/${TAG}_smoke.txt ;;
     bench_c2|bench_c4|bench_c5)
-      timeout -k 10 900 python3 bench.py --workload ${step#bench_} --steps 2 --warmup 1 > gpurun_out/${TAG}_${step}.json \
-        2> gpurun_out/${TAG}_${step}.err
-      cut -c1-300 gpurun_out/${TAG}_${step}.json ;;
+      timeout -k 10 900 python3 bench.py --full --workload ${step#bench_} --steps 2 --warmup 1 > $OUT/${TAG}_${step}.json \
+        2> $OUT/${TAG}_${step}.err
+      cut -c1-300 $OUT/${TAG}_${step}.json ;;
     *) echo "unknown step $step"; exit 1 ;;
   esac
 done
