@@ -11,6 +11,10 @@ The reference has no golden vectors, so these pin the oracle's semantics to math
   * k1 ~ Binomial(2k, 1/2);
   * the philox mapping and the reference-semantics mapping (ChaCha8 + first-reaction + BTPE)
     give the same law of the final state.
+
+Finer and wider law tests live in tests/test_exact_laws.py (this oracle, every draw path, 2^20 replicates against
+an exact enumeration of small populations, tests/exact_law.py) and tests/test_gpu_exact_laws.py (the HIP engine
+against the same laws).
 """
 import numpy as np
 import pytest
