@@ -70,6 +70,11 @@ int validate(const ecdna_ssa_params_t* p) {
     }
     if (p->reps_per_set == 0) return fail(ECDNA_E_INVALID, "reps_per_set must be >= 1");
     if (p->reserved0) return fail(ECDNA_E_INVALID, "reserved0 must be 0");
+    if (p->reserved1) return fail(ECDNA_E_INVALID, "reserved1 must be 0");
+    if (p->subsample_cells && !(p->flags & ECDNA_FLAG_REP_STATS))
+        return fail(ECDNA_E_INVALID, "subsample_cells needs ECDNA_FLAG_REP_STATS");
+    if (p->subsample_cells > ecdna::kMaxSubsampleCells)
+        return fail(ECDNA_E_INVALID, "subsample_cells must be <= 4096");
     // (bit 31 is the library's internal snapshot bit, kFlagSnapshotsRt: a caller setting it, or any other unknown bit,
     // would silently select another kernel instance)
     if (p->flags & ~(uint32_t)ECDNA_FLAG_ALL) return fail(ECDNA_E_INVALID, "unknown bits in flags");
@@ -206,6 +211,9 @@ struct ecdna_ssa_ctx {
     double target_mean = 0.0, target_entropy = 0.0, target_freq = 0.0;
     double* d_target_cdf = nullptr;
     ecdna_rep_stats_t* d_stats = nullptr;
+    // end-of-run subsampling (subsample_cells > 0): the samples' statistics [n] and histogram [n_sets][bins]
+    ecdna_rep_stats_t* d_sample_stats = nullptr;
+    uint64_t* d_sample_hist = nullptr;
     // device buffers
     float4* d_rates = nullptr;
     uint16_t* d_init = nullptr;
@@ -288,6 +296,8 @@ void free_ctx(ecdna_ssa_ctx* c) {
     (void)hipFree(c->d_snap_rows);
     (void)hipFree(c->d_target_cdf);
     (void)hipFree(c->d_stats);
+    (void)hipFree(c->d_sample_stats);
+    (void)hipFree(c->d_sample_hist);
     (void)hipFree(c->d_rows);
     (void)hipFree(c->d_bags);
     (void)hipFree(c->d_summ);
@@ -462,6 +472,10 @@ int ecdna_ssa_ctx_create(const ecdna_ssa_params_t* p, ecdna_ssa_ctx** out) {
     // outputs
     const uint64_t n = p->n_replicates;
     const uint64_t nb = (uint64_t)p->n_param_sets * p->hist_bins;
+    if (p->subsample_cells) {
+        CTX_TRY(hipMalloc(&c->d_sample_stats, std::max<uint64_t>(n, 1) * sizeof(ecdna_rep_stats_t)));
+        CTX_TRY(hipMalloc(&c->d_sample_hist, nb * sizeof(uint64_t)));
+    }
     CTX_TRY(hipMalloc(&c->d_hist_own, nb * sizeof(uint64_t)));
     CTX_TRY(hipMalloc(&c->d_tot_own, p->n_param_sets * sizeof(ecdna_totals_t)));
     CTX_TRY(hipMemset(c->d_hist_own, 0, nb * sizeof(uint64_t)));
@@ -696,6 +710,7 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
     const uint64_t nb = (uint64_t)p.n_param_sets * p.hist_bins;
     HIP_TRY(hipMemsetAsync(c->d_hist, 0, nb * sizeof(uint64_t), st));
     HIP_TRY(hipMemsetAsync(c->d_tot, 0, p.n_param_sets * sizeof(ecdna_totals_t), st));
+    if (c->d_sample_hist) HIP_TRY(hipMemsetAsync(c->d_sample_hist, 0, nb * sizeof(uint64_t), st));
     if (!c->chunks.empty())
         HIP_TRY(hipMemsetAsync(c->d_heads, 0, c->chunks.size() * sizeof(uint32_t), st));
     if (c->d_snap_meta)
@@ -802,6 +817,35 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
         hsa.bag_c32 = (uint32_t)c->bin_c32;
         const uint32_t hblocks = (ch.n + rpb - 1) / rpb;
         HIP_TRY(ecdna::launch_hist(hsa, hblocks, st));
+        if (p.subsample_cells) {  // the samples' statistics and histogram, from the same final state
+            ecdna::SubsampleArgs sa{};
+            sa.rows = hsa.rows;
+            sa.summaries = hsa.summaries;
+            sa.stats = c->d_sample_stats + ch.first;
+            sa.sample_hist = c->d_sample_hist;
+            sa.row_stride = hsa.row_stride;
+            sa.rid0 = hsa.rid0;
+            sa.rid_stride = hsa.rid_stride;
+            sa.reps_per_set = hsa.reps_per_set;
+            sa.seed = p.seed;
+            sa.n = ch.n;
+            sa.bins = p.hist_bins;
+            sa.m = p.subsample_cells;
+            sa.table_slots = ecdna::subsample_table_slots(p.subsample_cells);
+            sa.has_target = hsa.has_target;
+            sa.target_cdf = hsa.target_cdf;
+            sa.target_mean = hsa.target_mean;
+            sa.target_entropy = hsa.target_entropy;
+            sa.target_freq = hsa.target_freq;
+            sa.bags = hsa.bags;
+            sa.bag_k = hsa.bag_k;
+            sa.bag_c32 = hsa.bag_c32;
+            // one wave per replicate: a workgroup's share is at least one replicate per wave, at most the histogram
+            // pass's (which bounds the sets a workgroup walks)
+            const uint32_t sw = ecdna::subsample_waves(sa.bins, sa.bag_k, sa.table_slots, nullptr);
+            sa.reps_per_block = std::max<uint32_t>(sw, (ch.n + hist_blocks_max - 1) / hist_blocks_max);
+            HIP_TRY(ecdna::launch_subsample(sa, (ch.n + sa.reps_per_block - 1) / sa.reps_per_block, st));
+        }
         HIP_TRY(hipEventRecord(ch.ev[2], st));
     }
     c->last_stream = st;
@@ -976,6 +1020,22 @@ int ecdna_ssa_ctx_download_stats(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out) {
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->last_stream));
     HIP_TRY(hipMemcpy(out, c->d_stats, c->p.n_replicates * sizeof(ecdna_rep_stats_t), hipMemcpyDeviceToHost));
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_download_sample(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats, uint64_t* out_sample_hist) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!c->d_sample_hist) return fail(ECDNA_E_STATE, "the sample needs subsample_cells > 0");
+    if (!c->launched) return fail(ECDNA_E_STATE, "download before launch");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    const ecdna_ssa_params_t& p = c->p;
+    if (out_stats && p.n_replicates)
+        HIP_TRY(hipMemcpy(out_stats, c->d_sample_stats, p.n_replicates * sizeof(ecdna_rep_stats_t),
+                          hipMemcpyDeviceToHost));
+    if (out_sample_hist)
+        HIP_TRY(hipMemcpy(out_sample_hist, c->d_sample_hist,
+                          (uint64_t)p.n_param_sets * p.hist_bins * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return ECDNA_OK;
 }
 

@@ -103,6 +103,33 @@ struct HistArgs {
     uint32_t bag_c32;
 };
 
+// End-of-run subsampling pass over one chunk (ssa_subsample.hip; params.subsample_cells > 0): per replicate, the
+// statistics of a sample of m cells of its final state, and the per-set sum of the samples' histograms.
+struct SubsampleArgs {
+    const uint16_t* rows;
+    const ecdna_rep_summary_t* summaries; // chunk-offset
+    ecdna_rep_stats_t* stats;             // chunk-offset: the samples' statistics
+    uint64_t* sample_hist;                // [n_sets][bins]
+    uint64_t row_stride;
+    uint64_t rid0;
+    uint64_t rid_stride;                  // >= 1
+    uint64_t reps_per_set;
+    uint64_t seed;
+    uint32_t n;
+    uint32_t bins;
+    uint32_t reps_per_block;
+    uint32_t m;                           // sample size (cells), 1 .. kMaxSubsampleCells
+    uint32_t table_slots;                 // per-wave table of drawn positions: subsample_table_slots(m)
+    uint32_t has_target;
+    const double* target_cdf;
+    double target_mean, target_entropy, target_freq;
+    // bin store: per-replicate counters [n][bag_k] (u16, or u32 when bag_c32); nullptr = rows only
+    const void* bags;
+    uint32_t bag_k;
+    uint32_t bag_c32;
+};
+
+constexpr uint32_t kMaxSubsampleCells = 4096;  // LDS: 8 B of table per sampled cell and wave (<= 32 KiB)
 constexpr int kStepperBlock = 256;
 constexpr int kBinWideBlock = 64;  // bin store with 256 bins
 constexpr int kHistBlock = 256;
@@ -137,6 +164,11 @@ int bin_stepper_block(uint32_t bin_k);
 hipError_t launch_bin_stepper(const StepperArgs& a, int birth_death, int segregation, uint32_t bin_k, int c32, int ilp,
                               uint32_t blocks, hipStream_t stream);
 hipError_t launch_hist(const HistArgs& a, uint32_t blocks, hipStream_t stream);
+// The subsampling pass (ssa_subsample.hip): 2 * pow2ceil(m) table slots per wave; 1, 2 or 4 waves per workgroup, as
+// many as keep its dynamic LDS (lds_bytes) within 64 KiB; one wave per replicate.
+uint32_t subsample_table_slots(uint32_t m);
+uint32_t subsample_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, size_t* lds_bytes);
+hipError_t launch_subsample(const SubsampleArgs& a, uint32_t blocks, hipStream_t stream);
 // The reference-draws stepper (row store; ssa_refdraws.hip)
 const void* refdraws_kernel(int birth_death, int segregation);
 int refdraws_block();

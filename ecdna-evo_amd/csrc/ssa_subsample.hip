@@ -1,0 +1,334 @@
+// ssa_subsample.hip — end-of-run subsampling fused with the per-replicate ABC statistics (gfx950).
+//
+// The reference ends every run with into_subsampled(nb, &mut rng) (src/main.rs:110-123, 184-197): a patient's
+// data is a sample of some hundreds of cells, never the whole tumour, and the statistics an ABC caller compares
+// are those of the sample. This pass draws each replicate's sample of subsample_cells cells from its final
+// state where that state already lies (bin counters in `bags`, large-k cells in `rows`), right after ssa_hist
+// and on the same stream, and writes the sample's ecdna_rep_stats_t and the per-set sum of the samples'
+// histograms. The sample's law is subsample mapping v1 (include/ecdna_ssa.h);
+// tests/subsample_law.py restates it in numpy.
+//
+// One wave per replicate, as ssa_hist<true, BAG>. Per wave in LDS: the replicate's histogram (u32 per bin), the
+// inclusive prefix sums of its bin counters (position -> copy number), and an open-addressing table of the
+// positions drawn so far (u32, 0xffffffff = empty), which decides whether a draw is new.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ssa_device.hpp"
+#include "ssa_launch.h"
+
+#pragma clang fp contract(off)
+
+namespace ecdna {
+
+namespace {
+
+constexpr uint32_t kSubEmpty = 0xffffffffu;
+constexpr uint32_t kSubTag = 0xC0000000u;      // Philox counter word 1 of draw block t: kSubTag | t
+constexpr uint32_t kSubMaxDraws = 1u << 16;    // the guard: draws per replicate
+constexpr uint32_t kSubMaxBlocks = 1024;       // Philox blocks per draw (each rejects with p < 2^-4: unreachable)
+constexpr uint32_t kSubBlock = 256;
+
+__device__ __forceinline__ void sub_wave_sync_lds() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS accesses have completed
+    __builtin_amdgcn_wave_barrier();
+}
+
+template <typename T>
+__device__ __forceinline__ T sub_wave_sum(T x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+__device__ __forceinline__ double sub_wave_max(double x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o, 64));
+    return x;
+}
+
+// Draw i of replicate (rid_lo, rid_hi): a Lemire draw below N. Philox block t = 0, 1, ... on counter
+// (i, kSubTag | t, rid lo, rid hi); its four words are tried in order, word x gives p = x * N and is accepted as
+// p >> 32 when the low half is >= thr = (2^32 - N) mod N.
+__device__ __forceinline__ uint32_t sub_draw(uint32_t i, uint32_t N, uint32_t thr, uint32_t rid_lo, uint32_t rid_hi,
+                                             uint32_t k0, uint32_t k1, bool& fail) {
+    for (uint32_t t = 0; t < kSubMaxBlocks; ++t) {
+        const uint4 w = philox4x32_10(make_uint4(i, kSubTag | t, rid_lo, rid_hi), k0, k1);
+        const uint32_t x[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t p = (uint64_t)x[j] * N;
+            if ((uint32_t)p >= thr) return (uint32_t)(p >> 32);
+        }
+    }
+    fail = true;
+    return 0u;
+}
+
+// BAG as in ssa_hist: 0 = rows only; 1 / 2 = u16 / u32 bin counters bags[q][bag_k] for copy numbers 1..bag_k plus
+// the large-k cells at the head of the row.
+template <int BAG>
+__global__ void __launch_bounds__(kSubBlock) ssa_subsample(const SubsampleArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long lds[];
+    unsigned long long* hb = lds;  // [bins] the workgroup's sum of sample histograms (one parameter set at a time)
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t nw = blockDim.x >> 6;
+    const uint32_t wave_words = a.bins + a.bag_k + a.table_slots;
+    uint32_t* wh = reinterpret_cast<uint32_t*>(lds + a.bins) + (size_t)wave * wave_words;  // [bins]
+    uint32_t* pre = wh + a.bins;                                                           // [bag_k]
+    uint32_t* tab = pre + a.bag_k;                                                         // [table_slots]
+    const uint32_t r_begin = blockIdx.x * a.reps_per_block;
+    if (r_begin >= a.n) return;
+    const uint32_t r_end = min(a.n, r_begin + a.reps_per_block);
+    const uint32_t last = a.bins - 1;
+    const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
+
+    uint32_t r = r_begin;
+    while (r < r_end) {
+        // local replicates r .. seg_end - 1 share a parameter set (as ssa_hist)
+        const uint64_t set = (a.rid0 + (uint64_t)r * a.rid_stride) / a.reps_per_set;
+        const uint64_t set_end_rid = (set + 1) * a.reps_per_set;
+        const uint64_t in_set = (set_end_rid - a.rid0 + a.rid_stride - 1) / a.rid_stride;
+        const uint32_t seg_end = (uint32_t)min((uint64_t)r_end, in_set);
+        for (uint32_t b = tid; b < a.bins; b += blockDim.x) hb[b] = 0ull;
+        __syncthreads();
+        for (uint32_t q = r + wave; q < seg_end; q += nw) {
+            const ecdna_rep_summary_t* s = a.summaries + q;
+            const uint64_t nm = s->nminus;
+            const uint32_t np = (uint32_t)s->nplus;
+            const uint64_t cells_all = nm + (uint64_t)np;
+            const uint64_t rid = a.rid0 + (uint64_t)q * a.rid_stride;
+            const uint16_t* row = a.rows + (uint64_t)q * a.row_stride;
+            // the sample is the whole population (m >= N), the picked positions (m' = m) or what they leave (m' < m)
+            const bool whole = (uint64_t)a.m >= cells_all;
+            bool bad = !whole && cells_all >= 0xffffffffull;  // positions are u32, 0xffffffff marks an empty slot
+            const uint32_t N = (uint32_t)cells_all;
+            const uint32_t mp = (whole || bad) ? 0u : min(a.m, N - a.m);
+            const bool comp = mp != a.m;
+            const bool need_full = whole || comp;
+            for (uint32_t b = lane; b < a.bins; b += 64u) wh[b] = 0u;
+            sub_wave_sync_lds();
+
+            // 1. counters: prefix sums for the position -> k lookup, and (whole / complement) the full histogram
+            uint64_t ksum = 0;  // sum of k over the full population (need_full)
+            uint32_t small = 0;
+            if (BAG) {
+                for (uint32_t base = 0; base < a.bag_k; base += 64u) {
+                    const uint32_t b = base + lane;
+                    uint32_t cnt = 0;
+                    if (b < a.bag_k) {
+                        const uint64_t o = (uint64_t)q * a.bag_k + b;
+                        cnt = BAG == 2 ? reinterpret_cast<const uint32_t*>(a.bags)[o]
+                                       : (uint32_t)reinterpret_cast<const uint16_t*>(a.bags)[o];
+                    }
+                    if (need_full && cnt) {
+                        const uint32_t kk = b + 1u;
+                        atomicAdd(&wh[kk < last ? kk : last], cnt);
+                        ksum += (uint64_t)kk * cnt;
+                    }
+                    uint32_t scan = cnt;  // inclusive prefix sum over the wave
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const uint32_t y = __shfl_up(scan, o, 64);
+                        if ((int)lane >= o) scan += y;
+                    }
+                    if (b < a.bag_k) pre[b] = small + scan;
+                    small += __shfl(scan, 63, 64);
+                }
+                if (!whole && small > np) bad = true;  // the counters hold more cells than the summary
+            }
+            // cells held in the row (never trust counters past the row, nor the summary past the row's memory)
+            const uint32_t nrow = (uint32_t)min((uint64_t)(np >= small ? np - small : 0u), a.row_stride);
+            if (need_full) {
+                for (uint32_t c = lane * 8u; c < nrow; c += 512u) {
+                    const uint4 v = *reinterpret_cast<const uint4*>(row + c);
+                    const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        if (c + (uint32_t)j < nrow) {
+                            const uint32_t kk = (wv[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+                            atomicAdd(&wh[kk < last ? kk : last], 1u);
+                            ksum += kk;
+                        }
+                    }
+                }
+                if (lane == 0) atomicAdd(&wh[0], (uint32_t)nm);
+            }
+
+            // 2.-4. draws until m' distinct positions have appeared; every new one is looked up and counted
+            uint64_t psum = 0;  // sum of k over the picked positions
+            if (!whole && !bad) {
+                // table: 2 * pow2ceil(m') slots (load <= 1/2), hashed by the top bits of a multiplicative hash
+                const uint32_t lg = mp > 1u ? 32u - (uint32_t)__clz(mp - 1u) : 0u;
+                const uint32_t tsize = 2u << lg;
+                const uint32_t sh = 31u - lg;
+                bad = tsize > a.table_slots;
+                const uint32_t tclear = bad ? 0u : tsize;
+                for (uint32_t b = lane; b < tclear; b += 64u) tab[b] = kSubEmpty;
+                sub_wave_sync_lds();
+                const uint32_t thr = (0u - N) % N;
+                const uint32_t rid_lo = (uint32_t)rid, rid_hi = (uint32_t)(rid >> 32);
+                bool lane_bad = false;
+                uint32_t count = bad ? mp : 0u, base = 0;
+                while (count < mp && base < kSubMaxDraws) {
+                    // the next draws, one per lane: at most as many as positions are still missing, so every new
+                    // draw of the batch is one of the first m' and the table never holds more than m' positions
+                    const uint32_t nact = min(64u, min(mp - count, kSubMaxDraws - base));
+                    const bool active = lane < nact;
+                    uint32_t v = kSubEmpty;
+                    if (active) v = sub_draw(base + lane, N, thr, rid_lo, rid_hi, k0, k1, lane_bad);
+                    // a draw that repeats an earlier one of its batch is not new, whichever lane reaches LDS first
+                    bool dup = false;
+                    for (uint32_t j = 0; j + 1u < nact; ++j) {
+                        const uint32_t vj = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j);
+                        dup = dup || (j < lane && vj == v);
+                    }
+                    // the others are distinct: each is new iff the table did not hold it before the batch
+                    bool isnew = false;
+                    if (active && !dup && !lane_bad) {
+                        uint32_t sl = (v * 0x9E3779B1u) >> sh;
+                        bool placed = false;
+                        for (uint32_t probe = 0; probe < tsize; ++probe) {
+                            const uint32_t old = atomicCAS(&tab[sl], kSubEmpty, v);
+                            if (old == kSubEmpty || old == v) {
+                                isnew = old == kSubEmpty;
+                                placed = true;
+                                break;
+                            }
+                            sl = (sl + 1u) & (tsize - 1u);
+                        }
+                        if (!placed) lane_bad = true;
+                    }
+                    if (isnew) {
+                        // position -> copy number, in download order: N- cells, the counters k ascending, the row
+                        uint32_t kk = 0;
+                        bool ok = true;
+                        if ((uint64_t)v >= nm) {
+                            const uint32_t u = v - (uint32_t)nm;
+                            if (BAG && u < small) {
+                                uint32_t lo = 0, hi = a.bag_k - 1u;  // the first b with pre[b] > u
+                                while (lo < hi) {
+                                    const uint32_t mid = (lo + hi) >> 1;
+                                    if (pre[mid] > u)
+                                        hi = mid;
+                                    else
+                                        lo = mid + 1u;
+                                }
+                                kk = lo + 1u;
+                            } else {
+                                const uint32_t j = u - small;
+                                ok = j < nrow;  // a position the counters and the row cannot account for
+                                if (ok) kk = row[j];
+                            }
+                        }
+                        if (ok) {
+                            const uint32_t bin = kk < last ? kk : last;
+                            if (comp)
+                                atomicSub(&wh[bin], 1u);
+                            else
+                                atomicAdd(&wh[bin], 1u);
+                            psum += kk;
+                        } else {
+                            lane_bad = true;
+                        }
+                    }
+                    count += (uint32_t)__popcll(__ballot(isnew));
+                    base += nact;
+                    sub_wave_sync_lds();
+                }
+                bad = bad || count < mp || __any(lane_bad);
+            }
+            sub_wave_sync_lds();
+
+            // 5. statistics of the sample histogram: the wave routine of ssa_hist<true, BAG> (ssa_kernels.hip), copied
+            // so that the timed kernels' translation unit stays as it is
+            ksum = sub_wave_sum(ksum);
+            psum = sub_wave_sum(psum);
+            const uint64_t cells = bad ? 0ull : (whole ? cells_all : (uint64_t)a.m);
+            const uint64_t ks_sum = whole ? ksum : (comp ? ksum - psum : psum);
+            const uint64_t nplus_s = whole ? (uint64_t)np : cells - (uint64_t)wh[0];
+            const double inv = cells ? 1.0 / (double)cells : 0.0;
+            double carry = 0.0, ent = 0.0, ks = 0.0;
+            if (!bad) {
+                for (uint32_t base = 0; base < a.bins; base += 64u) {
+                    const uint32_t b = base + lane;
+                    const uint32_t cnt = b < a.bins ? wh[b] : 0u;
+                    if (cnt) atomicAdd(&hb[b], (unsigned long long)cnt);
+                    const double p = (double)cnt * inv;
+                    if (cnt) ent -= p * log(p);
+                    double scan = p;  // inclusive prefix sum over the wave
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const double y = __shfl_up(scan, o, 64);
+                        if ((int)lane >= o) scan += y;
+                    }
+                    if (a.has_target && b < a.bins) ks = fmax(ks, fabs(carry + scan - a.target_cdf[b]));
+                    carry += __shfl(scan, 63, 64);
+                }
+            }
+            ent = sub_wave_sum(ent);
+            ks = sub_wave_max(ks);
+            if (lane == 0) {
+                ecdna_rep_stats_t st;
+                if (bad) {  // the guard, or a state the counters cannot account for: all-zero sample statistics
+                    st.cells = 0;
+                    st.mean = st.entropy = st.frequency = st.ks = 0.0;
+                    st.mean_rel = st.entropy_rel = st.frequency_diff = 0.0;
+                } else {
+                    st.cells = cells;
+                    st.mean = cells ? (double)ks_sum * inv : 0.0;
+                    st.entropy = ent;
+                    st.frequency = cells ? (double)nplus_s * inv : 0.0;
+                    st.ks = a.has_target ? (cells ? ks : 1.0) : 0.0;
+                    const double dm = fabs(st.mean - a.target_mean), de = fabs(st.entropy - a.target_entropy);
+                    st.mean_rel = a.has_target ? (a.target_mean > 0.0 ? dm / a.target_mean : dm) : 0.0;
+                    st.entropy_rel = a.has_target ? (a.target_entropy > 0.0 ? de / a.target_entropy : de) : 0.0;
+                    st.frequency_diff = a.has_target ? fabs(st.frequency - a.target_freq) : 0.0;
+                }
+                a.stats[q] = st;
+            }
+            sub_wave_sync_lds();  // wh is zeroed again for the wave's next replicate
+        }
+        __syncthreads();
+        for (uint32_t b = tid; b < a.bins; b += blockDim.x)
+            if (hb[b]) atomicAdd((unsigned long long*)&a.sample_hist[set * a.bins + b], hb[b]);
+        __syncthreads();
+        r = seg_end;
+    }
+}
+
+}  // namespace
+
+uint32_t subsample_table_slots(uint32_t m) {
+    uint32_t p = 1;
+    while (p < m) p <<= 1;
+    return 2u * p;
+}
+
+uint32_t subsample_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, size_t* lds_bytes) {
+    // 1, 2 or 4 waves per workgroup, as many as keep the workgroup within 64 KiB of dynamic LDS
+    for (uint32_t nw = kSubBlock / 64u; nw >= 1u; nw >>= 1) {
+        const size_t lds = (size_t)bins * sizeof(unsigned long long) +
+                           (size_t)nw * ((size_t)bins + bag_k + table_slots) * sizeof(uint32_t);
+        if (lds <= 65536u || nw == 1u) {
+            if (lds_bytes) *lds_bytes = lds;
+            return nw;
+        }
+    }
+    return 1u;
+}
+
+hipError_t launch_subsample(const SubsampleArgs& a, uint32_t blocks, hipStream_t stream) {
+    SubsampleArgs copy = a;
+    void* args[] = {&copy};
+    size_t lds = 0;
+    const uint32_t nw = subsample_waves(a.bins, a.bag_k, a.table_slots, &lds);
+    if (lds > 65536u) return hipErrorInvalidValue;
+    static const void* const table[3] = {(const void*)ssa_subsample<0>, (const void*)ssa_subsample<1>,
+                                         (const void*)ssa_subsample<2>};
+    const int bag = a.bags ? (a.bag_c32 ? 2 : 1) : 0;
+    return hipLaunchKernel(table[bag], dim3(blocks), dim3(nw * 64u), args, lds, stream);
+}
+
+}  // namespace ecdna

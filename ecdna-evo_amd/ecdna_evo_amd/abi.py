@@ -14,10 +14,10 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-ABI_VERSION = 12
-# the oldest library an A/B may load under ECDNA_SSA_ABI_ANY=1: the same Params layout as this ABI (v10 appended
-# max_workgroups; v11 and v12 changed no struct)
-ABI_SAME_LAYOUT_SINCE = 10
+ABI_VERSION = 13
+# the oldest library an A/B may load under ECDNA_SSA_ABI_ANY=1: the same Params layout as this ABI (v13 appended
+# subsample_cells and reserved1, which an older library would not read)
+ABI_SAME_LAYOUT_SINCE = 13
 
 # ecdna_process_t (ProcessType, src/clap_app.rs:311-315)
 PURE_BIRTH = 0
@@ -93,6 +93,8 @@ class Params(C.Structure):
         ("set_cost_hint", C.POINTER(C.c_float)),
         ("max_workgroups", C.c_uint32),
         ("reserved0", C.c_uint32),
+        ("subsample_cells", C.c_uint32),
+        ("reserved1", C.c_uint32),
     ]
 
 
@@ -221,6 +223,9 @@ class RunSpec:
     set_cost_hint: Optional[Sequence[float]] = None  # per set: start costlier sets first (speed only)
     big_cap: int = 0  # FLAG_BIN_STORE: large-k row capacity (cells with k > bin_kmax); 0 = cell_cap
     max_workgroups: int = 0  # persistent-grid cap (0 = fill the device); for contexts sharing a GPU (speed only)
+    # end-of-run subsampling on the GPU (ABI v13): statistics and histogram of a sample of this many cells of every
+    # replicate's final population (Result.sample_stats / sample_hist); 0 = off; needs FLAG_REP_STATS; <= 4096
+    subsample_cells: int = 0
     _keep: list = field(default_factory=list, repr=False)
 
     def stride(self) -> int:
@@ -257,6 +262,7 @@ class RunSpec:
         # ctypes silently masks values that do not fit a field (a stride of 2^32 would become 0, i.e. 1):
         # reject them here instead
         for name, bits in (("replicate_stride", 32), ("big_cap", 32), ("bin_kmax", 32), ("hist_bins", 32),
+                           ("subsample_cells", 32),
                            ("n_replicates", 64), ("first_replicate", 64), ("seed", 64), ("max_cells", 64),
                            ("max_iter", 64)):
             v = getattr(self, name)
@@ -290,6 +296,7 @@ class RunSpec:
         p.bin_kmax = self.bin_kmax
         p.big_cap = self.big_cap
         p.max_workgroups = self.max_workgroups
+        p.subsample_cells = self.subsample_cells
         p.device = self.device
         if self.snapshots:
             snaps = np.asarray(sorted(int(x) for x in self.snapshots), dtype=np.uint64)

@@ -35,6 +35,7 @@ EXPORTS = [
     "ecdna_ssa_ctx_download",
     "ecdna_ssa_ctx_download_snapshots",
     "ecdna_ssa_ctx_download_stats",
+    "ecdna_ssa_ctx_download_sample",
     "ecdna_ssa_ctx_download_rng_words",
     "ecdna_ssa_ctx_row_stride",
     "ecdna_ssa_ctx_geometry",
@@ -99,6 +100,8 @@ def lib():
     L.ecdna_ssa_ctx_download_snapshots.restype = C.c_int
     L.ecdna_ssa_ctx_download_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.ecdna_ssa_ctx_download_stats.restype = C.c_int
+    L.ecdna_ssa_ctx_download_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ecdna_ssa_ctx_download_sample.restype = C.c_int
     L.ecdna_ssa_ctx_download_rng_words.argtypes = [C.c_void_p, C.c_void_p]
     L.ecdna_ssa_ctx_download_rng_words.restype = C.c_int
     L.ecdna_ssa_ctx_row_stride.argtypes = [C.c_void_p]
@@ -186,6 +189,10 @@ class Result:
         self.snapshots = None  # [n][S] abi.SNAPSHOT_DTYPE
         self.snapshot_rows = None  # [n][S][stride] u16 under FLAG_SNAPSHOT_ROWS
         self.stats = None  # [n] abi.STATS_DTYPE under FLAG_REP_STATS
+        # RunSpec.subsample_cells > 0: the statistics of every replicate's end-of-run sample, [n] abi.STATS_DTYPE, and
+        # the per-set sum of the samples' histograms, [n_sets][hist_bins] u64 (else None)
+        self.sample_stats = None
+        self.sample_hist = None
         self.rng_words = None  # [n] u64 under FLAG_REFERENCE_DRAWS: ChaCha8 stream position at the end
 
     def row(self, i: int) -> np.ndarray:
@@ -279,6 +286,12 @@ class Context:
             st = np.zeros(p.n_replicates, dtype=abi.STATS_DTYPE)
             _check(lib().ecdna_ssa_ctx_download_stats(self.h, st.ctypes.data), "download_stats")
             res.stats = st
+        if p.subsample_cells:
+            st = np.zeros(p.n_replicates, dtype=abi.STATS_DTYPE)
+            sh = np.zeros(p.n_param_sets * p.hist_bins, dtype=np.uint64)
+            _check(lib().ecdna_ssa_ctx_download_sample(self.h, st.ctypes.data, sh.ctypes.data), "download_sample")
+            res.sample_stats = st
+            res.sample_hist = sh.reshape(p.n_param_sets, p.hist_bins)
         if p.flags & abi.FLAG_REFERENCE_DRAWS:
             w = np.zeros(p.n_replicates, dtype=np.uint64)
             _check(lib().ecdna_ssa_ctx_download_rng_words(self.h, w.ctypes.data), "download_rng_words")

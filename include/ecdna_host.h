@@ -43,7 +43,10 @@ int64_t ecdna_host_load(const char* path, uint16_t* out_nplus, uint64_t cap, uin
 /* nb_cells of the n- + n+ cells uniformly without replacement (Floyd's algorithm). Randomness comes
  * from replicate rid's Philox key (seed) in a counter region the stepper never uses:
  * (sample_index, 0x80000000 | block, rid). nb_cells >= n- + n+ returns the distribution unchanged.
- * out_nplus needs min(nb_cells, n_plus) entries. Returns 0, or -1 on failure. */
+ * out_nplus needs min(nb_cells, n_plus) entries. Returns 0, or -1 on failure.
+ * The engine's own end-of-run sample (ecdna_ssa_params_t.subsample_cells, include/ecdna_ssa.h: counter region
+ * 0xC0000000 | block) is a different sample for the same seed: Floyd's set grows one cell at a time, which does not
+ * map onto a GPU wave. Both are uniform. */
 int ecdna_host_subsample(const uint16_t* nplus, uint64_t n_plus, uint64_t nminus, uint64_t nb_cells, uint64_t seed,
                          uint64_t rid, uint32_t sample_index, uint16_t* out_nplus, uint64_t* out_n_plus,
                          uint64_t* out_nminus);

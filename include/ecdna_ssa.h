@@ -43,7 +43,12 @@
 extern "C" {
 #endif
 
-/* ABI v12: draw mapping v8, the time step as the soft log times the correctly rounded reciprocal RN32(1 / a0) (v7
+/* ABI v13: end-of-run subsampling on the GPU. ecdna_ssa_params_t gains subsample_cells and reserved1 (appended after
+ * reserved0, so the v10-v12 layout is a prefix of this one) and ecdna_ssa_ctx_download_sample returns the statistics
+ * and the per-set histogram of a sample of subsample_cells cells of every replicate's final population (subsample
+ * mapping v1, below). With subsample_cells = 0 no new kernel is launched and every output is v12's; the draw mapping
+ * is v8 as before.
+ * ABI v12: draw mapping v8, the time step as the soft log times the correctly rounded reciprocal RN32(1 / a0) (v7
  * divided: the correctly rounded quotient; the two differ by at most one ulp, so results differ from v11's for the
  * same seed). The Params layout and everything else are those of v11.
  * ABI v11: ECDNA_REP_ERR_INTERNAL (a replicate whose event would pick from an empty N+ set stops instead of
@@ -51,7 +56,7 @@ extern "C" {
  * The Params layout is that of v10 (v10 appended ecdna_ssa_params_t.max_workgroups, a cap on the persistent grid for
  * contexts that share a GPU; v9 took the channel from all 32 bits of the event's word over f64 cumulative
  * propensities, draw mapping v7). */
-#define ECDNA_SSA_ABI_VERSION 12
+#define ECDNA_SSA_ABI_VERSION 13
 
 /* Process type — ProcessType (src/clap_app.rs:311-315); chosen as BirthDeath
  * when d0 > 0 or d1 > 0 (src/clap_app.rs:163-174, 194-200). */
@@ -210,6 +215,36 @@ typedef struct {
      * (DESIGN.md §7). Results do not depend on it. */
     uint32_t max_workgroups;
     uint32_t reserved0;             /* must be 0 */
+    /* End-of-run subsampling (since ABI v13; the reference's into_subsampled(nb, &mut rng), src/main.rs:110-123,
+     * 184-197; abc.md:38-55 carries both `cells` and `tumour_cells`): 0 = off; m > 0: after the run, a uniform
+     * sample of m cells is drawn from every replicate's final population on the GPU and its statistics and
+     * histogram are kept for ecdna_ssa_ctx_download_sample. Needs ECDNA_FLAG_REP_STATS (so hist_bins <= 2048);
+     * m <= 4096.
+     *
+     * Subsample mapping v1. A replicate's final population has N = n- + n+ cells at positions 0 .. N-1 in download
+     * order: first the n- N- cells (k = 0), then the N+ cells in the order ecdna_ssa_ctx_download returns its row
+     * (row store: row order; bin store: k = 1 .. bin_kmax ascending from the counters, then the large-k row).
+     *  - m >= N: the sample is the whole population; its statistics equal ecdna_ssa_ctx_download_stats'.
+     *  - m < N: with m' = min(m, N - m), draws u_0, u_1, ... are generated until m' distinct values have appeared;
+     *    draw i is new iff it equals no earlier draw, and the picked set is the values of the new draws up to and
+     *    including the m'-th new one (the first m' distinct values of an iid uniform sequence: a uniform m'-subset).
+     *    If m' = m the picked positions are the sample; otherwise they are the cells left out (sample histogram =
+     *    full histogram - picked histogram, likewise the sum of k).
+     *  - Draw i is a Lemire draw below N: Philox4x32-10 under the run's key (seed lo, seed hi) on counter
+     *    (i, 0xC0000000 | t, r lo, r hi), t = 0, 1, ... (the stepper's sub-blocks are small numbers and
+     *    ecdna_host_subsample's are 0x80000000 | block with fewer than 2^30 blocks: disjoint streams). The block's
+     *    four words are tried in order: word x gives p = x * N and is accepted as p >> 32 when
+     *    (p & 0xffffffff) >= (2^32 - N) mod N; if all four are rejected, block t + 1 follows. r is the GLOBAL
+     *    replicate id, so a replicate's sample does not depend on chunk, shard, grid or device.
+     *  - Guard: a replicate that has not found m' distinct values within 2^16 draws gets all-zero sample statistics
+     *    and adds nothing to the sample histogram (unreachable: m' <= N / 2, so every draw is new with probability
+     *    >= 1/2). So does one with N >= 2^32 - 1 and m < N (positions are 32-bit).
+     *  - The sample's mean uses every cell's true copy number, not the clipped bin, as the full statistics do. Error
+     *    and extinct replicates are treated as the full statistics treat them (N = 0: cells 0, ks 1.0 with a target).
+     * This is a different sample from ecdna_host_subsample's for the same seed (Floyd's sequential set does not map
+     * onto a wave); both are uniform. */
+    uint32_t subsample_cells;
+    uint32_t reserved1;             /* must be 0 */
 } ecdna_ssa_params_t;
 
 /* Per-replicate summary statistics of the final distribution (cells = n- + n+, copy number k per cell,
@@ -286,7 +321,8 @@ int ecdna_ssa_ctx_set_outputs(ecdna_ssa_ctx* c, uint64_t* d_hist, ecdna_totals_t
  * kernel over all replicates (in memory-bounded chunks), histogram kernel. Asynchronous. */
 int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream);
 /* Block until the last launch finished; returns its device time in ms (HIP events on the launch
- * stream): ssa_ms = SSA stepper kernels only, hist_ms = histogram/summary kernels. Either may be NULL. */
+ * stream): ssa_ms = SSA stepper kernels only, hist_ms = histogram/summary kernels (and the
+ * subsampling pass when params.subsample_cells > 0). Either may be NULL. */
 int ecdna_ssa_ctx_sync(ecdna_ssa_ctx* c, float* ssa_ms, float* hist_ms);
 /* Device pointers of the current outputs. */
 int ecdna_ssa_ctx_device_outputs(ecdna_ssa_ctx* c, uint64_t** d_hist, ecdna_totals_t** d_totals);
@@ -304,6 +340,13 @@ int ecdna_ssa_ctx_download(ecdna_ssa_ctx* c, ecdna_rep_summary_t* out_summaries,
 int ecdna_ssa_ctx_download_snapshots(ecdna_ssa_ctx* c, ecdna_snapshot_t* meta, uint16_t* rows);
 /* Per-replicate statistics of the last launch (needs ECDNA_FLAG_REP_STATS): out[n_replicates]. */
 int ecdna_ssa_ctx_download_stats(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out);
+/* The end-of-run subsample of the last launch (ABI v13; params.subsample_cells > 0, else ECDNA_E_STATE, as before a
+ * launch). Either buffer may be NULL. out_stats[n_replicates]: the statistics of replicate i's sample, with the
+ * definitions of ecdna_rep_stats_t (cells = the sample's size, distances against params.stats_target_hist).
+ * out_sample_hist[n_param_sets * hist_bins]: per set, the sum of its replicates' sample histograms, binned as
+ * out_hist (bin 0 = N- cells, last bin = overflow). Chunked runs are covered (the buffers are sized by the run, not
+ * the chunk). ecdna_ssa_ctx_reduce does not reduce the sample histogram: callers sum the shards' themselves. */
+int ecdna_ssa_ctx_download_sample(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats, uint64_t* out_sample_hist);
 /* Reference draws (ECDNA_FLAG_REFERENCE_DRAWS, ABI v7): per replicate, the number of 32-bit words its ChaCha8
  * stream (seed_from_u64(seed), stream seed*10 + r) had handed out when it stopped — where the reference's
  * end-of-run subsampling continues the same rng (into_subsampled(nb, &mut rng), src/main.rs:110-123, 184-197;
