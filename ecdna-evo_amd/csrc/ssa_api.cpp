@@ -1,6 +1,6 @@
 // ssa_api.cpp — the C ABI of include/ecdna_ssa.h: parameter validation,
 // device-resident run contexts, chunking by HBM capacity, and launches of the
-// stepper and histogram kernels (ssa_kernels.hip).
+// stepper and histogram kernels (ssa_kernels.hip, ssa_hist.hip).
 //
 // This file replaces, for one GPU, the per-replicate driver loop of the
 // reference: run_simulations(idx) mapped by rayon over seed*10 .. seed*10+runs

@@ -1,5 +1,6 @@
-// ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by
-// ssa_kernels.hip (device code) and ssa_api.cpp (the C ABI).
+// ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by the device
+// code (steppers: ssa_kernels.hip, ssa_refdraws.hip; end-of-run passes: ssa_hist.hip,
+// ssa_subsample.hip) and ssa_api.cpp (the C ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>

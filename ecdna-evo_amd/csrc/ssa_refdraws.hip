@@ -20,6 +20,7 @@
 #include "refdraws.hpp"
 #include "ssa_device.hpp"
 #include "ssa_launch.h"
+#include "ssa_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -75,7 +76,7 @@ __device__ unsigned long long g_cycle_stats_ref[16];
     do {                                                                                                       \
         __builtin_amdgcn_s_waitcnt(0xc07f);                                                                    \
         for (int q = 0; q < 4; ++q) rcy_[11 + q] = rng.dbg[q];                                                 \
-        for (int q = 8; q < 15; ++q) rcy_[q] = wave_sum_u64(rcy_[q]);                                          \
+        for (int q = 8; q < 15; ++q) rcy_[q] = wave_sum(rcy_[q]);                                          \
         if ((threadIdx.x & 63u) == 0u) {                                                                       \
             for (int q = 0; q < 7; ++q) rcy_[q] = rcyc_w_[rcy_wave_][q];                                       \
             rcy_[15] = clock64() - rcy_start_;                                                                 \
@@ -83,11 +84,6 @@ __device__ unsigned long long g_cycle_stats_ref[16];
                 __hip_atomic_fetch_add(&g_cycle_stats_ref[q], rcy_[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
         }                                                                                                      \
     } while (0)
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
 #else
 #define RCYC_DECL
 #define RCYC_MARK(i) ((void)0)

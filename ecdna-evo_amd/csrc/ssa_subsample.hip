@@ -16,6 +16,7 @@
 
 #include "ssa_device.hpp"
 #include "ssa_launch.h"
+#include "ssa_wave.hpp"
 
 #pragma clang fp contract(off)
 
@@ -28,25 +29,6 @@ constexpr uint32_t kSubTag = 0xC0000000u;      // Philox counter word 1 of draw 
 constexpr uint32_t kSubMaxDraws = 1u << 16;    // the guard: draws per replicate
 constexpr uint32_t kSubMaxBlocks = 1024;       // Philox blocks per draw (each rejects with p < 2^-4: unreachable)
 constexpr uint32_t kSubBlock = 256;
-
-__device__ __forceinline__ void sub_wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS accesses have completed
-    __builtin_amdgcn_wave_barrier();
-}
-
-template <typename T>
-__device__ __forceinline__ T sub_wave_sum(T x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-__device__ __forceinline__ double sub_wave_max(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o, 64));
-    return x;
-}
 
 // Draw i of replicate (rid_lo, rid_hi): a Lemire draw below N. Philox block t = 0, 1, ... on counter
 // (i, kSubTag | t, rid lo, rid hi); its four words are tried in order, word x gives p = x * N and is accepted as
@@ -86,11 +68,7 @@ __global__ void __launch_bounds__(kSubBlock) ssa_subsample(const SubsampleArgs a
 
     uint32_t r = r_begin;
     while (r < r_end) {
-        // local replicates r .. seg_end - 1 share a parameter set (as ssa_hist)
-        const uint64_t set = (a.rid0 + (uint64_t)r * a.rid_stride) / a.reps_per_set;
-        const uint64_t set_end_rid = (set + 1) * a.reps_per_set;
-        const uint64_t in_set = (set_end_rid - a.rid0 + a.rid_stride - 1) / a.rid_stride;
-        const uint32_t seg_end = (uint32_t)min((uint64_t)r_end, in_set);
+        const auto [set, seg_end] = set_segment(a.rid0, a.rid_stride, a.reps_per_set, r, r_end);
         for (uint32_t b = tid; b < a.bins; b += blockDim.x) hb[b] = 0ull;
         __syncthreads();
         for (uint32_t q = r + wave; q < seg_end; q += nw) {
@@ -108,7 +86,7 @@ __global__ void __launch_bounds__(kSubBlock) ssa_subsample(const SubsampleArgs a
             const bool comp = mp != a.m;
             const bool need_full = whole || comp;
             for (uint32_t b = lane; b < a.bins; b += 64u) wh[b] = 0u;
-            sub_wave_sync_lds();
+            wave_sync_lds();
 
             // 1. counters: prefix sums for the position -> k lookup, and (whole / complement) the full histogram
             uint64_t ksum = 0;  // sum of k over the full population (need_full)
@@ -116,23 +94,13 @@ __global__ void __launch_bounds__(kSubBlock) ssa_subsample(const SubsampleArgs a
             if (BAG) {
                 for (uint32_t base = 0; base < a.bag_k; base += 64u) {
                     const uint32_t b = base + lane;
-                    uint32_t cnt = 0;
-                    if (b < a.bag_k) {
-                        const uint64_t o = (uint64_t)q * a.bag_k + b;
-                        cnt = BAG == 2 ? reinterpret_cast<const uint32_t*>(a.bags)[o]
-                                       : (uint32_t)reinterpret_cast<const uint16_t*>(a.bags)[o];
-                    }
+                    const uint32_t cnt = b < a.bag_k ? bag_counter<BAG>(a.bags, q, a.bag_k, b) : 0u;
                     if (need_full && cnt) {
                         const uint32_t kk = b + 1u;
                         atomicAdd(&wh[kk < last ? kk : last], cnt);
                         ksum += (uint64_t)kk * cnt;
                     }
-                    uint32_t scan = cnt;  // inclusive prefix sum over the wave
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const uint32_t y = __shfl_up(scan, o, 64);
-                        if ((int)lane >= o) scan += y;
-                    }
+                    const uint32_t scan = wave_inclusive_scan(cnt, lane);
                     if (b < a.bag_k) pre[b] = small + scan;
                     small += __shfl(scan, 63, 64);
                 }
@@ -166,7 +134,7 @@ __global__ void __launch_bounds__(kSubBlock) ssa_subsample(const SubsampleArgs a
                 bad = tsize > a.table_slots;
                 const uint32_t tclear = bad ? 0u : tsize;
                 for (uint32_t b = lane; b < tclear; b += 64u) tab[b] = kSubEmpty;
-                sub_wave_sync_lds();
+                wave_sync_lds();
                 const uint32_t thr = (0u - N) % N;
                 const uint32_t rid_lo = (uint32_t)rid, rid_hi = (uint32_t)(rid >> 32);
                 bool lane_bad = false;
@@ -235,60 +203,26 @@ __global__ void __launch_bounds__(kSubBlock) ssa_subsample(const SubsampleArgs a
                     }
                     count += (uint32_t)__popcll(__ballot(isnew));
                     base += nact;
-                    sub_wave_sync_lds();
+                    wave_sync_lds();
                 }
                 bad = bad || count < mp || __any(lane_bad);
             }
-            sub_wave_sync_lds();
+            wave_sync_lds();
 
-            // 5. statistics of the sample histogram: the wave routine of ssa_hist<true, BAG> (ssa_kernels.hip), copied
-            // so that the timed kernels' translation unit stays as it is
-            ksum = sub_wave_sum(ksum);
-            psum = sub_wave_sum(psum);
-            const uint64_t cells = bad ? 0ull : (whole ? cells_all : (uint64_t)a.m);
-            const uint64_t ks_sum = whole ? ksum : (comp ? ksum - psum : psum);
-            const uint64_t nplus_s = whole ? (uint64_t)np : cells - (uint64_t)wh[0];
-            const double inv = cells ? 1.0 / (double)cells : 0.0;
-            double carry = 0.0, ent = 0.0, ks = 0.0;
-            if (!bad) {
-                for (uint32_t base = 0; base < a.bins; base += 64u) {
-                    const uint32_t b = base + lane;
-                    const uint32_t cnt = b < a.bins ? wh[b] : 0u;
-                    if (cnt) atomicAdd(&hb[b], (unsigned long long)cnt);
-                    const double p = (double)cnt * inv;
-                    if (cnt) ent -= p * log(p);
-                    double scan = p;  // inclusive prefix sum over the wave
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) {
-                        const double y = __shfl_up(scan, o, 64);
-                        if ((int)lane >= o) scan += y;
-                    }
-                    if (a.has_target && b < a.bins) ks = fmax(ks, fabs(carry + scan - a.target_cdf[b]));
-                    carry += __shfl(scan, 63, 64);
-                }
+            // 5. statistics of the sample histogram (the guard, or a state the counters cannot account for: all-zero
+            // sample statistics, nothing added to hb)
+            ksum = wave_sum(ksum);
+            psum = wave_sum(psum);
+            if (bad) {
+                if (lane == 0) a.stats[q] = ecdna_rep_stats_t{};
+            } else {
+                const uint64_t cells = whole ? cells_all : (uint64_t)a.m;
+                const uint64_t ks_sum = whole ? ksum : (comp ? ksum - psum : psum);
+                const uint64_t nplus_s = whole ? (uint64_t)np : cells - (uint64_t)wh[0];
+                wave_rep_stats(wh, hb, a.bins, cells, ks_sum, nplus_s, a.has_target, a.target_cdf, a.target_mean,
+                               a.target_entropy, a.target_freq, lane, a.stats + q);
             }
-            ent = sub_wave_sum(ent);
-            ks = sub_wave_max(ks);
-            if (lane == 0) {
-                ecdna_rep_stats_t st;
-                if (bad) {  // the guard, or a state the counters cannot account for: all-zero sample statistics
-                    st.cells = 0;
-                    st.mean = st.entropy = st.frequency = st.ks = 0.0;
-                    st.mean_rel = st.entropy_rel = st.frequency_diff = 0.0;
-                } else {
-                    st.cells = cells;
-                    st.mean = cells ? (double)ks_sum * inv : 0.0;
-                    st.entropy = ent;
-                    st.frequency = cells ? (double)nplus_s * inv : 0.0;
-                    st.ks = a.has_target ? (cells ? ks : 1.0) : 0.0;
-                    const double dm = fabs(st.mean - a.target_mean), de = fabs(st.entropy - a.target_entropy);
-                    st.mean_rel = a.has_target ? (a.target_mean > 0.0 ? dm / a.target_mean : dm) : 0.0;
-                    st.entropy_rel = a.has_target ? (a.target_entropy > 0.0 ? de / a.target_entropy : de) : 0.0;
-                    st.frequency_diff = a.has_target ? fabs(st.frequency - a.target_freq) : 0.0;
-                }
-                a.stats[q] = st;
-            }
-            sub_wave_sync_lds();  // wh is zeroed again for the wave's next replicate
+            wave_sync_lds();  // wh is zeroed again for the wave's next replicate
         }
         __syncthreads();
         for (uint32_t b = tid; b < a.bins; b += blockDim.x)

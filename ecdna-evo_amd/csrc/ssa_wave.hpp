@@ -1,0 +1,107 @@
+// ssa_wave.hpp — the wave-level pieces the end-of-run kernels share (ssa_hist.hip, ssa_subsample.hip; wave_sum also
+// the development counters of ssa_refdraws.hip): wave reductions and the inclusive scan, the wave's LDS ordering
+// point, a chunk's parameter-set segments, the bin-counter read, and the one routine for
+// the per-replicate ABC statistics. Plain functions over one 64-lane wave; every lane of the wave calls them.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/ecdna_ssa.h"
+
+#pragma clang fp contract(off)
+
+namespace ecdna {
+
+// The wave's LDS accesses so far are complete and ordered before its later ones: plain stores (wh[b] = 0) against
+// other lanes' later LDS atomics too, which is what the wavefront-scope fence adds to the wait.
+__device__ __forceinline__ void wave_sync_lds() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's LDS accesses have completed
+    __builtin_amdgcn_wave_barrier();
+}
+
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+__device__ __forceinline__ double wave_max(double x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = fmax(x, __shfl_xor(x, o, 64));
+    return x;
+}
+
+// The lane's inclusive prefix sum over the wave (lanes 0 .. lane); lane 63 holds the wave's total.
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_scan(T x, uint32_t lane) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(x, o, 64);
+        if ((int)lane >= o) x += y;
+    }
+    return x;
+}
+
+// Local replicates r .. seg_end - 1 of a chunk share parameter set `set`: their ids rid0 + r * rid_stride lie below
+// the set's end (set + 1) * reps_per_set. seg_end <= r_end.
+struct SetSegment {
+    uint64_t set;
+    uint32_t seg_end;
+};
+__device__ __forceinline__ SetSegment set_segment(uint64_t rid0, uint64_t rid_stride, uint64_t reps_per_set, uint32_t r,
+                                                  uint32_t r_end) {
+    const uint64_t set = (rid0 + (uint64_t)r * rid_stride) / reps_per_set;
+    const uint64_t set_end_rid = (set + 1) * reps_per_set;
+    const uint64_t in_set = (set_end_rid - rid0 + rid_stride - 1) / rid_stride;
+    return {set, (uint32_t)min((uint64_t)r_end, in_set)};
+}
+
+// Bin counter b (copy number b + 1) of replicate q: bags[q][bag_k], u16 (BAG = 1) or u32 (BAG = 2).
+template <int BAG>
+__device__ __forceinline__ uint32_t bag_counter(const void* bags, uint64_t q, uint32_t bag_k, uint32_t b) {
+    const uint64_t o = q * bag_k + b;
+    return BAG == 2 ? reinterpret_cast<const uint32_t*>(bags)[o] : (uint32_t)reinterpret_cast<const uint16_t*>(bags)[o];
+}
+
+// The ABC statistics of one replicate (or of its sample) from the wave's LDS histogram wh[bins]: mean = ksum / cells,
+// entropy, N+ frequency = nplus / cells, the KS distance to target_cdf by a wave prefix scan over the bins, and the
+// distances to the target (abc.md:38-55). cells == 0: mean, entropy and frequency 0, ks 1.0 with a target. The
+// non-zero bins of wh are added to the workgroup histogram hb on the way. ksum and nplus are wave totals; wh must be
+// complete (wave_sync_lds). Lane 0 writes *out.
+__device__ __forceinline__ void wave_rep_stats(const uint32_t* wh, unsigned long long* hb, uint32_t bins, uint64_t cells,
+                                               uint64_t ksum, uint64_t nplus, uint32_t has_target,
+                                               const double* target_cdf, double target_mean, double target_entropy,
+                                               double target_freq, uint32_t lane, ecdna_rep_stats_t* out) {
+    const double inv = cells ? 1.0 / (double)cells : 0.0;
+    double carry = 0.0, ent = 0.0, ks = 0.0;
+    for (uint32_t base = 0; base < bins; base += 64u) {
+        const uint32_t b = base + lane;
+        const uint32_t cnt = b < bins ? wh[b] : 0u;
+        if (cnt) atomicAdd(&hb[b], (unsigned long long)cnt);
+        const double p = (double)cnt * inv;
+        if (cnt) ent -= p * log(p);
+        const double scan = wave_inclusive_scan(p, lane);
+        if (has_target && b < bins) ks = fmax(ks, fabs(carry + scan - target_cdf[b]));
+        carry += __shfl(scan, 63, 64);
+    }
+    ent = wave_sum(ent);
+    ks = wave_max(ks);
+    if (lane == 0) {
+        ecdna_rep_stats_t st;
+        st.cells = cells;
+        st.mean = cells ? (double)ksum * inv : 0.0;
+        st.entropy = ent;
+        st.frequency = cells ? (double)nplus * inv : 0.0;
+        st.ks = has_target ? (cells ? ks : 1.0) : 0.0;
+        const double dm = fabs(st.mean - target_mean), de = fabs(st.entropy - target_entropy);
+        st.mean_rel = has_target ? (target_mean > 0.0 ? dm / target_mean : dm) : 0.0;
+        st.entropy_rel = has_target ? (target_entropy > 0.0 ? de / target_entropy : de) : 0.0;
+        st.frequency_diff = has_target ? fabs(st.frequency - target_freq) : 0.0;
+        *out = st;
+    }
+}
+
+}  // namespace ecdna
