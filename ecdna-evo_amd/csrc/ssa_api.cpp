@@ -1,6 +1,6 @@
 // ssa_api.cpp — the C ABI of include/ecdna_ssa.h: parameter validation,
 // device-resident run contexts, chunking by HBM capacity, and launches of the
-// stepper and histogram kernels (ssa_kernels.hip, ssa_hist.hip).
+// stepper and end-of-run kernels (ssa_kernels.hip, ssa_hist.hip, ssa_subsample.hip, ssa_snapstats.hip).
 //
 // This file replaces, for one GPU, the per-replicate driver loop of the
 // reference: run_simulations(idx) mapped by rayon over seed*10 .. seed*10+runs
@@ -59,7 +59,7 @@ InitOfSet init_of_set(const ecdna_ssa_params_t* p, uint64_t s) {
     return r;
 }
 
-int validate(const ecdna_ssa_params_t* p) {
+int validate(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext) {
     if (!p) return fail(ECDNA_E_INVALID, "params is NULL");
     if (!p->rates || p->n_param_sets == 0) return fail(ECDNA_E_INVALID, "rates/n_param_sets");
     for (uint32_t s = 0; s < p->n_param_sets; ++s) {  // (the steppers' f32 time-step division relies on it)
@@ -119,7 +119,44 @@ int validate(const ecdna_ssa_params_t* p) {
             if (in.copies[j] == 0) return fail(ECDNA_E_INVALID, "initial copy numbers must be >= 1");
         if (!p->init_set_offsets && !p->init_set_nminus) break;
     }
+    if (ext) {  // the extension block (per-snapshot ABC statistics)
+        if (ext->struct_size != sizeof(ecdna_ssa_ext_t))
+            return fail(ECDNA_E_INVALID, "ext.struct_size must be sizeof(ecdna_ssa_ext_t)");
+        if (ext->reserved) return fail(ECDNA_E_INVALID, "ext.reserved must be 0");
+        if (ext->snapshot_subsample_cells > ecdna::kMaxSubsampleCells)
+            return fail(ECDNA_E_INVALID, "ext.snapshot_subsample_cells must be <= 4096");
+        if (ext->snapshot_stats > 1u) return fail(ECDNA_E_INVALID, "ext.snapshot_stats must be 0 or 1");
+        if (ext->snapshot_stats) {
+            if (!p->n_snapshots) return fail(ECDNA_E_INVALID, "ext.snapshot_stats needs n_snapshots > 0");
+            if (!(p->flags & ECDNA_FLAG_REP_STATS))
+                return fail(ECDNA_E_INVALID, "ext.snapshot_stats needs ECDNA_FLAG_REP_STATS");
+            for (uint32_t q = 0; ext->snapshot_target_hists && q < p->n_snapshots; ++q) {
+                const uint64_t* t = ext->snapshot_target_hists + (uint64_t)q * p->hist_bins;
+                bool any = false;
+                for (uint32_t b = 0; b < p->hist_bins; ++b) any |= t[b] != 0;
+                if (!any)
+                    return fail(ECDNA_E_INVALID, "ext.snapshot_target_hists[" + std::to_string(q) + "] is empty");
+            }
+        }
+    }
     return ECDNA_OK;
+}
+
+// A target histogram's CDF over the bins and its mean / entropy / N+ frequency (the overflow bin counts at
+// k = bins - 1), as the kernels compare against them. tot > 0.
+void target_summary(const uint64_t* hist, uint32_t bins, double tot, double* cdf, double* mean, double* entropy,
+                    double* freq) {
+    double acc = 0.0, ksum = 0.0, ent = 0.0;
+    for (uint32_t b = 0; b < bins; ++b) {
+        const double pb = (double)hist[b] / tot;
+        acc += pb;
+        cdf[b] = acc;
+        ksum += (double)b * (double)hist[b];
+        if (pb > 0.0) ent -= pb * std::log(pb);
+    }
+    *mean = ksum / tot;
+    *entropy = ent;
+    *freq = 1.0 - (double)hist[0] / tot;
 }
 
 // Reference draws (ECDNA_FLAG_REFERENCE_DRAWS): rand_core 0.6.4 seed_from_u64 — the 32-byte ChaCha key filled
@@ -214,6 +251,17 @@ struct ecdna_ssa_ctx {
     // end-of-run subsampling (subsample_cells > 0): the samples' statistics [n] and histogram [n_sets][bins]
     ecdna_rep_stats_t* d_sample_stats = nullptr;
     uint64_t* d_sample_hist = nullptr;
+    // per-snapshot ABC statistics (ecdna_ssa_ext_t.snapshot_stats): statistics [n][S] and histograms [S][n_sets][bins]
+    // of the saved states and (snap_m > 0) of their samples; each snapshot's target: CDF [S][bins], scalars [S][3]
+    bool snap_stats = false;
+    uint32_t snap_m = 0;
+    bool snap_rows_local = false;  // d_snap_rows holds one chunk's rows (scratch), not the run's
+    ecdna_rep_stats_t* d_snap_stats = nullptr;
+    ecdna_rep_stats_t* d_snap_sample_stats = nullptr;
+    uint64_t* d_snap_hist = nullptr;
+    uint64_t* d_snap_sample_hist = nullptr;
+    double* d_snap_target_cdf = nullptr;
+    double* d_snap_target_scalars = nullptr;
     // device buffers
     float4* d_rates = nullptr;
     uint16_t* d_init = nullptr;
@@ -298,6 +346,12 @@ void free_ctx(ecdna_ssa_ctx* c) {
     (void)hipFree(c->d_stats);
     (void)hipFree(c->d_sample_stats);
     (void)hipFree(c->d_sample_hist);
+    (void)hipFree(c->d_snap_stats);
+    (void)hipFree(c->d_snap_sample_stats);
+    (void)hipFree(c->d_snap_hist);
+    (void)hipFree(c->d_snap_sample_hist);
+    (void)hipFree(c->d_snap_target_cdf);
+    (void)hipFree(c->d_snap_target_scalars);
     (void)hipFree(c->d_rows);
     (void)hipFree(c->d_bags);
     (void)hipFree(c->d_summ);
@@ -374,9 +428,13 @@ int ecdna_ssa_device_count(void) {
 }
 
 int ecdna_ssa_ctx_create(const ecdna_ssa_params_t* p, ecdna_ssa_ctx** out) {
+    return ecdna_ssa_ctx_create_ext(p, nullptr, out);
+}
+
+int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, ecdna_ssa_ctx** out) {
     if (!out) return fail(ECDNA_E_INVALID, "out is NULL");
     *out = nullptr;
-    int rc = validate(p);
+    int rc = validate(p, ext);
     if (rc) return rc;
     rc = pick_device(p->device);
     if (rc) return rc;
@@ -451,18 +509,9 @@ int ecdna_ssa_ctx_create(const ecdna_ssa_params_t* p, ecdna_ssa_ctx** out) {
             for (uint32_t b = 0; b < bins; ++b) tot += (double)p->stats_target_hist[b];
             if (!(tot > 0.0)) return bail(fail(ECDNA_E_INVALID, "stats_target_hist is empty"));
             std::vector<double> cdf(bins);
-            double acc = 0.0, ksum = 0.0, ent = 0.0;
-            for (uint32_t b = 0; b < bins; ++b) {
-                const double pb = (double)p->stats_target_hist[b] / tot;
-                acc += pb;
-                cdf[b] = acc;
-                ksum += (double)b * (double)p->stats_target_hist[b];
-                if (pb > 0.0) ent -= pb * std::log(pb);
-            }
+            target_summary(p->stats_target_hist, bins, tot, cdf.data(), &c->target_mean, &c->target_entropy,
+                           &c->target_freq);
             c->has_target = true;
-            c->target_mean = ksum / tot;
-            c->target_entropy = ent;
-            c->target_freq = 1.0 - (double)p->stats_target_hist[0] / tot;
             CTX_TRY(hipMalloc(&c->d_target_cdf, bins * sizeof(double)));
             CTX_TRY(hipMemcpy(c->d_target_cdf, cdf.data(), bins * sizeof(double), hipMemcpyHostToDevice));
         }
@@ -475,6 +524,34 @@ int ecdna_ssa_ctx_create(const ecdna_ssa_params_t* p, ecdna_ssa_ctx** out) {
     if (p->subsample_cells) {
         CTX_TRY(hipMalloc(&c->d_sample_stats, std::max<uint64_t>(n, 1) * sizeof(ecdna_rep_stats_t)));
         CTX_TRY(hipMalloc(&c->d_sample_hist, nb * sizeof(uint64_t)));
+    }
+    // per-snapshot statistics: sized by the run (the snapshot rows they are computed from may be one chunk's, below)
+    c->snap_stats = ext && ext->snapshot_stats;
+    if (c->snap_stats) {
+        const uint64_t S = p->n_snapshots;
+        const uint64_t stats_bytes = std::max<uint64_t>(n, 1) * S * sizeof(ecdna_rep_stats_t);
+        c->snap_m = ext->snapshot_subsample_cells;
+        CTX_TRY(hipMalloc(&c->d_snap_stats, stats_bytes));
+        CTX_TRY(hipMalloc(&c->d_snap_hist, S * nb * sizeof(uint64_t)));
+        if (c->snap_m) {
+            CTX_TRY(hipMalloc(&c->d_snap_sample_stats, stats_bytes));
+            CTX_TRY(hipMalloc(&c->d_snap_sample_hist, S * nb * sizeof(uint64_t)));
+        }
+        if (ext->snapshot_target_hists) {
+            const uint32_t bins = p->hist_bins;
+            std::vector<double> cdf(S * bins), scal(S * 3);
+            for (uint64_t q = 0; q < S; ++q) {
+                const uint64_t* t = ext->snapshot_target_hists + q * bins;
+                double tot = 0.0;
+                for (uint32_t b = 0; b < bins; ++b) tot += (double)t[b];
+                target_summary(t, bins, tot, cdf.data() + q * bins, &scal[3 * q], &scal[3 * q + 1], &scal[3 * q + 2]);
+            }
+            CTX_TRY(hipMalloc(&c->d_snap_target_cdf, cdf.size() * sizeof(double)));
+            CTX_TRY(hipMemcpy(c->d_snap_target_cdf, cdf.data(), cdf.size() * sizeof(double), hipMemcpyHostToDevice));
+            CTX_TRY(hipMalloc(&c->d_snap_target_scalars, scal.size() * sizeof(double)));
+            CTX_TRY(hipMemcpy(c->d_snap_target_scalars, scal.data(), scal.size() * sizeof(double),
+                              hipMemcpyHostToDevice));
+        }
     }
     CTX_TRY(hipMalloc(&c->d_hist_own, nb * sizeof(uint64_t)));
     CTX_TRY(hipMalloc(&c->d_tot_own, p->n_param_sets * sizeof(ecdna_totals_t)));
@@ -506,7 +583,11 @@ int ecdna_ssa_ctx_create(const ecdna_ssa_params_t* p, ecdna_ssa_ctx** out) {
 
     // rows: one u16 row per replicate of the chunk; chunk bounded by free HBM
     const uint64_t rot_bytes = c->bin_k ? ecdna::kParkVecs * 16u + 4u : 0u;  // parked scalars + state word
-    const uint64_t row_bytes = c->row_stride * sizeof(uint16_t) + bag_bytes + rot_bytes;
+    // (snapshot statistics without ECDNA_FLAG_SNAPSHOT_ROWS: the snapshot rows are the chunk's scratch, n_snapshots
+    // rows of out_stride cells per replicate of the chunk, so a large run chunks instead of failing)
+    c->snap_rows_local = c->snap_stats && !c->d_snap_rows;
+    const uint64_t snap_row_bytes = c->snap_rows_local ? p->n_snapshots * c->out_stride * sizeof(uint16_t) : 0u;
+    const uint64_t row_bytes = c->row_stride * sizeof(uint16_t) + bag_bytes + rot_bytes + snap_row_bytes;
     size_t free_b = 0, total_b = 0;
     CTX_TRY(hipMemGetInfo(&free_b, &total_b));
     uint64_t budget = (uint64_t)((double)free_b * 0.85);
@@ -519,6 +600,7 @@ int ecdna_ssa_ctx_create(const ecdna_ssa_params_t* p, ecdna_ssa_ctx** out) {
     c->chunk_reps = std::min<uint64_t>(std::max<uint64_t>(n, 1), fit);
     CTX_TRY(hipMalloc(&c->d_rows, c->chunk_reps * c->row_stride * sizeof(uint16_t)));
     if (c->bin_k) CTX_TRY(hipMalloc(&c->d_bags, c->chunk_reps * bag_bytes));
+    if (c->snap_rows_local) CTX_TRY(hipMalloc(&c->d_snap_rows, c->chunk_reps * snap_row_bytes));
 
     const uint64_t n_chunks = n ? (n + c->chunk_reps - 1) / c->chunk_reps : 0;
     CTX_TRY(hipMalloc(&c->d_heads, std::max<uint64_t>(n_chunks, 1) * sizeof(uint32_t)));
@@ -711,6 +793,9 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
     HIP_TRY(hipMemsetAsync(c->d_hist, 0, nb * sizeof(uint64_t), st));
     HIP_TRY(hipMemsetAsync(c->d_tot, 0, p.n_param_sets * sizeof(ecdna_totals_t), st));
     if (c->d_sample_hist) HIP_TRY(hipMemsetAsync(c->d_sample_hist, 0, nb * sizeof(uint64_t), st));
+    if (c->d_snap_hist) HIP_TRY(hipMemsetAsync(c->d_snap_hist, 0, p.n_snapshots * nb * sizeof(uint64_t), st));
+    if (c->d_snap_sample_hist)
+        HIP_TRY(hipMemsetAsync(c->d_snap_sample_hist, 0, p.n_snapshots * nb * sizeof(uint64_t), st));
     if (!c->chunks.empty())
         HIP_TRY(hipMemsetAsync(c->d_heads, 0, c->chunks.size() * sizeof(uint32_t), st));
     if (c->d_snap_meta)
@@ -749,7 +834,9 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
         a.n_snap = p.n_snapshots;
         a.snap_cells = c->d_snap_cells;
         a.snap_meta = c->d_snap_meta ? c->d_snap_meta + ch.first * p.n_snapshots : nullptr;
-        a.snap_rows = c->d_snap_rows ? c->d_snap_rows + ch.first * p.n_snapshots * c->out_stride : nullptr;
+        // (the run's rows at the chunk's offset, or the chunk's scratch)
+        a.snap_rows = c->d_snap_rows;
+        if (a.snap_rows && !c->snap_rows_local) a.snap_rows += ch.first * p.n_snapshots * c->out_stride;
         a.snap_stride = c->out_stride;
         a.big_cap = c->big_cap;
         a.bags = c->d_bags;
@@ -845,6 +932,32 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
             const uint32_t sw = ecdna::subsample_waves(sa.bins, sa.bag_k, sa.table_slots, nullptr);
             sa.reps_per_block = std::max<uint32_t>(sw, (ch.n + hist_blocks_max - 1) / hist_blocks_max);
             HIP_TRY(ecdna::launch_subsample(sa, (ch.n + sa.reps_per_block - 1) / sa.reps_per_block, st));
+        }
+        if (c->snap_stats) {  // the statistics of the chunk's snapshots, from the rows the stepper just saved
+            ecdna::SnapStatsArgs ta{};
+            ta.snap_meta = a.snap_meta;
+            ta.snap_rows = a.snap_rows;
+            ta.stats = c->d_snap_stats + ch.first * p.n_snapshots;
+            ta.sample_stats = c->d_snap_sample_stats ? c->d_snap_sample_stats + ch.first * p.n_snapshots : nullptr;
+            ta.hist = c->d_snap_hist;
+            ta.sample_hist = c->d_snap_sample_hist;
+            ta.target_cdf = c->d_snap_target_cdf;
+            ta.target_scalars = c->d_snap_target_scalars;
+            ta.snap_stride = a.snap_stride;
+            ta.rid0 = hsa.rid0;
+            ta.rid_stride = hsa.rid_stride;
+            ta.reps_per_set = hsa.reps_per_set;
+            ta.seed = p.seed;
+            ta.n = ch.n;
+            ta.n_snap = p.n_snapshots;
+            ta.n_sets = p.n_param_sets;
+            ta.bins = p.hist_bins;
+            ta.m = c->snap_m;
+            ta.table_slots = c->snap_m ? ecdna::subsample_table_slots(c->snap_m) : 0u;
+            // one wave per (replicate, snapshot): a workgroup's share as the subsampling pass's
+            const uint32_t tw = ecdna::snapstats_waves(ta.bins, ta.table_slots, nullptr, nullptr);
+            ta.reps_per_block = std::max<uint32_t>(tw, (ch.n + hist_blocks_max - 1) / hist_blocks_max);
+            HIP_TRY(ecdna::launch_snapstats(ta, (ch.n + ta.reps_per_block - 1) / ta.reps_per_block, st));
         }
         HIP_TRY(hipEventRecord(ch.ev[2], st));
     }
@@ -1006,7 +1119,8 @@ int ecdna_ssa_ctx_download_snapshots(ecdna_ssa_ctx* c, ecdna_snapshot_t* meta, u
     const uint64_t ns = p.n_replicates * p.n_snapshots;
     if (meta) HIP_TRY(hipMemcpy(meta, c->d_snap_meta, ns * sizeof(ecdna_snapshot_t), hipMemcpyDeviceToHost));
     if (rows) {
-        if (!c->d_snap_rows) return fail(ECDNA_E_STATE, "snapshot rows need ECDNA_FLAG_SNAPSHOT_ROWS");
+        if (!c->d_snap_rows || c->snap_rows_local)
+            return fail(ECDNA_E_STATE, "snapshot rows need ECDNA_FLAG_SNAPSHOT_ROWS");
         HIP_TRY(hipMemcpy(rows, c->d_snap_rows, ns * c->out_stride * sizeof(uint16_t), hipMemcpyDeviceToHost));
     }
     return ECDNA_OK;
@@ -1036,6 +1150,27 @@ int ecdna_ssa_ctx_download_sample(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats
     if (out_sample_hist)
         HIP_TRY(hipMemcpy(out_sample_hist, c->d_sample_hist,
                           (uint64_t)p.n_param_sets * p.hist_bins * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_download_snapshot_stats(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats,
+                                          ecdna_rep_stats_t* out_sample_stats, uint64_t* out_hist,
+                                          uint64_t* out_sample_hist) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!c->snap_stats) return fail(ECDNA_E_STATE, "snapshot statistics need ecdna_ssa_ext_t.snapshot_stats");
+    if (!c->launched) return fail(ECDNA_E_STATE, "download before launch");
+    if ((out_sample_stats || out_sample_hist) && !c->snap_m)
+        return fail(ECDNA_E_STATE, "the snapshot samples need ecdna_ssa_ext_t.snapshot_subsample_cells > 0");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t ns = p.n_replicates * p.n_snapshots * sizeof(ecdna_rep_stats_t);
+    const uint64_t hb = (uint64_t)p.n_snapshots * p.n_param_sets * p.hist_bins * sizeof(uint64_t);
+    if (out_stats && ns) HIP_TRY(hipMemcpy(out_stats, c->d_snap_stats, ns, hipMemcpyDeviceToHost));
+    if (out_sample_stats && ns)
+        HIP_TRY(hipMemcpy(out_sample_stats, c->d_snap_sample_stats, ns, hipMemcpyDeviceToHost));
+    if (out_hist) HIP_TRY(hipMemcpy(out_hist, c->d_snap_hist, hb, hipMemcpyDeviceToHost));
+    if (out_sample_hist) HIP_TRY(hipMemcpy(out_sample_hist, c->d_snap_sample_hist, hb, hipMemcpyDeviceToHost));
     return ECDNA_OK;
 }
 

@@ -1,6 +1,6 @@
 // ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by the device
 // code (steppers: ssa_kernels.hip, ssa_refdraws.hip; end-of-run passes: ssa_hist.hip,
-// ssa_subsample.hip) and ssa_api.cpp (the C ABI).
+// ssa_subsample.hip, ssa_snapstats.hip) and ssa_api.cpp (the C ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -130,6 +130,32 @@ struct SubsampleArgs {
     uint32_t bag_c32;
 };
 
+// Per-snapshot ABC statistics over one chunk (ssa_snapstats.hip; ecdna_ssa_ext_t.snapshot_stats): for every replicate
+// and snapshot, the statistics of the saved state (and of a sample of m of its cells), and per snapshot and set the
+// sum of the saved states' (the samples') histograms. A snapshot that was not taken counts as an empty population.
+struct SnapStatsArgs {
+    const ecdna_snapshot_t* snap_meta;    // [n][n_snap], chunk-offset
+    const uint16_t* snap_rows;            // [n][n_snap][snap_stride]: the chunk's snapshot rows (expanded u16 rows)
+    ecdna_rep_stats_t* stats;             // [n][n_snap], chunk-offset
+    ecdna_rep_stats_t* sample_stats;      // [n][n_snap], chunk-offset; nullptr when m == 0
+    uint64_t* hist;                       // [n_snap][n_sets][bins]
+    uint64_t* sample_hist;                // [n_snap][n_sets][bins]; nullptr when m == 0
+    const double* target_cdf;             // [n_snap][bins]: each snapshot's own target, or nullptr (no distances)
+    const double* target_scalars;         // [n_snap][3]: the targets' mean, entropy, N+ frequency
+    uint64_t snap_stride;
+    uint64_t rid0;
+    uint64_t rid_stride;                  // >= 1
+    uint64_t reps_per_set;
+    uint64_t seed;
+    uint32_t n;
+    uint32_t n_snap;
+    uint32_t n_sets;
+    uint32_t bins;
+    uint32_t reps_per_block;
+    uint32_t m;                           // sample size (cells), 0 = no samples, <= kMaxSubsampleCells
+    uint32_t table_slots;                 // per-wave table of drawn positions: subsample_table_slots(m), 0 when m == 0
+};
+
 constexpr uint32_t kMaxSubsampleCells = 4096;  // LDS: 8 B of table per sampled cell and wave (<= 32 KiB)
 constexpr int kStepperBlock = 256;
 constexpr int kBinWideBlock = 64;  // bin store with 256 bins
@@ -170,6 +196,11 @@ hipError_t launch_hist(const HistArgs& a, uint32_t blocks, hipStream_t stream);
 uint32_t subsample_table_slots(uint32_t m);
 uint32_t subsample_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, size_t* lds_bytes);
 hipError_t launch_subsample(const SubsampleArgs& a, uint32_t blocks, hipStream_t stream);
+// The snapshot statistics pass (ssa_snapstats.hip): one wave per (replicate, snapshot); 1, 2 or 4 waves per workgroup,
+// as many as keep its dynamic LDS (lds_bytes) within 64 KiB. sample_hist_lds: whether the workgroup's sum of the
+// samples' histograms has room in LDS beside the rest (else the waves add their samples' bins to global memory).
+uint32_t snapstats_waves(uint32_t bins, uint32_t table_slots, size_t* lds_bytes, bool* sample_hist_lds);
+hipError_t launch_snapstats(const SnapStatsArgs& a, uint32_t blocks, hipStream_t stream);
 // The reference-draws stepper (row store; ssa_refdraws.hip)
 const void* refdraws_kernel(int birth_death, int segregation);
 int refdraws_block();

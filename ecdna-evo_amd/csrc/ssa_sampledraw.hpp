@@ -1,0 +1,148 @@
+// ssa_sampledraw.hpp — the draws of subsample mapping v1 (include/ecdna_ssa.h), shared by the
+// end-of-run sample (ssa_subsample.hip) and the samples at the snapshots (ssa_snapstats.hip): the Lemire draw below N
+// on a tagged Philox stream, the wave's table of the positions drawn so far, and the position -> copy number lookup.
+// One 64-lane wave per population; every lane of the wave calls wave_sample_picks.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "ssa_device.hpp"
+#include "ssa_wave.hpp"
+
+#pragma clang fp contract(off)
+
+namespace ecdna {
+
+constexpr uint32_t kSubEmpty = 0xffffffffu;
+constexpr uint32_t kSubTag = 0xC0000000u;      // Philox counter word 1 of draw block t: kSubTag | stream | t
+constexpr uint32_t kSubMaxDraws = 1u << 16;    // the guard: draws per population
+constexpr uint32_t kSubMaxBlocks = 1024;       // Philox blocks per draw (each rejects with p < 2^-4: unreachable)
+
+// The stream field of counter word 1: 0 for the end-of-run sample, (s + 1) << 16 for the sample at snapshot s
+// (t < kSubMaxBlocks = 2^10 and s < kMaxSnapshots = 64, so the fields never meet and stay below kSubTag's bits).
+__host__ __device__ constexpr uint32_t sample_stream_tag(uint32_t snapshot_plus_one) {
+    return kSubTag | (snapshot_plus_one << 16);
+}
+
+// Draw i of replicate (rid_lo, rid_hi): a Lemire draw below N. Philox block t = 0, 1, ... on counter
+// (i, tag | t, rid lo, rid hi); its four words are tried in order, word x gives p = x * N and is accepted as
+// p >> 32 when the low half is >= thr = (2^32 - N) mod N.
+__device__ __forceinline__ uint32_t sub_draw(uint32_t i, uint32_t N, uint32_t thr, uint32_t tag, uint32_t rid_lo,
+                                             uint32_t rid_hi, uint32_t k0, uint32_t k1, bool& fail) {
+    for (uint32_t t = 0; t < kSubMaxBlocks; ++t) {
+        const uint4 w = philox4x32_10(make_uint4(i, tag | t, rid_lo, rid_hi), k0, k1);
+        const uint32_t x[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t p = (uint64_t)x[j] * N;
+            if ((uint32_t)p >= thr) return (uint32_t)(p >> 32);
+        }
+    }
+    fail = true;
+    return 0u;
+}
+
+// A population of N = nm + (N+ cells) cells in download order: positions 0 .. nm - 1 are the N- cells, then `small`
+// cells held in bin counters (BAG: pre[bag_k] their inclusive prefix sums, in the wave's LDS), then row[0 .. nrow).
+struct SamplePop {
+    uint64_t nm;
+    const uint32_t* pre;
+    uint32_t bag_k;
+    uint32_t small;
+    const uint16_t* row;
+    uint32_t nrow;
+};
+
+// Steps 2-4 of the mapping: draws on stream `tag` until mp distinct positions below N have appeared; every new one is
+// looked up and counted into the wave's histogram wh (bins clip at `last`; comp: taken out of it, the picked cells
+// are those left out of the sample). psum gains the lane's sum of k over its picked positions. tab[table_slots] is
+// the wave's table of drawn positions (LDS). Returns true when the guard ends the population (too small a table, 2^16
+// draws, a position the counters and the row cannot account for): wh is then not to be used.
+template <int BAG>
+__device__ __forceinline__ bool wave_sample_picks(uint32_t* wh, uint32_t* tab, uint32_t table_slots,
+                                                  const SamplePop& pop, uint32_t N, uint32_t mp, bool comp,
+                                                  uint32_t last, uint32_t tag, uint64_t rid, uint32_t k0, uint32_t k1,
+                                                  uint32_t lane, uint64_t& psum) {
+    // table: 2 * pow2ceil(m') slots (load <= 1/2), hashed by the top bits of a multiplicative hash
+    const uint32_t lg = mp > 1u ? 32u - (uint32_t)__clz(mp - 1u) : 0u;
+    const uint32_t tsize = 2u << lg;
+    const uint32_t sh = 31u - lg;
+    bool bad = tsize > table_slots;
+    const uint32_t tclear = bad ? 0u : tsize;
+    for (uint32_t b = lane; b < tclear; b += 64u) tab[b] = kSubEmpty;
+    wave_sync_lds();
+    const uint32_t thr = (0u - N) % N;
+    const uint32_t rid_lo = (uint32_t)rid, rid_hi = (uint32_t)(rid >> 32);
+    bool lane_bad = false;
+    uint32_t count = bad ? mp : 0u, base = 0;
+    while (count < mp && base < kSubMaxDraws) {
+        // the next draws, one per lane: at most as many as positions are still missing, so every new
+        // draw of the batch is one of the first m' and the table never holds more than m' positions
+        const uint32_t nact = min(64u, min(mp - count, kSubMaxDraws - base));
+        const bool active = lane < nact;
+        uint32_t v = kSubEmpty;
+        if (active) v = sub_draw(base + lane, N, thr, tag, rid_lo, rid_hi, k0, k1, lane_bad);
+        // a draw that repeats an earlier one of its batch is not new, whichever lane reaches LDS first
+        bool dup = false;
+        for (uint32_t j = 0; j + 1u < nact; ++j) {
+            const uint32_t vj = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j);
+            dup = dup || (j < lane && vj == v);
+        }
+        // the others are distinct: each is new iff the table did not hold it before the batch
+        bool isnew = false;
+        if (active && !dup && !lane_bad) {
+            uint32_t sl = (v * 0x9E3779B1u) >> sh;
+            bool placed = false;
+            for (uint32_t probe = 0; probe < tsize; ++probe) {
+                const uint32_t old = atomicCAS(&tab[sl], kSubEmpty, v);
+                if (old == kSubEmpty || old == v) {
+                    isnew = old == kSubEmpty;
+                    placed = true;
+                    break;
+                }
+                sl = (sl + 1u) & (tsize - 1u);
+            }
+            if (!placed) lane_bad = true;
+        }
+        if (isnew) {
+            // position -> copy number, in download order: N- cells, the counters k ascending, the row
+            uint32_t kk = 0;
+            bool ok = true;
+            if ((uint64_t)v >= pop.nm) {
+                const uint32_t u = v - (uint32_t)pop.nm;
+                if (BAG && u < pop.small) {
+                    uint32_t lo = 0, hi = pop.bag_k - 1u;  // the first b with pre[b] > u
+                    while (lo < hi) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (pop.pre[mid] > u)
+                            hi = mid;
+                        else
+                            lo = mid + 1u;
+                    }
+                    kk = lo + 1u;
+                } else {
+                    const uint32_t j = u - pop.small;
+                    ok = j < pop.nrow;  // a position the counters and the row cannot account for
+                    if (ok) kk = pop.row[j];
+                }
+            }
+            if (ok) {
+                const uint32_t bin = kk < last ? kk : last;
+                if (comp)
+                    atomicSub(&wh[bin], 1u);
+                else
+                    atomicAdd(&wh[bin], 1u);
+                psum += kk;
+            } else {
+                lane_bad = true;
+            }
+        }
+        count += (uint32_t)__popcll(__ballot(isnew));
+        base += nact;
+        wave_sync_lds();
+    }
+    return bad || count < mp || __any(lane_bad);
+}
+
+}  // namespace ecdna

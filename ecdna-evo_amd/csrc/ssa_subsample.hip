@@ -10,12 +10,14 @@
 //
 // One wave per replicate, as ssa_hist<true, BAG>. Per wave in LDS: the replicate's histogram (u32 per bin), the
 // inclusive prefix sums of its bin counters (position -> copy number), and an open-addressing table of the
-// positions drawn so far (u32, 0xffffffff = empty), which decides whether a draw is new.
+// positions drawn so far (u32, 0xffffffff = empty), which decides whether a draw is new. The draws, the table and the
+// position -> copy number lookup are wave_sample_picks (ssa_sampledraw.hpp), shared with ssa_snapstats.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ssa_device.hpp"
 #include "ssa_launch.h"
+#include "ssa_sampledraw.hpp"
 #include "ssa_wave.hpp"
 
 #pragma clang fp contract(off)
@@ -24,29 +26,7 @@ namespace ecdna {
 
 namespace {
 
-constexpr uint32_t kSubEmpty = 0xffffffffu;
-constexpr uint32_t kSubTag = 0xC0000000u;      // Philox counter word 1 of draw block t: kSubTag | t
-constexpr uint32_t kSubMaxDraws = 1u << 16;    // the guard: draws per replicate
-constexpr uint32_t kSubMaxBlocks = 1024;       // Philox blocks per draw (each rejects with p < 2^-4: unreachable)
 constexpr uint32_t kSubBlock = 256;
-
-// Draw i of replicate (rid_lo, rid_hi): a Lemire draw below N. Philox block t = 0, 1, ... on counter
-// (i, kSubTag | t, rid lo, rid hi); its four words are tried in order, word x gives p = x * N and is accepted as
-// p >> 32 when the low half is >= thr = (2^32 - N) mod N.
-__device__ __forceinline__ uint32_t sub_draw(uint32_t i, uint32_t N, uint32_t thr, uint32_t rid_lo, uint32_t rid_hi,
-                                             uint32_t k0, uint32_t k1, bool& fail) {
-    for (uint32_t t = 0; t < kSubMaxBlocks; ++t) {
-        const uint4 w = philox4x32_10(make_uint4(i, kSubTag | t, rid_lo, rid_hi), k0, k1);
-        const uint32_t x[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const uint64_t p = (uint64_t)x[j] * N;
-            if ((uint32_t)p >= thr) return (uint32_t)(p >> 32);
-        }
-    }
-    fail = true;
-    return 0u;
-}
 
 // BAG as in ssa_hist: 0 = rows only; 1 / 2 = u16 / u32 bin counters bags[q][bag_k] for copy numbers 1..bag_k plus
 // the large-k cells at the head of the row.
@@ -127,85 +107,9 @@ __global__ void __launch_bounds__(kSubBlock) ssa_subsample(const SubsampleArgs a
             // 2.-4. draws until m' distinct positions have appeared; every new one is looked up and counted
             uint64_t psum = 0;  // sum of k over the picked positions
             if (!whole && !bad) {
-                // table: 2 * pow2ceil(m') slots (load <= 1/2), hashed by the top bits of a multiplicative hash
-                const uint32_t lg = mp > 1u ? 32u - (uint32_t)__clz(mp - 1u) : 0u;
-                const uint32_t tsize = 2u << lg;
-                const uint32_t sh = 31u - lg;
-                bad = tsize > a.table_slots;
-                const uint32_t tclear = bad ? 0u : tsize;
-                for (uint32_t b = lane; b < tclear; b += 64u) tab[b] = kSubEmpty;
-                wave_sync_lds();
-                const uint32_t thr = (0u - N) % N;
-                const uint32_t rid_lo = (uint32_t)rid, rid_hi = (uint32_t)(rid >> 32);
-                bool lane_bad = false;
-                uint32_t count = bad ? mp : 0u, base = 0;
-                while (count < mp && base < kSubMaxDraws) {
-                    // the next draws, one per lane: at most as many as positions are still missing, so every new
-                    // draw of the batch is one of the first m' and the table never holds more than m' positions
-                    const uint32_t nact = min(64u, min(mp - count, kSubMaxDraws - base));
-                    const bool active = lane < nact;
-                    uint32_t v = kSubEmpty;
-                    if (active) v = sub_draw(base + lane, N, thr, rid_lo, rid_hi, k0, k1, lane_bad);
-                    // a draw that repeats an earlier one of its batch is not new, whichever lane reaches LDS first
-                    bool dup = false;
-                    for (uint32_t j = 0; j + 1u < nact; ++j) {
-                        const uint32_t vj = (uint32_t)__builtin_amdgcn_readlane((int)v, (int)j);
-                        dup = dup || (j < lane && vj == v);
-                    }
-                    // the others are distinct: each is new iff the table did not hold it before the batch
-                    bool isnew = false;
-                    if (active && !dup && !lane_bad) {
-                        uint32_t sl = (v * 0x9E3779B1u) >> sh;
-                        bool placed = false;
-                        for (uint32_t probe = 0; probe < tsize; ++probe) {
-                            const uint32_t old = atomicCAS(&tab[sl], kSubEmpty, v);
-                            if (old == kSubEmpty || old == v) {
-                                isnew = old == kSubEmpty;
-                                placed = true;
-                                break;
-                            }
-                            sl = (sl + 1u) & (tsize - 1u);
-                        }
-                        if (!placed) lane_bad = true;
-                    }
-                    if (isnew) {
-                        // position -> copy number, in download order: N- cells, the counters k ascending, the row
-                        uint32_t kk = 0;
-                        bool ok = true;
-                        if ((uint64_t)v >= nm) {
-                            const uint32_t u = v - (uint32_t)nm;
-                            if (BAG && u < small) {
-                                uint32_t lo = 0, hi = a.bag_k - 1u;  // the first b with pre[b] > u
-                                while (lo < hi) {
-                                    const uint32_t mid = (lo + hi) >> 1;
-                                    if (pre[mid] > u)
-                                        hi = mid;
-                                    else
-                                        lo = mid + 1u;
-                                }
-                                kk = lo + 1u;
-                            } else {
-                                const uint32_t j = u - small;
-                                ok = j < nrow;  // a position the counters and the row cannot account for
-                                if (ok) kk = row[j];
-                            }
-                        }
-                        if (ok) {
-                            const uint32_t bin = kk < last ? kk : last;
-                            if (comp)
-                                atomicSub(&wh[bin], 1u);
-                            else
-                                atomicAdd(&wh[bin], 1u);
-                            psum += kk;
-                        } else {
-                            lane_bad = true;
-                        }
-                    }
-                    count += (uint32_t)__popcll(__ballot(isnew));
-                    base += nact;
-                    wave_sync_lds();
-                }
-                bad = bad || count < mp || __any(lane_bad);
+                const SamplePop pop{nm, pre, a.bag_k, small, row, nrow};
+                bad = wave_sample_picks<BAG>(wh, tab, a.table_slots, pop, N, mp, comp, last, sample_stream_tag(0u), rid,
+                                             k0, k1, lane, psum);
             }
             wave_sync_lds();
 

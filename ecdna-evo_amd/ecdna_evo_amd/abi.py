@@ -98,6 +98,18 @@ class Params(C.Structure):
     ]
 
 
+class Ext(C.Structure):
+    """ecdna_ssa_ext_t: the extension block of ecdna_ssa_ctx_create_ext (added within ABI v13)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("snapshot_stats", C.c_uint32),
+        ("snapshot_target_hists", C.POINTER(C.c_uint64)),
+        ("snapshot_subsample_cells", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 STATS_DTYPE = np.dtype([("mean", "<f8"), ("entropy", "<f8"), ("frequency", "<f8"), ("ks", "<f8"),
                         ("mean_rel", "<f8"), ("entropy_rel", "<f8"), ("frequency_diff", "<f8"), ("cells", "<u8")])
 assert STATS_DTYPE.itemsize == 64
@@ -226,7 +238,16 @@ class RunSpec:
     # end-of-run subsampling on the GPU (ABI v13): statistics and histogram of a sample of this many cells of every
     # replicate's final population (Result.sample_stats / sample_hist); 0 = off; needs FLAG_REP_STATS; <= 4096
     subsample_cells: int = 0
+    # per-snapshot ABC statistics on the GPU (ecdna_ssa_ext_t, within ABI v13): the statistics of every replicate's
+    # state at every snapshot (Result.snapshot_stats / snapshot_hist), distances against snapshot_targets[s]
+    # ([S][hist_bins], or None: no distances), and of a sample of snapshot_subsample_cells of its cells
+    # (Result.snapshot_sample_stats / snapshot_sample_hist; 0 = off, <= 4096). Needs snapshots and FLAG_REP_STATS;
+    # without FLAG_SNAPSHOT_ROWS the snapshot rows stay on the device, one chunk at a time
+    snapshot_stats: bool = False
+    snapshot_targets: Optional[Sequence[Sequence[int]]] = None
+    snapshot_subsample_cells: int = 0
     _keep: list = field(default_factory=list, repr=False)
+    _keep_ext: list = field(default_factory=list, repr=False)
 
     def stride(self) -> int:
         """The id step as the C ABI reads it: replicate_stride 0 means 1 (include/ecdna_ssa.h)."""
@@ -344,6 +365,25 @@ class RunSpec:
             cap = max(int(min(self.max_cells, 2**32 - 1)), max_np, 1)
         p.cell_cap = cap
         return p
+
+    def ext(self) -> Optional[Ext]:
+        """The extension block this spec asks for, or None: the context is then made by ecdna_ssa_ctx_create."""
+        if not (self.snapshot_stats or self.snapshot_targets is not None or self.snapshot_subsample_cells):
+            return None
+        if not (0 <= int(self.snapshot_subsample_cells) < (1 << 32)):
+            raise ValueError(f"snapshot_subsample_cells = {self.snapshot_subsample_cells} does not fit the ABI's u32 field")
+        self._keep_ext = []
+        e = Ext()
+        e.struct_size = C.sizeof(Ext)
+        e.snapshot_stats = 1 if self.snapshot_stats else 0
+        e.snapshot_subsample_cells = self.snapshot_subsample_cells
+        if self.snapshot_targets is not None:
+            tgt = np.ascontiguousarray(self.snapshot_targets, dtype=np.uint64)
+            if tgt.shape != (len(self.snapshots or ()), self.hist_bins):
+                raise ValueError("snapshot_targets must have one histogram of hist_bins entries per snapshot")
+            self._keep_ext.append(tgt)
+            e.snapshot_target_hists = _ptr(tgt, C.c_uint64)
+        return e
 
 
 def cost_hint(rates: Sequence[Sequence[float]], inits: Optional[Sequence[Dict[int, int]]] = None) -> List[float]:

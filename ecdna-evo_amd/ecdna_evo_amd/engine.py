@@ -28,6 +28,7 @@ EXPORTS = [
     "ecdna_ssa_device_count",
     "ecdna_ssa_run",
     "ecdna_ssa_ctx_create",
+    "ecdna_ssa_ctx_create_ext",
     "ecdna_ssa_ctx_set_outputs",
     "ecdna_ssa_ctx_launch",
     "ecdna_ssa_ctx_sync",
@@ -36,6 +37,7 @@ EXPORTS = [
     "ecdna_ssa_ctx_download_snapshots",
     "ecdna_ssa_ctx_download_stats",
     "ecdna_ssa_ctx_download_sample",
+    "ecdna_ssa_ctx_download_snapshot_stats",
     "ecdna_ssa_ctx_download_rng_words",
     "ecdna_ssa_ctx_row_stride",
     "ecdna_ssa_ctx_geometry",
@@ -124,6 +126,13 @@ def lib():
     L.ecdna_ssa_reduce_hist.restype = C.c_int
     L.ecdna_ssa_ctx_reduce.argtypes = [C.c_void_p, C.c_void_p]
     L.ecdna_ssa_ctx_reduce.restype = C.c_int
+    # (added within v13: a same-box A/B may load a v13 library built before them, which runs everything but the
+    # per-snapshot statistics; Context raises when a spec asks such a library for them)
+    if hasattr(L, "ecdna_ssa_ctx_create_ext"):
+        L.ecdna_ssa_ctx_create_ext.argtypes = [P(abi.Params), P(abi.Ext), P(C.c_void_p)]
+        L.ecdna_ssa_ctx_create_ext.restype = C.c_int
+        L.ecdna_ssa_ctx_download_snapshot_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ecdna_ssa_ctx_download_snapshot_stats.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -193,6 +202,13 @@ class Result:
         # the per-set sum of the samples' histograms, [n_sets][hist_bins] u64 (else None)
         self.sample_stats = None
         self.sample_hist = None
+        # RunSpec.snapshot_stats: the statistics of every replicate's state at every snapshot, [n][S] abi.STATS_DTYPE
+        # (a snapshot not taken: an empty population), and per snapshot and set the sum of the states' histograms,
+        # [S][n_sets][hist_bins] u64; with snapshot_subsample_cells > 0 the same for the samples (else None)
+        self.snapshot_stats = None
+        self.snapshot_hist = None
+        self.snapshot_sample_stats = None
+        self.snapshot_sample_hist = None
         self.rng_words = None  # [n] u64 under FLAG_REFERENCE_DRAWS: ChaCha8 stream position at the end
 
     def row(self, i: int) -> np.ndarray:
@@ -205,11 +221,19 @@ class Result:
 class Context:
     """A device-resident run (ecdna_ssa_ctx): create once, launch many times."""
 
-    def __init__(self, spec: "abi.RunSpec"):
+    def __init__(self, spec: "abi.RunSpec", ext: Optional["abi.Ext"] = None):
+        """`ext`: an explicit extension block (ecdna_ssa_ctx_create_ext); default: the one `spec` asks for, if any."""
         self.spec = spec
         self.params = spec.params()
+        self.ext = ext if ext is not None else spec.ext()
         h = C.c_void_p()
-        _check(lib().ecdna_ssa_ctx_create(C.byref(self.params), C.byref(h)), "ecdna_ssa_ctx_create")
+        if self.ext is not None:  # (only a spec that asks for the extension goes through _ext)
+            if not hasattr(lib(), "ecdna_ssa_ctx_create_ext"):
+                raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_ext (per-snapshot statistics)")
+            _check(lib().ecdna_ssa_ctx_create_ext(C.byref(self.params), C.byref(self.ext), C.byref(h)),
+                   "ecdna_ssa_ctx_create_ext")
+        else:
+            _check(lib().ecdna_ssa_ctx_create(C.byref(self.params), C.byref(h)), "ecdna_ssa_ctx_create")
         self.h = h
 
     def close(self):
@@ -292,6 +316,18 @@ class Context:
             _check(lib().ecdna_ssa_ctx_download_sample(self.h, st.ctypes.data, sh.ctypes.data), "download_sample")
             res.sample_stats = st
             res.sample_hist = sh.reshape(p.n_param_sets, p.hist_bins)
+        if self.ext is not None and self.ext.snapshot_stats:
+            S, m = p.n_snapshots, self.ext.snapshot_subsample_cells
+            shape = (S, p.n_param_sets, p.hist_bins)
+            st = np.zeros((p.n_replicates, S), dtype=abi.STATS_DTYPE)
+            sh = np.zeros(shape, dtype=np.uint64)
+            sst = np.zeros((p.n_replicates, S), dtype=abi.STATS_DTYPE) if m else None
+            ssh = np.zeros(shape, dtype=np.uint64) if m else None
+            _check(lib().ecdna_ssa_ctx_download_snapshot_stats(
+                self.h, st.ctypes.data, sst.ctypes.data if m else None, sh.ctypes.data, ssh.ctypes.data if m else None),
+                "download_snapshot_stats")
+            res.snapshot_stats, res.snapshot_hist = st, sh
+            res.snapshot_sample_stats, res.snapshot_sample_hist = sst, ssh
         if p.flags & abi.FLAG_REFERENCE_DRAWS:
             w = np.zeros(p.n_replicates, dtype=np.uint64)
             _check(lib().ecdna_ssa_ctx_download_rng_words(self.h, w.ctypes.data), "download_rng_words")

@@ -126,13 +126,15 @@ def gather_records(local, total: int, layout: str = "contiguous", group=None):
 def gather_structured(arr, total: int, layout: str = "contiguous", device=None, group=None):
     """gather_records for a numpy structured array (ecdna_rep_summary_t or ecdna_rep_stats_t records as
     abi.SUMMARY_DTYPE / abi.STATS_DTYPE): the records travel as raw bytes, so every field comes back
-    bit for bit. `device`: where the exchange buffers live ("cuda" under RCCL, None = CPU for gloo)."""
+    bit for bit. One record per replicate, or a row of them ([n][S]: the per-snapshot statistics), which comes
+    back as [total][S]. `device`: where the exchange buffers live ("cuda" under RCCL, None = CPU for gloo)."""
     import numpy as np
     import torch
 
-    raw = np.ascontiguousarray(arr).view(np.uint8).reshape(len(arr), arr.dtype.itemsize)
+    per_replicate = int(np.prod(arr.shape[1:], dtype=np.int64))
+    raw = np.ascontiguousarray(arr).view(np.uint8).reshape(len(arr), per_replicate * arr.dtype.itemsize)
     t = torch.from_numpy(raw.copy())
     if device is not None:
         t = t.to(device)
     g = gather_records(t, total, layout, group).cpu().numpy()
-    return np.ascontiguousarray(g).view(arr.dtype).reshape(-1)
+    return np.ascontiguousarray(g).view(arr.dtype).reshape((-1,) + tuple(arr.shape[1:]))

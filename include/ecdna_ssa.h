@@ -43,7 +43,10 @@
 extern "C" {
 #endif
 
-/* ABI v13: end-of-run subsampling on the GPU. ecdna_ssa_params_t gains subsample_cells and reserved1 (appended after
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): per-snapshot ABC
+ * statistics on the GPU for longitudinal inference — the extension block ecdna_ssa_ext_t, ecdna_ssa_ctx_create_ext and
+ * ecdna_ssa_ctx_download_snapshot_stats (below). ecdna_ssa_ctx_create(p, out) is ecdna_ssa_ctx_create_ext(p, NULL, out).
+ * ABI v13: end-of-run subsampling on the GPU. ecdna_ssa_params_t gains subsample_cells and reserved1 (appended after
  * reserved0, so the v10-v12 layout is a prefix of this one) and ecdna_ssa_ctx_download_sample returns the statistics
  * and the per-set histogram of a sample of subsample_cells cells of every replicate's final population (subsample
  * mapping v1, below). With subsample_cells = 0 no new kernel is launched and every output is v12's; the draw mapping
@@ -314,6 +317,40 @@ int ecdna_ssa_run(const ecdna_ssa_params_t* p, ecdna_rep_summary_t* out_summarie
 typedef struct ecdna_ssa_ctx ecdna_ssa_ctx;
 
 int ecdna_ssa_ctx_create(const ecdna_ssa_params_t* p, ecdna_ssa_ctx** out);
+
+/* Extension block of ecdna_ssa_ctx_create_ext (added within ABI v13; ecdna_ssa_params_t does not grow).
+ *
+ * Per-snapshot ABC statistics (abc.md's `timepoint` column: a patient, or a culture, is sampled several times as the
+ * tumour grows, and a run is scored against the data of every timepoint). With snapshot_stats = 1, after every chunk's
+ * stepper and histogram pass the GPU computes, for every replicate and every snapshot of params.snapshot_cells, the
+ * ecdna_rep_stats_t of the saved state (n- N- cells and the snapshot's N+ row), with the definitions of the end-of-run
+ * statistics: mean from the true copy numbers, bins clipped at hist_bins - 1, distances against snapshot s's OWN target
+ * snapshot_target_hists[s]. A snapshot that was not taken (ecdna_snapshot_t.taken == 0: the replicate never had that
+ * many cells before an event) is scored as an empty population — cells, mean, entropy and frequency 0, ks 1.0 with a
+ * target — and adds nothing to a histogram; ecdna_ssa_ctx_download_snapshots tells the two cases apart. Needs
+ * params.n_snapshots > 0 and ECDNA_FLAG_REP_STATS.
+ *
+ * Without ECDNA_FLAG_SNAPSHOT_ROWS the snapshot rows are scratch of one chunk (chunk_replicates x n_snapshots rows
+ * instead of n_replicates x n_snapshots: large runs chunk instead of failing) and are not downloadable; with it the
+ * whole run's rows are kept as before.
+ *
+ * Sampling at the snapshots: snapshot_subsample_cells = m > 0 also draws a uniform sample of m cells of every taken
+ * snapshot by subsample mapping v1 (ecdna_ssa_params_t.subsample_cells above) — the population is the nminus N- cells
+ * followed by the snapshot row — and keeps the sample's statistics and histogram. The one difference is the stream:
+ * draw i of snapshot s (s = 0 .. n_snapshots - 1 < 64) uses Philox counter
+ * (i, 0xC0000000 | (s + 1) << 16 | t, r lo, r hi) with t < 1024, disjoint from the end-of-run sample's (field 0) and
+ * from every other snapshot's, so the samples of different timepoints are independent. */
+typedef struct {
+    uint32_t struct_size;               /* sizeof(ecdna_ssa_ext_t); anything else: ECDNA_E_INVALID */
+    uint32_t snapshot_stats;            /* 0 / 1 */
+    const uint64_t* snapshot_target_hists; /* host, [n_snapshots][hist_bins], or NULL: no distances */
+    uint32_t snapshot_subsample_cells;  /* 0 = off, <= 4096 */
+    uint32_t reserved;                  /* must be 0 */
+} ecdna_ssa_ext_t;
+/* ecdna_ssa_ctx_create with an extension block. ext == NULL or ext->snapshot_stats == 0: nothing more is allocated or
+ * launched and every output is ecdna_ssa_ctx_create's (struct_size, reserved and the sample size's range are checked
+ * whenever ext is given). */
+int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, ecdna_ssa_ctx** out);
 /* Use caller-owned DEVICE buffers for the histogram [n_param_sets*hist_bins] u64 and totals
  * [n_param_sets] (e.g. tensors later all-reduced over RCCL). NULL keeps the internal buffer. */
 int ecdna_ssa_ctx_set_outputs(ecdna_ssa_ctx* c, uint64_t* d_hist, ecdna_totals_t* d_totals);
@@ -322,7 +359,8 @@ int ecdna_ssa_ctx_set_outputs(ecdna_ssa_ctx* c, uint64_t* d_hist, ecdna_totals_t
 int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream);
 /* Block until the last launch finished; returns its device time in ms (HIP events on the launch
  * stream): ssa_ms = SSA stepper kernels only, hist_ms = histogram/summary kernels (and the
- * subsampling pass when params.subsample_cells > 0). Either may be NULL. */
+ * subsampling pass when params.subsample_cells > 0, and the snapshot statistics pass under
+ * ecdna_ssa_ext_t.snapshot_stats). Either may be NULL. */
 int ecdna_ssa_ctx_sync(ecdna_ssa_ctx* c, float* ssa_ms, float* hist_ms);
 /* Device pointers of the current outputs. */
 int ecdna_ssa_ctx_device_outputs(ecdna_ssa_ctx* c, uint64_t** d_hist, ecdna_totals_t** d_totals);
@@ -335,7 +373,7 @@ int ecdna_ssa_ctx_download(ecdna_ssa_ctx* c, ecdna_rep_summary_t* out_summaries,
                            ecdna_totals_t* out_totals, uint16_t* out_rows);
 /* Snapshots of the last launch: meta[n_replicates][n_snapshots] and, under ECDNA_FLAG_SNAPSHOT_ROWS,
  * rows[n_replicates][n_snapshots][row_stride] u16 (the N+ cells at the save, in the order of
- * ecdna_ssa_ctx_download).
+ * ecdna_ssa_ctx_download; without the flag rows must be NULL, else ECDNA_E_STATE).
  * Either may be NULL. */
 int ecdna_ssa_ctx_download_snapshots(ecdna_ssa_ctx* c, ecdna_snapshot_t* meta, uint16_t* rows);
 /* Per-replicate statistics of the last launch (needs ECDNA_FLAG_REP_STATS): out[n_replicates]. */
@@ -347,6 +385,16 @@ int ecdna_ssa_ctx_download_stats(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out);
  * out_hist (bin 0 = N- cells, last bin = overflow). Chunked runs are covered (the buffers are sized by the run, not
  * the chunk). ecdna_ssa_ctx_reduce does not reduce the sample histogram: callers sum the shards' themselves. */
 int ecdna_ssa_ctx_download_sample(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats, uint64_t* out_sample_hist);
+/* The per-snapshot statistics of the last launch (added within ABI v13; ecdna_ssa_ext_t.snapshot_stats, else
+ * ECDNA_E_STATE, as before a launch, and as when a sample buffer is asked for with snapshot_subsample_cells == 0). Any
+ * buffer may be NULL. out_stats[n_replicates][n_snapshots]: the statistics of replicate i's state at snapshot s;
+ * out_sample_stats, same shape: those of its sample (cells = the sample's size). out_hist and out_sample_hist
+ * [n_snapshots][n_param_sets][hist_bins]: per snapshot and set, the sum of the replicates' (samples') histograms,
+ * binned as out_hist of ecdna_ssa_ctx_download. Chunked runs are covered. ecdna_ssa_ctx_reduce does not reduce these
+ * histograms: callers sum the shards' themselves. */
+int ecdna_ssa_ctx_download_snapshot_stats(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats,
+                                          ecdna_rep_stats_t* out_sample_stats, uint64_t* out_hist,
+                                          uint64_t* out_sample_hist);
 /* Reference draws (ECDNA_FLAG_REFERENCE_DRAWS, ABI v7): per replicate, the number of 32-bit words its ChaCha8
  * stream (seed_from_u64(seed), stream seed*10 + r) had handed out when it stopped — where the reference's
  * end-of-run subsampling continues the same rng (into_subsampled(nb, &mut rng), src/main.rs:110-123, 184-197;
