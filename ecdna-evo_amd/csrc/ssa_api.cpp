@@ -1,6 +1,7 @@
 // ssa_api.cpp — the C ABI of include/ecdna_ssa.h: parameter validation,
 // device-resident run contexts, chunking by HBM capacity, and launches of the
-// stepper and end-of-run kernels (ssa_kernels.hip, ssa_hist.hip, ssa_subsample.hip, ssa_snapstats.hip).
+// stepper and end-of-run kernels (ssa_kernels.hip, ssa_hist.hip, ssa_subsample.hip, ssa_snapstats.hip,
+// ssa_passage.hip).
 //
 // This file replaces, for one GPU, the per-replicate driver loop of the
 // reference: run_simulations(idx) mapped by rayon over seed*10 .. seed*10+runs
@@ -59,7 +60,7 @@ InitOfSet init_of_set(const ecdna_ssa_params_t* p, uint64_t s) {
     return r;
 }
 
-int validate(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext) {
+int validate(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, const ecdna_ssa_passages_t* pas) {
     if (!p) return fail(ECDNA_E_INVALID, "params is NULL");
     if (!p->rates || p->n_param_sets == 0) return fail(ECDNA_E_INVALID, "rates/n_param_sets");
     for (uint32_t s = 0; s < p->n_param_sets; ++s) {  // (the steppers' f32 time-step division relies on it)
@@ -139,7 +140,42 @@ int validate(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext) {
             }
         }
     }
+    if (pas) {  // the passage block (serial passaging)
+        if (pas->struct_size != sizeof(ecdna_ssa_passages_t))
+            return fail(ECDNA_E_INVALID, "passages.struct_size must be sizeof(ecdna_ssa_passages_t)");
+        if (pas->reserved) return fail(ECDNA_E_INVALID, "passages.reserved must be 0");
+        if (pas->n_passages < 1u || pas->n_passages > ecdna::kMaxPassages)
+            return fail(ECDNA_E_INVALID, "passages.n_passages must be in [1, 16]");
+        if (pas->passage_cells < 1u || pas->passage_cells > ecdna::kMaxSubsampleCells)
+            return fail(ECDNA_E_INVALID, "passages.passage_cells must be in [1, 4096]");
+        if (pas->passage_cells > p->cell_cap)
+            return fail(ECDNA_E_INVALID, "passages.passage_cells must be <= cell_cap");
+        if (!(p->flags & ECDNA_FLAG_REP_STATS)) return fail(ECDNA_E_INVALID, "passages need ECDNA_FLAG_REP_STATS");
+        if (p->subsample_cells)
+            return fail(ECDNA_E_INVALID, "passages: subsample_cells must be 0 (passage_cells is the sample size)");
+        if (p->n_snapshots) return fail(ECDNA_E_INVALID, "passages: n_snapshots must be 0");
+        if (ext && ext->snapshot_stats) return fail(ECDNA_E_INVALID, "passages: ext.snapshot_stats must be 0");
+        if (p->flags & ECDNA_FLAG_REFERENCE_DRAWS)
+            return fail(ECDNA_E_INVALID, "passages do not run under ECDNA_FLAG_REFERENCE_DRAWS");
+        for (uint32_t g = 0; pas->passage_target_hists && g < pas->n_passages; ++g) {
+            const uint64_t* t = pas->passage_target_hists + (uint64_t)g * p->hist_bins;
+            bool any = false;
+            for (uint32_t b = 0; b < p->hist_bins; ++b) any |= t[b] != 0;
+            if (!any)
+                return fail(ECDNA_E_INVALID, "passages.passage_target_hists[" + std::to_string(g) + "] is empty");
+        }
+    }
     return ECDNA_OK;
+}
+
+// The Philox key of growth phase g of a passage run (passage mapping v1, include/ecdna_ssa.h): the seed itself for
+// phase 0, else the splitmix64 finaliser of seed + g * 0x9E3779B97F4A7C15.
+uint64_t passage_seed(uint64_t seed, uint32_t g) {
+    if (g == 0) return seed;
+    uint64_t z = seed + (uint64_t)g * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
 }
 
 // A target histogram's CDF over the bins and its mean / entropy / N+ frequency (the overflow bin counts at
@@ -203,7 +239,7 @@ constexpr int kBtpeRow = 16;  // refdraws::kBtpeRow
 struct Chunk {
     uint64_t first;  // local index of the first replicate
     uint32_t n;
-    hipEvent_t ev[3];
+    std::vector<hipEvent_t> ev;  // per growth phase (one in an ordinary run): start, stepper done, passes done
     // replicate rotation (bin store; 0 = off): partition size and the counters it starts from
     uint32_t rot_n_pad = 0;
     std::vector<ecdna::RotPart> rot_init;
@@ -262,6 +298,22 @@ struct ecdna_ssa_ctx {
     uint64_t* d_snap_sample_hist = nullptr;
     double* d_snap_target_cdf = nullptr;
     double* d_snap_target_scalars = nullptr;
+    // serial passaging (ecdna_ssa_passages_t; 0 = an ordinary run): G growth phases per chunk, each started from the
+    // founders the previous phase's sample left (one chunk's worth, written by ssa_passage). Every phase's outputs
+    // are sized G x run; the ordinary buffers receive phase G - 1's at the end of a launch.
+    uint32_t n_passages = 0;
+    uint32_t passage_m = 0;
+    uint64_t founder_stride = 0;
+    uint16_t* d_founder_rows = nullptr;     // [chunk_reps][founder_stride]
+    uint2* d_founder_counts = nullptr;      // [chunk_reps] {n-, n+}
+    ecdna_rep_summary_t* d_pas_summ = nullptr;      // [G][n]
+    uint64_t* d_pas_hist = nullptr;                 // [G][n_sets][bins]
+    ecdna_totals_t* d_pas_tot = nullptr;            // [G][n_sets]
+    ecdna_rep_stats_t* d_pas_stats = nullptr;       // [G][n]
+    ecdna_rep_stats_t* d_pas_sample_stats = nullptr;// [G][n]
+    uint64_t* d_pas_sample_hist = nullptr;          // [G][n_sets][bins]
+    double* d_pas_target_cdf = nullptr;             // [G][bins], or nullptr: no target
+    std::vector<double> pas_target_scalars;         // [G][3]: the targets' mean, entropy, N+ frequency
     // device buffers
     float4* d_rates = nullptr;
     uint16_t* d_init = nullptr;
@@ -292,7 +344,9 @@ struct ecdna_ssa_ctx {
 namespace {
 
 // the flags the kernels see: the caller's, plus the internal snapshot bit that selects the runtime-flags instances
-uint32_t kernel_flags(const ecdna_ssa_params_t& p) { return p.flags | (p.n_snapshots ? ecdna::kFlagSnapshotsRt : 0u); }
+uint32_t kernel_flags(const ecdna_ssa_params_t& p, bool passages) {
+    return p.flags | (p.n_snapshots ? ecdna::kFlagSnapshotsRt : 0u) | (passages ? ecdna::kFlagPassageRt : 0u);
+}
 
 int pick_device(int dev) {
     int n = 0;
@@ -352,6 +406,15 @@ void free_ctx(ecdna_ssa_ctx* c) {
     (void)hipFree(c->d_snap_sample_hist);
     (void)hipFree(c->d_snap_target_cdf);
     (void)hipFree(c->d_snap_target_scalars);
+    (void)hipFree(c->d_founder_rows);
+    (void)hipFree(c->d_founder_counts);
+    (void)hipFree(c->d_pas_summ);
+    (void)hipFree(c->d_pas_hist);
+    (void)hipFree(c->d_pas_tot);
+    (void)hipFree(c->d_pas_stats);
+    (void)hipFree(c->d_pas_sample_stats);
+    (void)hipFree(c->d_pas_sample_hist);
+    (void)hipFree(c->d_pas_target_cdf);
     (void)hipFree(c->d_rows);
     (void)hipFree(c->d_bags);
     (void)hipFree(c->d_summ);
@@ -432,9 +495,14 @@ int ecdna_ssa_ctx_create(const ecdna_ssa_params_t* p, ecdna_ssa_ctx** out) {
 }
 
 int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, ecdna_ssa_ctx** out) {
+    return ecdna_ssa_ctx_create_passages(p, ext, nullptr, out);
+}
+
+int ecdna_ssa_ctx_create_passages(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                                  const ecdna_ssa_passages_t* pas, ecdna_ssa_ctx** out) {
     if (!out) return fail(ECDNA_E_INVALID, "out is NULL");
     *out = nullptr;
-    int rc = validate(p, ext);
+    int rc = validate(p, ext, pas);
     if (rc) return rc;
     rc = pick_device(p->device);
     if (rc) return rc;
@@ -442,6 +510,11 @@ int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t*
     ecdna_ssa_ctx* c = new ecdna_ssa_ctx();
     c->p = *p;
     c->device = p->device;
+    if (pas) {
+        c->n_passages = pas->n_passages;
+        c->passage_m = pas->passage_cells;
+        c->founder_stride = round_up(pas->passage_cells, 64);
+    }
     // own copies of host inputs
     c->rates.assign(p->rates, p->rates + p->n_param_sets);
     uint64_t n_init = p->init_set_offsets ? p->init_set_offsets[p->n_param_sets] : p->init_nplus;
@@ -525,6 +598,31 @@ int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t*
         CTX_TRY(hipMalloc(&c->d_sample_stats, std::max<uint64_t>(n, 1) * sizeof(ecdna_rep_stats_t)));
         CTX_TRY(hipMalloc(&c->d_sample_hist, nb * sizeof(uint64_t)));
     }
+    if (pas) {  // every phase's outputs, sized G x run; the last phase's are copied into the ordinary buffers
+        const uint64_t G = pas->n_passages, n1 = std::max<uint64_t>(n, 1);
+        const uint32_t bins = p->hist_bins;
+        CTX_TRY(hipMalloc(&c->d_sample_stats, n1 * sizeof(ecdna_rep_stats_t)));
+        CTX_TRY(hipMalloc(&c->d_sample_hist, nb * sizeof(uint64_t)));
+        CTX_TRY(hipMalloc(&c->d_pas_summ, G * n1 * sizeof(ecdna_rep_summary_t)));
+        CTX_TRY(hipMalloc(&c->d_pas_stats, G * n1 * sizeof(ecdna_rep_stats_t)));
+        CTX_TRY(hipMalloc(&c->d_pas_sample_stats, G * n1 * sizeof(ecdna_rep_stats_t)));
+        CTX_TRY(hipMalloc(&c->d_pas_hist, G * nb * sizeof(uint64_t)));
+        CTX_TRY(hipMalloc(&c->d_pas_sample_hist, G * nb * sizeof(uint64_t)));
+        CTX_TRY(hipMalloc(&c->d_pas_tot, G * p->n_param_sets * sizeof(ecdna_totals_t)));
+        if (pas->passage_target_hists) {  // phase g's own target
+            std::vector<double> cdf(G * bins);
+            c->pas_target_scalars.assign(G * 3, 0.0);
+            for (uint64_t g = 0; g < G; ++g) {
+                const uint64_t* t = pas->passage_target_hists + g * bins;
+                double tot = 0.0;
+                for (uint32_t b = 0; b < bins; ++b) tot += (double)t[b];
+                double* sc = c->pas_target_scalars.data() + 3 * g;
+                target_summary(t, bins, tot, cdf.data() + g * bins, sc, sc + 1, sc + 2);
+            }
+            CTX_TRY(hipMalloc(&c->d_pas_target_cdf, cdf.size() * sizeof(double)));
+            CTX_TRY(hipMemcpy(c->d_pas_target_cdf, cdf.data(), cdf.size() * sizeof(double), hipMemcpyHostToDevice));
+        }
+    }
     // per-snapshot statistics: sized by the run (the snapshot rows they are computed from may be one chunk's, below)
     c->snap_stats = ext && ext->snapshot_stats;
     if (c->snap_stats) {
@@ -587,7 +685,10 @@ int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t*
     // rows of out_stride cells per replicate of the chunk, so a large run chunks instead of failing)
     c->snap_rows_local = c->snap_stats && !c->d_snap_rows;
     const uint64_t snap_row_bytes = c->snap_rows_local ? p->n_snapshots * c->out_stride * sizeof(uint16_t) : 0u;
-    const uint64_t row_bytes = c->row_stride * sizeof(uint16_t) + bag_bytes + rot_bytes + snap_row_bytes;
+    // (a passage run: the chunk's founders, one row of passage_cells and {n-, n+} per replicate)
+    const uint64_t founder_bytes = c->n_passages ? c->founder_stride * sizeof(uint16_t) + sizeof(uint2) : 0u;
+    const uint64_t row_bytes =
+        c->row_stride * sizeof(uint16_t) + bag_bytes + rot_bytes + snap_row_bytes + founder_bytes;
     size_t free_b = 0, total_b = 0;
     CTX_TRY(hipMemGetInfo(&free_b, &total_b));
     uint64_t budget = (uint64_t)((double)free_b * 0.85);
@@ -601,6 +702,10 @@ int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t*
     CTX_TRY(hipMalloc(&c->d_rows, c->chunk_reps * c->row_stride * sizeof(uint16_t)));
     if (c->bin_k) CTX_TRY(hipMalloc(&c->d_bags, c->chunk_reps * bag_bytes));
     if (c->snap_rows_local) CTX_TRY(hipMalloc(&c->d_snap_rows, c->chunk_reps * snap_row_bytes));
+    if (c->n_passages) {
+        CTX_TRY(hipMalloc(&c->d_founder_rows, c->chunk_reps * c->founder_stride * sizeof(uint16_t)));
+        CTX_TRY(hipMalloc(&c->d_founder_counts, c->chunk_reps * sizeof(uint2)));
+    }
 
     const uint64_t n_chunks = n ? (n + c->chunk_reps - 1) / c->chunk_reps : 0;
     CTX_TRY(hipMalloc(&c->d_heads, std::max<uint64_t>(n_chunks, 1) * sizeof(uint32_t)));
@@ -609,6 +714,7 @@ int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t*
         ch.first = k * c->chunk_reps;
         ch.n = (uint32_t)std::min<uint64_t>(c->chunk_reps, n - ch.first);
         c->chunks.push_back(ch);
+        c->chunks.back().ev.assign(3u * std::max<uint32_t>(c->n_passages, 1u), nullptr);
         for (auto& e : c->chunks.back().ev) CTX_TRY(hipEventCreate(&e));
     }
 
@@ -657,7 +763,7 @@ int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t*
         // ECDNA_SSA_SCHED = 0 default, 1 max-ILP, 2 auto, 3 the 128-VGPR build (K = 64 / u16; else 0).
         uint64_t max_chunk = 0;
         for (const auto& ch : c->chunks) max_chunk = std::max<uint64_t>(max_chunk, ch.n);
-        const uint32_t kflags = kernel_flags(*p);
+        const uint32_t kflags = kernel_flags(*p, c->n_passages != 0);
         const uint64_t sched = env_u64("ECDNA_SSA_SCHED", 2);
         // (auto only without f32 time and the event hash: that variant spills 12 B at 128 VGPRs)
         const bool k64u16 = c->bin_k == 64 && !c->bin_c32;
@@ -691,7 +797,8 @@ int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t*
             (int)c->stepper_block, 0));
     } else {
         CTX_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, ecdna::stepper_kernel(p->process, p->segregation, c->window), ecdna::kStepperBlock, 0));
+            &per_cu, ecdna::stepper_kernel(p->process, p->segregation, c->window, kernel_flags(*p, c->n_passages != 0)),
+            ecdna::kStepperBlock, 0));
         // Memory-level parallelism of the random row accesses saturates HBM at about 3 resident 256-lane
         // blocks per CU (C3 sweep, DESIGN.md §8: 1/2/3/4/7 blocks -> 617/372/329/336/349 ms); fewer
         // lanes also mean more replicates per lane and a shorter drain once the work queue is empty.
@@ -800,12 +907,25 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
         HIP_TRY(hipMemsetAsync(c->d_heads, 0, c->chunks.size() * sizeof(uint32_t), st));
     if (c->d_snap_meta)
         HIP_TRY(hipMemsetAsync(c->d_snap_meta, 0, p.n_replicates * p.n_snapshots * sizeof(ecdna_snapshot_t), st));
+    // a passage run: G growth phases per chunk, phase g into its own slice of the per-phase outputs
+    const uint32_t G = std::max<uint32_t>(c->n_passages, 1u);
+    const uint64_t n_run = std::max<uint64_t>(p.n_replicates, 1);
+    if (c->n_passages) {
+        HIP_TRY(hipMemsetAsync(c->d_pas_hist, 0, G * nb * sizeof(uint64_t), st));
+        HIP_TRY(hipMemsetAsync(c->d_pas_sample_hist, 0, G * nb * sizeof(uint64_t), st));
+        HIP_TRY(hipMemsetAsync(c->d_pas_tot, 0, (uint64_t)G * p.n_param_sets * sizeof(ecdna_totals_t), st));
+    }
 
     for (size_t k = 0; k < c->chunks.size(); ++k) {
+      for (uint32_t g = 0; g < G; ++g) {
         Chunk& ch = c->chunks[k];
+        hipEvent_t* const ev = ch.ev.data() + 3u * g;
+        const bool pas = c->n_passages != 0;
+        // the chunk's work counter starts every phase at zero (the rotation state is reset below, per launch)
+        if (g > 0) HIP_TRY(hipMemsetAsync(c->d_heads + k, 0, sizeof(uint32_t), st));
         ecdna::StepperArgs a{};
         a.rows = c->d_rows;
-        a.summaries = c->d_summ + ch.first;
+        a.summaries = (pas ? c->d_pas_summ + g * n_run : c->d_summ) + ch.first;
         a.head = c->d_heads + k;
         a.order = c->d_order ? c->d_order + ch.first : nullptr;
         a.rates = c->d_rates;
@@ -813,7 +933,12 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
         a.init_offsets = c->d_init_off;
         a.init_nminus_set = c->d_init_nm;
         a.row_stride = c->row_stride;
-        a.seed = p.seed;
+        a.seed = passage_seed(p.seed, g);  // (an ordinary run: the seed)
+        if (g > 0) {  // started from the founders the previous phase's sample left
+            a.founder_rows = c->d_founder_rows;
+            a.founder_counts = c->d_founder_counts;
+            a.founder_stride = c->founder_stride;
+        }
         const uint64_t stride = p.replicate_stride ? p.replicate_stride : 1u;
         a.rid0 = p.first_replicate + ch.first * stride;
         a.rid_stride = stride;
@@ -826,7 +951,7 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
         a.init_nplus = p.init_nplus;
         a.max_iter = (uint32_t)p.max_iter;
         a.cell_cap = p.cell_cap;
-        a.flags = kernel_flags(p);  // (with the internal snapshot bit: it selects the kernel instance)
+        a.flags = kernel_flags(p, c->n_passages != 0);  // (with the internal snapshot bit: it selects the kernel instance)
         // (n- + n+) * 2 >= max_cells  <=>  n- + n+ >= ceil(max_cells / 2)
         a.stop_cells = (p.process == ECDNA_BIRTH_DEATH && (p.flags & ECDNA_FLAG_BD_CAP_COMPAT))
                            ? p.max_cells / 2 + (p.max_cells & 1)
@@ -861,20 +986,20 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
         a.ref_key = c->d_ref_key;
         a.ref_btpe = c->d_ref_btpe;
         a.rng_words = c->d_rng_words ? c->d_rng_words + ch.first : nullptr;
-        HIP_TRY(hipEventRecord(ch.ev[0], st));
+        HIP_TRY(hipEventRecord(ev[0], st));
         if (c->refdraws)
             HIP_TRY(ecdna::launch_refdraws(a, p.process, p.segregation, blocks, st));
         else if (c->bin_k)
             HIP_TRY(ecdna::launch_bin_stepper(a, p.process, p.segregation, c->bin_k, c->bin_c32, c->bin_ilp, blocks, st));
         else
             HIP_TRY(ecdna::launch_stepper(a, p.process, p.segregation, c->window, blocks, st));
-        HIP_TRY(hipEventRecord(ch.ev[1], st));
+        HIP_TRY(hipEventRecord(ev[1], st));
 
         ecdna::HistArgs hsa{};
         hsa.rows = c->d_rows;
-        hsa.summaries = c->d_summ + ch.first;
-        hsa.hist = c->d_hist;
-        hsa.totals = reinterpret_cast<unsigned long long*>(c->d_tot);
+        hsa.summaries = a.summaries;
+        hsa.hist = pas ? c->d_pas_hist + g * nb : c->d_hist;
+        hsa.totals = reinterpret_cast<unsigned long long*>(pas ? c->d_pas_tot + (uint64_t)g * p.n_param_sets : c->d_tot);
         hsa.row_stride = c->row_stride;
         hsa.rid0 = p.first_replicate + ch.first * stride;
         hsa.rid_stride = stride;
@@ -899,6 +1024,16 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
         hsa.target_entropy = c->target_entropy;
         hsa.target_freq = c->target_freq;
         hsa.has_target = c->has_target ? 1u : 0u;
+        if (pas) {
+            hsa.stats = c->d_pas_stats + g * n_run + ch.first;
+            if (c->d_pas_target_cdf) {  // phase g's own target (else params.stats_target_hist for all, as above)
+                hsa.target_cdf = c->d_pas_target_cdf + (uint64_t)g * p.hist_bins;
+                hsa.target_mean = c->pas_target_scalars[3 * g];
+                hsa.target_entropy = c->pas_target_scalars[3 * g + 1];
+                hsa.target_freq = c->pas_target_scalars[3 * g + 2];
+                hsa.has_target = 1u;
+            }
+        }
         hsa.bags = c->d_bags;
         hsa.bag_k = c->bin_k;
         hsa.bag_c32 = (uint32_t)c->bin_c32;
@@ -933,6 +1068,38 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
             sa.reps_per_block = std::max<uint32_t>(sw, (ch.n + hist_blocks_max - 1) / hist_blocks_max);
             HIP_TRY(ecdna::launch_subsample(sa, (ch.n + sa.reps_per_block - 1) / sa.reps_per_block, st));
         }
+        if (pas) {  // the phase's measurement, and (but for the last phase) the founders of the next
+            ecdna::PassageArgs pa{};
+            pa.rows = hsa.rows;
+            pa.summaries = hsa.summaries;
+            pa.stats = c->d_pas_sample_stats + g * n_run + ch.first;
+            pa.sample_hist = c->d_pas_sample_hist + g * nb;
+            pa.founder_rows = g + 1u < G ? c->d_founder_rows : nullptr;
+            pa.founder_counts = c->d_founder_counts;
+            pa.founder_stride = c->founder_stride;
+            pa.row_stride = hsa.row_stride;
+            pa.rid0 = hsa.rid0;
+            pa.rid_stride = hsa.rid_stride;
+            pa.reps_per_set = hsa.reps_per_set;
+            pa.seed = a.seed;
+            pa.n = ch.n;
+            pa.bins = p.hist_bins;
+            pa.m = c->passage_m;
+            pa.table_slots = ecdna::subsample_table_slots(c->passage_m);
+            pa.sort_slots = ecdna::passage_sort_slots(c->passage_m);
+            pa.has_target = hsa.has_target;
+            pa.target_cdf = hsa.target_cdf;
+            pa.target_mean = hsa.target_mean;
+            pa.target_entropy = hsa.target_entropy;
+            pa.target_freq = hsa.target_freq;
+            pa.bags = hsa.bags;
+            pa.bag_k = hsa.bag_k;
+            pa.bag_c32 = hsa.bag_c32;
+            // one wave per replicate: a workgroup's share as the subsampling pass's
+            const uint32_t pw = ecdna::passage_waves(pa.bins, pa.bag_k, pa.table_slots, pa.sort_slots, nullptr);
+            pa.reps_per_block = std::max<uint32_t>(pw, (ch.n + hist_blocks_max - 1) / hist_blocks_max);
+            HIP_TRY(ecdna::launch_passage(pa, (ch.n + pa.reps_per_block - 1) / pa.reps_per_block, st));
+        }
         if (c->snap_stats) {  // the statistics of the chunk's snapshots, from the rows the stepper just saved
             ecdna::SnapStatsArgs ta{};
             ta.snap_meta = a.snap_meta;
@@ -959,7 +1126,25 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
             ta.reps_per_block = std::max<uint32_t>(tw, (ch.n + hist_blocks_max - 1) / hist_blocks_max);
             HIP_TRY(ecdna::launch_snapstats(ta, (ch.n + ta.reps_per_block - 1) / ta.reps_per_block, st));
         }
-        HIP_TRY(hipEventRecord(ch.ev[2], st));
+        HIP_TRY(hipEventRecord(ev[2], st));
+      }  // (growth phases)
+    }
+    if (c->n_passages && p.n_replicates) {  // the ordinary outputs are the last phase's
+        const uint64_t gl = G - 1u;
+        HIP_TRY(hipMemcpyAsync(c->d_summ, c->d_pas_summ + gl * n_run, p.n_replicates * sizeof(ecdna_rep_summary_t),
+                               hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->d_stats, c->d_pas_stats + gl * n_run, p.n_replicates * sizeof(ecdna_rep_stats_t),
+                               hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->d_sample_stats, c->d_pas_sample_stats + gl * n_run,
+                               p.n_replicates * sizeof(ecdna_rep_stats_t), hipMemcpyDeviceToDevice, st));
+    }
+    if (c->n_passages) {
+        const uint64_t gl = G - 1u;
+        HIP_TRY(hipMemcpyAsync(c->d_hist, c->d_pas_hist + gl * nb, nb * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->d_sample_hist, c->d_pas_sample_hist + gl * nb, nb * sizeof(uint64_t),
+                               hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->d_tot, c->d_pas_tot + gl * p.n_param_sets, p.n_param_sets * sizeof(ecdna_totals_t),
+                               hipMemcpyDeviceToDevice, st));
     }
     c->last_stream = st;
     c->launched = true;
@@ -973,11 +1158,13 @@ int ecdna_ssa_ctx_sync(ecdna_ssa_ctx* c, float* ssa_ms, float* hist_ms) {
     HIP_TRY(hipStreamSynchronize(c->last_stream));
     float s = 0.f, h = 0.f;
     for (auto& ch : c->chunks) {
-        float a = 0.f, b = 0.f;
-        HIP_TRY(hipEventElapsedTime(&a, ch.ev[0], ch.ev[1]));
-        HIP_TRY(hipEventElapsedTime(&b, ch.ev[1], ch.ev[2]));
-        s += a;
-        h += b;
+        for (size_t e = 0; e + 2 < ch.ev.size(); e += 3) {  // per growth phase (one in an ordinary run)
+            float a = 0.f, b = 0.f;
+            HIP_TRY(hipEventElapsedTime(&a, ch.ev[e], ch.ev[e + 1]));
+            HIP_TRY(hipEventElapsedTime(&b, ch.ev[e + 1], ch.ev[e + 2]));
+            s += a;
+            h += b;
+        }
     }
     if (ssa_ms) *ssa_ms = s;
     if (hist_ms) *hist_ms = h;
@@ -1018,14 +1205,14 @@ int ecdna_ssa_ctx_instance(const ecdna_ssa_ctx* c, ecdna_ssa_instance_t* out) {
         r.paired = c->bin_ilp == 3 ? 1 : 0;
         r.bin_kmax = c->bin_k;
         r.bin_c32 = (uint32_t)c->bin_c32;
-        r.runtime_flags = (kernel_flags(p) & ecdna::kRuntimeFlagMask) ? 1 : 0;
-        fn = ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kernel_flags(p), c->bin_ilp);
+        r.runtime_flags = (kernel_flags(p, c->n_passages != 0) & ecdna::kRuntimeFlagMask) ? 1 : 0;
+        fn = ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kernel_flags(p, c->n_passages != 0), c->bin_ilp);
     } else {
         r.kernel = ECDNA_KERNEL_ROWS;
         r.schedule = -1;
         r.window = (uint32_t)c->window;
         r.runtime_flags = 1;
-        fn = ecdna::stepper_kernel(p.process, p.segregation, c->window);
+        fn = ecdna::stepper_kernel(p.process, p.segregation, c->window, kernel_flags(p, c->n_passages != 0));
     }
     for (const auto& ch : c->chunks) {
         r.rotation += ch.rot_n_pad ? 1 : 0;
@@ -1171,6 +1358,31 @@ int ecdna_ssa_ctx_download_snapshot_stats(ecdna_ssa_ctx* c, ecdna_rep_stats_t* o
         HIP_TRY(hipMemcpy(out_sample_stats, c->d_snap_sample_stats, ns, hipMemcpyDeviceToHost));
     if (out_hist) HIP_TRY(hipMemcpy(out_hist, c->d_snap_hist, hb, hipMemcpyDeviceToHost));
     if (out_sample_hist) HIP_TRY(hipMemcpy(out_sample_hist, c->d_snap_sample_hist, hb, hipMemcpyDeviceToHost));
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_download_passages(ecdna_ssa_ctx* c, ecdna_rep_summary_t* out_summaries, ecdna_totals_t* out_totals,
+                                    ecdna_rep_stats_t* out_stats, ecdna_rep_stats_t* out_sample_stats,
+                                    uint64_t* out_hist, uint64_t* out_sample_hist) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!c->n_passages) return fail(ECDNA_E_STATE, "per-phase results need ecdna_ssa_ctx_create_passages");
+    if (!c->launched) return fail(ECDNA_E_STATE, "download before launch");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t G = c->n_passages, n = p.n_replicates;
+    const uint64_t hb = G * p.n_param_sets * p.hist_bins * sizeof(uint64_t);
+    if (out_summaries && n)
+        HIP_TRY(hipMemcpy(out_summaries, c->d_pas_summ, G * n * sizeof(ecdna_rep_summary_t), hipMemcpyDeviceToHost));
+    if (out_totals)
+        HIP_TRY(hipMemcpy(out_totals, c->d_pas_tot, G * p.n_param_sets * sizeof(ecdna_totals_t), hipMemcpyDeviceToHost));
+    if (out_stats && n)
+        HIP_TRY(hipMemcpy(out_stats, c->d_pas_stats, G * n * sizeof(ecdna_rep_stats_t), hipMemcpyDeviceToHost));
+    if (out_sample_stats && n)
+        HIP_TRY(hipMemcpy(out_sample_stats, c->d_pas_sample_stats, G * n * sizeof(ecdna_rep_stats_t),
+                          hipMemcpyDeviceToHost));
+    if (out_hist) HIP_TRY(hipMemcpy(out_hist, c->d_pas_hist, hb, hipMemcpyDeviceToHost));
+    if (out_sample_hist) HIP_TRY(hipMemcpy(out_sample_hist, c->d_pas_sample_hist, hb, hipMemcpyDeviceToHost));
     return ECDNA_OK;
 }
 

@@ -47,7 +47,9 @@ __device__ __forceinline__ uint32_t gload_u16(const uint16_t* p) {
 constexpr uint32_t kWin = 32;
 constexpr uint32_t kFlush = 16;
 
-template <bool BD, int SEG, bool WIN>
+// FND: the instances of a passage run (kFlagPassageRt), whose replicate start reads the founders of a growth phase
+// g > 0; the others (the bench's) hold none of that code.
+template <bool BD, int SEG, bool WIN, bool FND = false>
 __global__ void __launch_bounds__(kStepperBlock) ssa_stepper(const StepperArgs a) {
     __shared__ uint16_t win[WIN ? kWin + 1 : 1][kStepperBlock];  // + 1 spare row
     __shared__ float2 logtab[ECDNA_LOGTAB_N];
@@ -163,6 +165,14 @@ __global__ void __launch_bounds__(kStepperBlock) ssa_stepper(const StepperArgs a
                 src = a.init_copies + a.init_offsets[set];
                 cnt = a.init_offsets[set + 1] - a.init_offsets[set];
             }
+            uint32_t founder_nm = 0;
+            const bool founders = FND && a.founder_rows != nullptr;
+            if (founders) {  // a passage run's phase g > 0: the founders the previous phase's sample left
+                const uint2 fc = a.founder_counts[i];
+                src = a.founder_rows + (uint64_t)i * a.founder_stride;
+                cnt = min(fc.y, min(a.cell_cap, (uint32_t)a.founder_stride));
+                founder_nm = fc.x;
+            }
             wb = (WIN && cnt) ? ((cnt - 1) / kFlush) * kFlush : 0;
             if (WIN) {
                 for (uint32_t j = 0; j < wb; ++j) row[j] = src[j];
@@ -172,6 +182,7 @@ __global__ void __launch_bounds__(kStepperBlock) ssa_stepper(const StepperArgs a
             }
             np = cnt;
             nm = (uint32_t)(a.init_nminus_set ? a.init_nminus_set[set] : a.init_nminus);
+            if (founders) nm = founder_nm;
             tail_ok = false;
             if (WIN && cnt) tail = src[cnt - 1];
             t = 0.0;
@@ -1038,20 +1049,42 @@ __global__ void __launch_bounds__(BLK, SCH == 2 ? 4 : 1) ssa_stepper_bins(const 
                     src = ra->init_copies + ra->init_offsets[set];
                     cnt = ra->init_offsets[set + 1] - ra->init_offsets[set];
                 }
+                // a passage run's phase g > 0 (runtime-flags instances only): the founders the previous phase's sample
+                // left. No host validation has seen them, so the large-k row is guarded here: more founders above
+                // bin_kmax than big_cap stop the replicate at its start
+                bool founders = false;
+                uint32_t founder_nm = 0;
+                if (TF != 0 && (ra->flags & kFlagPassageRt) && ra->founder_rows) {
+                    const uint2 fc = ra->founder_counts[i];
+                    src = ra->founder_rows + (uint64_t)i * ra->founder_stride;
+                    cnt = min(fc.y, min(ra->cell_cap, (uint32_t)ra->founder_stride));
+                    founder_nm = fc.x;
+                    founders = true;
+                }
                 bins_zero();
                 ns = 0;
                 nb = 0;
+                bool big_over = false;
 #pragma unroll 1
                 for (uint32_t j = 0; j < cnt; ++j) {
                     const uint32_t kk = src[j];
                     if (kk <= K) {
                         bin_add(kk, 1u);
                         ++ns;
+                    } else if (TF != 0 && founders && nb >= ra->big_cap) {
+                        big_over = true;  // (never past the row's capacity)
                     } else {
                         row[nb++] = (uint16_t)kk;
                     }
                 }
                 nm = (uint32_t)(ra->init_nminus_set ? ra->init_nminus_set[set] : ra->init_nminus);
+                if (TF != 0 && founders) nm = founder_nm;
+                if (TF != 0 && big_over) {  // reported with no cells: the founders cannot be held
+                    bins_zero();
+                    ns = 0;
+                    nb = 0;
+                    nm = 0;
+                }
                 t = 0.0;
                 t32 = 0.f;
                 e = n_dm = n_un = 0;
@@ -1064,6 +1097,7 @@ __global__ void __launch_bounds__(BLK, SCH == 2 ? 4 : 1) ssa_stepper_bins(const 
                 // stops at this iteration's stop test (a0 = 0 there; the reason follows err), so that every lane that
                 // reaches the event path without PAIR holds a replicate and the path needs no skip branch
                 if (ns + nb == 0 && nm == 0) err = ECDNA_REP_ERR_EMPTY;
+                if (TF != 0 && big_over) err = ECDNA_REP_ERR_CELL_CAP;  // (a0 = 0 stops it as it stops the empty start)
             }
             }  // (a replicate claimed)
         }
@@ -1556,13 +1590,16 @@ __global__ void __launch_bounds__(BLK, SCH == 2 ? 4 : 1) ssa_stepper_bins(const 
 // ---------------------------------------------------------------- launch
 
 #ifndef ECDNA_ILP_BUILD
-#define ECDNA_STEPPER_TABLE(BD, WIN)                                                                        \
-    {(const void*)ssa_stepper<BD, 0, WIN>, (const void*)ssa_stepper<BD, 1, WIN>,                             \
-     (const void*)ssa_stepper<BD, 2, WIN>, (const void*)ssa_stepper<BD, 3, WIN>}
+#define ECDNA_STEPPER_TABLE(BD, WIN, FND)                                                                        \
+    {(const void*)ssa_stepper<BD, 0, WIN, FND>, (const void*)ssa_stepper<BD, 1, WIN, FND>,                   \
+     (const void*)ssa_stepper<BD, 2, WIN, FND>, (const void*)ssa_stepper<BD, 3, WIN, FND>}
 
-static const void* const kStepperTable[2][2][4] = {
-    {ECDNA_STEPPER_TABLE(false, false), ECDNA_STEPPER_TABLE(true, false)},
-    {ECDNA_STEPPER_TABLE(false, true), ECDNA_STEPPER_TABLE(true, true)}};
+// [passage run][window][birth_death][segregation]
+static const void* const kStepperTable[2][2][2][4] = {
+    {{ECDNA_STEPPER_TABLE(false, false, false), ECDNA_STEPPER_TABLE(true, false, false)},
+     {ECDNA_STEPPER_TABLE(false, true, false), ECDNA_STEPPER_TABLE(true, true, false)}},
+    {{ECDNA_STEPPER_TABLE(false, false, true), ECDNA_STEPPER_TABLE(true, false, true)},
+     {ECDNA_STEPPER_TABLE(false, true, true), ECDNA_STEPPER_TABLE(true, true, true)}}};
 #endif
 
 // bin-store variants: [birth_death][segregation][K = 32 | 64 | 256][u16 | u32 counters]; the 256-bin
@@ -1625,8 +1662,8 @@ const void* bin_stepper_kernel_pair(int segregation, uint32_t bin_k, int c32, ui
     return nullptr;
 }
 #else
-const void* stepper_kernel(int birth_death, int segregation, int window) {
-    return kStepperTable[window ? 1 : 0][birth_death ? 1 : 0][segregation & 3];
+const void* stepper_kernel(int birth_death, int segregation, int window, uint32_t flags) {
+    return kStepperTable[(flags & kFlagPassageRt) ? 1 : 0][window ? 1 : 0][birth_death ? 1 : 0][segregation & 3];
 }
 
 const void* bin_stepper_kernel(int birth_death, int segregation, uint32_t bin_k, int c32, uint32_t flags, int ilp) {
@@ -1645,8 +1682,8 @@ hipError_t launch_stepper(const StepperArgs& a, int birth_death, int segregation
                           hipStream_t stream) {
     StepperArgs copy = a;
     void* args[] = {&copy};
-    return hipLaunchKernel(stepper_kernel(birth_death, segregation, window), dim3(blocks), dim3(kStepperBlock), args,
-                           0, stream);
+    return hipLaunchKernel(stepper_kernel(birth_death, segregation, window, a.flags), dim3(blocks),
+                           dim3(kStepperBlock), args, 0, stream);
 }
 
 hipError_t launch_bin_stepper(const StepperArgs& a, int birth_death, int segregation, uint32_t bin_k, int c32, int ilp,

@@ -1,6 +1,6 @@
 // ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by the device
 // code (steppers: ssa_kernels.hip, ssa_refdraws.hip; end-of-run passes: ssa_hist.hip,
-// ssa_subsample.hip, ssa_snapstats.hip) and ssa_api.cpp (the C ABI).
+// ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip) and ssa_api.cpp (the C ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -78,6 +78,14 @@ struct StepperArgs {
     const uint32_t* ref_key;
     const double* ref_btpe;
     uint64_t* rng_words;            // [n] chunk-offset: ChaCha8 words each replicate's stream handed out (or nullptr)
+    // serial passaging (ecdna_ssa_passages_t; ssa_passage.hip): a growth phase g > 0 starts replicate i (chunk-local)
+    // from the founders the previous phase's sample left, founder_counts[i] = {n-, n+} and the n+ copy numbers
+    // founder_rows[i][0 .. n+) in ascending order, instead of the run's initial distribution. nullptr / 0: phase 0 and
+    // every other run. Only the instances kFlagPassageRt selects read them: the bin stepper's runtime-flags instances
+    // and the row stepper's FND = true instances.
+    const uint16_t* founder_rows;   // [n][founder_stride]
+    const uint2* founder_counts;    // [n]
+    uint64_t founder_stride;        // cells per founder row (passage_cells rounded up to 64)
 };
 
 // Histogram / totals pass over one chunk.
@@ -156,6 +164,38 @@ struct SnapStatsArgs {
     uint32_t table_slots;                 // per-wave table of drawn positions: subsample_table_slots(m), 0 when m == 0
 };
 
+// The passage pass over one chunk (ssa_passage.hip; ecdna_ssa_passages_t): per replicate, the sample of m cells of the
+// phase's final state by subsample mapping v1 (statistics and per-set histogram exactly as SubsampleArgs' pass), and,
+// unless this is the last phase, the sample's cells as the next phase's founders.
+struct PassageArgs {
+    const uint16_t* rows;
+    const ecdna_rep_summary_t* summaries; // chunk-offset
+    ecdna_rep_stats_t* stats;             // chunk-offset: the samples' statistics
+    uint64_t* sample_hist;                // [n_sets][bins]
+    uint16_t* founder_rows;               // [n][founder_stride], chunk-local: the sample's N+ copy numbers, ascending;
+                                          // nullptr: no founders (the last phase)
+    uint2* founder_counts;                // [n], chunk-local: {n-, n+} of the sample
+    uint64_t founder_stride;              // >= m
+    uint64_t row_stride;
+    uint64_t rid0;
+    uint64_t rid_stride;                  // >= 1
+    uint64_t reps_per_set;
+    uint64_t seed;                        // the phase's key seed_g
+    uint32_t n;
+    uint32_t bins;
+    uint32_t reps_per_block;
+    uint32_t m;                           // sample size (cells), 1 .. kMaxSubsampleCells
+    uint32_t table_slots;                 // per-wave table of drawn positions: subsample_table_slots(m)
+    uint32_t sort_slots;                  // per-wave founder array (u16): passage_sort_slots(m)
+    uint32_t has_target;
+    const double* target_cdf;
+    double target_mean, target_entropy, target_freq;
+    // bin store: per-replicate counters [n][bag_k] (u16, or u32 when bag_c32); nullptr = rows only
+    const void* bags;
+    uint32_t bag_k;
+    uint32_t bag_c32;
+};
+
 constexpr uint32_t kMaxSubsampleCells = 4096;  // LDS: 8 B of table per sampled cell and wave (<= 32 KiB)
 constexpr int kStepperBlock = 256;
 constexpr int kBinWideBlock = 64;  // bin store with 256 bins
@@ -166,11 +206,17 @@ constexpr uint32_t kMaxSnapshots = 64;
 // stepper's runtime-flags instances (TF = 1); the TF = 0 instances (the bench's) compile snapshots, f32 time and the
 // hash out, which frees the scalar registers the snapshot test held across the event loop.
 constexpr uint32_t kFlagSnapshotsRt = 0x80000000u;
-constexpr uint32_t kRuntimeFlagMask = ECDNA_FLAG_TIME_F32 | ECDNA_FLAG_EVENT_HASH | kFlagSnapshotsRt;
+// Internal flag bit: the run is a passage run (ecdna_ssa_passages_t), set for every phase from phase 0 on. It selects the
+// bin stepper's runtime-flags instances too: only they hold the start from founders and its big_cap guard.
+constexpr uint32_t kFlagPassageRt = 0x40000000u;
+constexpr uint32_t kRuntimeFlagMask =
+    ECDNA_FLAG_TIME_F32 | ECDNA_FLAG_EVENT_HASH | kFlagSnapshotsRt | kFlagPassageRt;
+constexpr uint32_t kMaxPassages = 16;
 
 // Kernel handle for occupancy queries and the launch itself.
-// window: 1 = LDS tail window variant (default), 0 = rows straight in HBM (A/B reference)
-const void* stepper_kernel(int birth_death, int segregation, int window);
+// window: 1 = LDS tail window variant (default), 0 = rows straight in HBM (A/B reference); flags: kFlagPassageRt selects
+// the instances whose replicate start reads a passage run's founders (launch_stepper: a.flags)
+const void* stepper_kernel(int birth_death, int segregation, int window, uint32_t flags = 0);
 hipError_t launch_stepper(const StepperArgs& a, int birth_death, int segregation, int window, uint32_t blocks,
                           hipStream_t stream);
 // Bin store (ECDNA_FLAG_BIN_STORE): bin_k = 64 or 256 binned copy numbers; c32 = u32 counters
@@ -201,6 +247,12 @@ hipError_t launch_subsample(const SubsampleArgs& a, uint32_t blocks, hipStream_t
 // samples' histograms has room in LDS beside the rest (else the waves add their samples' bins to global memory).
 uint32_t snapstats_waves(uint32_t bins, uint32_t table_slots, size_t* lds_bytes, bool* sample_hist_lds);
 hipError_t launch_snapstats(const SnapStatsArgs& a, uint32_t blocks, hipStream_t stream);
+// The passage pass (ssa_passage.hip): one wave per replicate; 1, 2 or 4 waves per workgroup, as many as keep its
+// dynamic LDS (lds_bytes) within 64 KiB. The waves add their samples' bins to global memory (no workgroup histogram:
+// at the limits, 2,048 bins beside m = 4096, the table, the histogram and the founders take 49 KiB of one wave).
+uint32_t passage_sort_slots(uint32_t m);
+uint32_t passage_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, uint32_t sort_slots, size_t* lds_bytes);
+hipError_t launch_passage(const PassageArgs& a, uint32_t blocks, hipStream_t stream);
 // The reference-draws stepper (row store; ssa_refdraws.hip)
 const void* refdraws_kernel(int birth_death, int segregation);
 int refdraws_block();

@@ -54,20 +54,80 @@ struct SamplePop {
     uint32_t nrow;
 };
 
+// Position v (below N) -> copy number kk, in download order: the N- cells (kk = 0), the counters k ascending, the row.
+// False for a position the counters and the row cannot account for.
+template <int BAG>
+__device__ __forceinline__ bool sample_pos_k(const SamplePop& pop, uint32_t v, uint32_t& kk) {
+    kk = 0;
+    if ((uint64_t)v < pop.nm) return true;
+    const uint32_t u = v - (uint32_t)pop.nm;
+    if (BAG && u < pop.small) {
+        uint32_t lo = 0, hi = pop.bag_k - 1u;  // the first b with pre[b] > u
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (pop.pre[mid] > u)
+                hi = mid;
+            else
+                lo = mid + 1u;
+        }
+        kk = lo + 1u;
+        return true;
+    }
+    const uint32_t j = u - pop.small;
+    if (j >= pop.nrow) return false;
+    kk = pop.row[j];
+    return true;
+}
+
+// The wave's table of drawn positions for m' picks: 2 * pow2ceil(m') slots (load <= 1/2), hashed by the top bits of a
+// multiplicative hash, linear probing.
+struct SampleTable {
+    uint32_t tsize;
+    uint32_t sh;
+};
+__device__ __forceinline__ SampleTable sample_table(uint32_t mp) {
+    const uint32_t lg = mp > 1u ? 32u - (uint32_t)__clz(mp - 1u) : 0u;
+    return {2u << lg, 31u - lg};
+}
+// Whether position v was picked (the table as wave_sample_picks left it).
+__device__ __forceinline__ bool sample_tab_has(const uint32_t* tab, SampleTable t, uint32_t v) {
+    uint32_t sl = (v * 0x9E3779B1u) >> t.sh;
+    for (uint32_t probe = 0; probe < t.tsize; ++probe) {
+        const uint32_t old = tab[sl];
+        if (old == v) return true;
+        if (old == kSubEmpty) return false;
+        sl = (sl + 1u) & (t.tsize - 1u);
+    }
+    return false;
+}
+
+// Appends the copy numbers of the lanes with `take` to out[0 .. cap) behind the n already there (wave-uniform n; the
+// order within a batch is lane order). Every lane of the wave calls it.
+__device__ __forceinline__ void wave_append_u16(bool take, uint32_t kk, uint16_t* out, uint32_t cap, uint32_t& n,
+                                                uint32_t lane) {
+    const unsigned long long mask = __ballot(take);
+    if (take) {
+        const uint32_t idx = n + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+        if (idx < cap) out[idx] = (uint16_t)kk;
+    }
+    n += (uint32_t)__popcll(mask);
+}
+
 // Steps 2-4 of the mapping: draws on stream `tag` until mp distinct positions below N have appeared; every new one is
 // looked up and counted into the wave's histogram wh (bins clip at `last`; comp: taken out of it, the picked cells
 // are those left out of the sample). psum gains the lane's sum of k over its picked positions. tab[table_slots] is
 // the wave's table of drawn positions (LDS). Returns true when the guard ends the population (too small a table, 2^16
 // draws, a position the counters and the row cannot account for): wh is then not to be used.
+// gout (ssa_passage.hip; nullptr: off): the true copy numbers of the picked N+ cells are appended to gout[0 .. gcap),
+// *gn counting them (the picks are the sample, comp == false; a complement's cells are gathered by its caller).
 template <int BAG>
 __device__ __forceinline__ bool wave_sample_picks(uint32_t* wh, uint32_t* tab, uint32_t table_slots,
                                                   const SamplePop& pop, uint32_t N, uint32_t mp, bool comp,
                                                   uint32_t last, uint32_t tag, uint64_t rid, uint32_t k0, uint32_t k1,
-                                                  uint32_t lane, uint64_t& psum) {
-    // table: 2 * pow2ceil(m') slots (load <= 1/2), hashed by the top bits of a multiplicative hash
-    const uint32_t lg = mp > 1u ? 32u - (uint32_t)__clz(mp - 1u) : 0u;
-    const uint32_t tsize = 2u << lg;
-    const uint32_t sh = 31u - lg;
+                                                  uint32_t lane, uint64_t& psum, uint16_t* gout = nullptr,
+                                                  uint32_t gcap = 0, uint32_t* gn = nullptr) {
+    const SampleTable tb = sample_table(mp);
+    const uint32_t tsize = tb.tsize, sh = tb.sh;
     bool bad = tsize > table_slots;
     const uint32_t tclear = bad ? 0u : tsize;
     for (uint32_t b = lane; b < tclear; b += 64u) tab[b] = kSubEmpty;
@@ -105,29 +165,11 @@ __device__ __forceinline__ bool wave_sample_picks(uint32_t* wh, uint32_t* tab, u
             }
             if (!placed) lane_bad = true;
         }
+        uint32_t kk = 0;
+        bool counted = false;
         if (isnew) {
-            // position -> copy number, in download order: N- cells, the counters k ascending, the row
-            uint32_t kk = 0;
-            bool ok = true;
-            if ((uint64_t)v >= pop.nm) {
-                const uint32_t u = v - (uint32_t)pop.nm;
-                if (BAG && u < pop.small) {
-                    uint32_t lo = 0, hi = pop.bag_k - 1u;  // the first b with pre[b] > u
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (pop.pre[mid] > u)
-                            hi = mid;
-                        else
-                            lo = mid + 1u;
-                    }
-                    kk = lo + 1u;
-                } else {
-                    const uint32_t j = u - pop.small;
-                    ok = j < pop.nrow;  // a position the counters and the row cannot account for
-                    if (ok) kk = pop.row[j];
-                }
-            }
-            if (ok) {
+            counted = sample_pos_k<BAG>(pop, v, kk);
+            if (counted) {
                 const uint32_t bin = kk < last ? kk : last;
                 if (comp)
                     atomicSub(&wh[bin], 1u);
@@ -138,6 +180,7 @@ __device__ __forceinline__ bool wave_sample_picks(uint32_t* wh, uint32_t* tab, u
                 lane_bad = true;
             }
         }
+        if (gout && !comp) wave_append_u16(counted && kk > 0u, kk, gout, gcap, *gn, lane);
         count += (uint32_t)__popcll(__ballot(isnew));
         base += nact;
         wave_sync_lds();

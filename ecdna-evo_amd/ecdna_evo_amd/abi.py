@@ -110,6 +110,32 @@ class Ext(C.Structure):
     ]
 
 
+class Passages(C.Structure):
+    """ecdna_ssa_passages_t: the passage block of ecdna_ssa_ctx_create_passages (added within ABI v13)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_passages", C.c_uint32),
+        ("passage_cells", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("passage_target_hists", C.POINTER(C.c_uint64)),
+    ]
+
+
+_MASK64 = (1 << 64) - 1
+
+
+def passage_seed(seed: int, g: int) -> int:
+    """The Philox key seed_g of growth phase g (passage mapping v1, include/ecdna_ssa.h): the seed for phase 0, else
+    the splitmix64 finaliser of seed + g * 0x9E3779B97F4A7C15 (mod 2^64)."""
+    if g == 0:
+        return int(seed) & _MASK64
+    z = (int(seed) + g * 0x9E3779B97F4A7C15) & _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
+
+
 STATS_DTYPE = np.dtype([("mean", "<f8"), ("entropy", "<f8"), ("frequency", "<f8"), ("ks", "<f8"),
                         ("mean_rel", "<f8"), ("entropy_rel", "<f8"), ("frequency_diff", "<f8"), ("cells", "<u8")])
 assert STATS_DTYPE.itemsize == 64
@@ -246,8 +272,16 @@ class RunSpec:
     snapshot_stats: bool = False
     snapshot_targets: Optional[Sequence[Sequence[int]]] = None
     snapshot_subsample_cells: int = 0
+    # serial passaging on the GPU (ecdna_ssa_passages_t, within ABI v13; the reference's cell-line strategy): n_passages
+    # growth phases per replicate, each after the first regrown from a sample of passage_cells cells of the previous
+    # one (Result.passages; distances against passage_targets[g], [G][hist_bins], or None: stats_target for all).
+    # 0 = an ordinary run. Needs FLAG_REP_STATS; no snapshots, no subsample_cells, no reference draws
+    n_passages: int = 0
+    passage_cells: int = 0
+    passage_targets: Optional[Sequence[Sequence[int]]] = None
     _keep: list = field(default_factory=list, repr=False)
     _keep_ext: list = field(default_factory=list, repr=False)
+    _keep_pas: list = field(default_factory=list, repr=False)
 
     def stride(self) -> int:
         """The id step as the C ABI reads it: replicate_stride 0 means 1 (include/ecdna_ssa.h)."""
@@ -384,6 +418,26 @@ class RunSpec:
             self._keep_ext.append(tgt)
             e.snapshot_target_hists = _ptr(tgt, C.c_uint64)
         return e
+
+    def passages(self) -> Optional[Passages]:
+        """The passage block this spec asks for, or None: the context is then made without ecdna_ssa_ctx_create_passages."""
+        if not (self.n_passages or self.passage_cells or self.passage_targets is not None):
+            return None
+        for name in ("n_passages", "passage_cells"):
+            if not (0 <= int(getattr(self, name)) < (1 << 32)):
+                raise ValueError(f"{name} = {getattr(self, name)} does not fit the ABI's u32 field")
+        self._keep_pas = []
+        b = Passages()
+        b.struct_size = C.sizeof(Passages)
+        b.n_passages = self.n_passages
+        b.passage_cells = self.passage_cells
+        if self.passage_targets is not None:
+            tgt = np.ascontiguousarray(self.passage_targets, dtype=np.uint64)
+            if tgt.shape != (self.n_passages, self.hist_bins):
+                raise ValueError("passage_targets must have one histogram of hist_bins entries per passage")
+            self._keep_pas.append(tgt)
+            b.passage_target_hists = _ptr(tgt, C.c_uint64)
+        return b
 
 
 def cost_hint(rates: Sequence[Sequence[float]], inits: Optional[Sequence[Dict[int, int]]] = None) -> List[float]:

@@ -29,6 +29,7 @@ EXPORTS = [
     "ecdna_ssa_run",
     "ecdna_ssa_ctx_create",
     "ecdna_ssa_ctx_create_ext",
+    "ecdna_ssa_ctx_create_passages",
     "ecdna_ssa_ctx_set_outputs",
     "ecdna_ssa_ctx_launch",
     "ecdna_ssa_ctx_sync",
@@ -38,6 +39,7 @@ EXPORTS = [
     "ecdna_ssa_ctx_download_stats",
     "ecdna_ssa_ctx_download_sample",
     "ecdna_ssa_ctx_download_snapshot_stats",
+    "ecdna_ssa_ctx_download_passages",
     "ecdna_ssa_ctx_download_rng_words",
     "ecdna_ssa_ctx_row_stride",
     "ecdna_ssa_ctx_geometry",
@@ -133,6 +135,12 @@ def lib():
         L.ecdna_ssa_ctx_create_ext.restype = C.c_int
         L.ecdna_ssa_ctx_download_snapshot_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ecdna_ssa_ctx_download_snapshot_stats.restype = C.c_int
+    # (likewise added within v13: serial passaging; Context raises when a spec asks an earlier library for it)
+    if hasattr(L, "ecdna_ssa_ctx_create_passages"):
+        L.ecdna_ssa_ctx_create_passages.argtypes = [P(abi.Params), P(abi.Ext), P(abi.Passages), P(C.c_void_p)]
+        L.ecdna_ssa_ctx_create_passages.restype = C.c_int
+        L.ecdna_ssa_ctx_download_passages.argtypes = [C.c_void_p] * 7
+        L.ecdna_ssa_ctx_download_passages.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -210,6 +218,9 @@ class Result:
         self.snapshot_sample_stats = None
         self.snapshot_sample_hist = None
         self.rng_words = None  # [n] u64 under FLAG_REFERENCE_DRAWS: ChaCha8 stream position at the end
+        # RunSpec.n_passages = G > 0: every growth phase's results (PassageResult), each array with a leading G axis;
+        # the fields above are then the last phase's
+        self.passages = None
 
     def row(self, i: int) -> np.ndarray:
         return self.rows[i, : int(self.summaries[i]["nplus"])]
@@ -218,16 +229,40 @@ class Result:
         return self.snapshot_rows[i, s, : int(self.snapshots[i, s]["nplus"])]
 
 
+class PassageResult:
+    """Every growth phase of a passage run (ecdna_ssa_ctx_download_passages): summaries [G][n], totals [G][n_sets],
+    stats and sample_stats [G][n] abi.STATS_DTYPE (the phase's final population and its sample of passage_cells cells),
+    hist and sample_hist [G][n_sets][hist_bins] u64."""
+
+    def __init__(self, summaries, totals, stats, sample_stats, hist, sample_hist):
+        self.summaries = summaries
+        self.totals = totals
+        self.stats = stats
+        self.sample_stats = sample_stats
+        self.hist = hist
+        self.sample_hist = sample_hist
+
+
 class Context:
     """A device-resident run (ecdna_ssa_ctx): create once, launch many times."""
 
-    def __init__(self, spec: "abi.RunSpec", ext: Optional["abi.Ext"] = None):
-        """`ext`: an explicit extension block (ecdna_ssa_ctx_create_ext); default: the one `spec` asks for, if any."""
+    def __init__(self, spec: "abi.RunSpec", ext: Optional["abi.Ext"] = None,
+                 passages: Optional["abi.Passages"] = None):
+        """`ext`: an explicit extension block (ecdna_ssa_ctx_create_ext); default: the one `spec` asks for, if any.
+        `passages`: likewise the passage block (ecdna_ssa_ctx_create_passages)."""
         self.spec = spec
         self.params = spec.params()
         self.ext = ext if ext is not None else spec.ext()
+        self.passages = passages if passages is not None else spec.passages()
         h = C.c_void_p()
-        if self.ext is not None:  # (only a spec that asks for the extension goes through _ext)
+        if self.passages is not None:  # (only a spec that asks for passages goes through _passages)
+            if not hasattr(lib(), "ecdna_ssa_ctx_create_passages"):
+                raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_passages (serial passaging)")
+            _check(lib().ecdna_ssa_ctx_create_passages(C.byref(self.params),
+                                                       C.byref(self.ext) if self.ext is not None else None,
+                                                       C.byref(self.passages), C.byref(h)),
+                   "ecdna_ssa_ctx_create_passages")
+        elif self.ext is not None:  # (only a spec that asks for the extension goes through _ext)
             if not hasattr(lib(), "ecdna_ssa_ctx_create_ext"):
                 raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_ext (per-snapshot statistics)")
             _check(lib().ecdna_ssa_ctx_create_ext(C.byref(self.params), C.byref(self.ext), C.byref(h)),
@@ -310,7 +345,7 @@ class Context:
             st = np.zeros(p.n_replicates, dtype=abi.STATS_DTYPE)
             _check(lib().ecdna_ssa_ctx_download_stats(self.h, st.ctypes.data), "download_stats")
             res.stats = st
-        if p.subsample_cells:
+        if p.subsample_cells or self.passages is not None:  # (a passage run: the last phase's sample)
             st = np.zeros(p.n_replicates, dtype=abi.STATS_DTYPE)
             sh = np.zeros(p.n_param_sets * p.hist_bins, dtype=np.uint64)
             _check(lib().ecdna_ssa_ctx_download_sample(self.h, st.ctypes.data, sh.ctypes.data), "download_sample")
@@ -328,6 +363,16 @@ class Context:
                 "download_snapshot_stats")
             res.snapshot_stats, res.snapshot_hist = st, sh
             res.snapshot_sample_stats, res.snapshot_sample_hist = sst, ssh
+        if self.passages is not None:
+            G, n, sets = self.passages.n_passages, p.n_replicates, p.n_param_sets
+            out = PassageResult(np.zeros((G, n), dtype=abi.SUMMARY_DTYPE), np.zeros((G, sets), dtype=abi.TOTALS_DTYPE),
+                                np.zeros((G, n), dtype=abi.STATS_DTYPE), np.zeros((G, n), dtype=abi.STATS_DTYPE),
+                                np.zeros((G, sets, p.hist_bins), dtype=np.uint64),
+                                np.zeros((G, sets, p.hist_bins), dtype=np.uint64))
+            _check(lib().ecdna_ssa_ctx_download_passages(
+                self.h, out.summaries.ctypes.data, out.totals.ctypes.data, out.stats.ctypes.data,
+                out.sample_stats.ctypes.data, out.hist.ctypes.data, out.sample_hist.ctypes.data), "download_passages")
+            res.passages = out
         if p.flags & abi.FLAG_REFERENCE_DRAWS:
             w = np.zeros(p.n_replicates, dtype=np.uint64)
             _check(lib().ecdna_ssa_ctx_download_rng_words(self.h, w.ctypes.data), "download_rng_words")

@@ -43,7 +43,11 @@
 extern "C" {
 #endif
 
-/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): per-snapshot ABC
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): serial passaging —
+ * every replicate regrown from its own sample on the GPU, the reference's cell-line strategy: the passage block
+ * ecdna_ssa_passages_t, ecdna_ssa_ctx_create_passages and ecdna_ssa_ctx_download_passages (below; passage mapping v1).
+ * ecdna_ssa_ctx_create_ext(p, ext, out) is ecdna_ssa_ctx_create_passages(p, ext, NULL, out).
+ * Added within v13 (additive: no layout and no existing function changes, the version stays 13): per-snapshot ABC
  * statistics on the GPU for longitudinal inference — the extension block ecdna_ssa_ext_t, ecdna_ssa_ctx_create_ext and
  * ecdna_ssa_ctx_download_snapshot_stats (below). ecdna_ssa_ctx_create(p, out) is ecdna_ssa_ctx_create_ext(p, NULL, out).
  * ABI v13: end-of-run subsampling on the GPU. ecdna_ssa_params_t gains subsample_cells and reserved1 (appended after
@@ -351,6 +355,70 @@ typedef struct {
  * launched and every output is ecdna_ssa_ctx_create's (struct_size, reserved and the sample size's range are checked
  * whenever ext is given). */
 int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, ecdna_ssa_ctx** out);
+
+/* Serial passaging (added within ABI v13; the reference's cell-line strategy of longitudinal inference: growth
+ * restarts from the subsample — a culture is grown, a few hundred cells are taken and measured, and those same cells
+ * found the next flask. The patient strategy, growth continuing from the whole population, is the per-snapshot
+ * statistics above). Every replicate is regrown on the GPU from its own sample; nothing but the results leaves the
+ * device, so chunked sweeps are covered.
+ *
+ * Passage mapping v1. A run with n_passages = G and passage_cells = m runs G growth phases g = 0 .. G-1 per replicate
+ * r (r the GLOBAL id).
+ *  - Key. Phase g runs under Philox key seed_g: seed_0 = seed; for g >= 1, with all arithmetic mod 2^64 (the
+ *    splitmix64 finaliser of seed + g * golden ratio),
+ *        z = seed + g * 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *        z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  seed_g = z ^ (z >> 31).
+ *    It is computed on the host: the stepper and the sample pass of phase g receive seed_g where they receive seed in
+ *    an ordinary run.
+ *  - One phase is an ordinary run: the event index starts at 0 and the time at 0, the spare-word stack is empty, the
+ *    hash is at its offset, and the stop checks are those of DESIGN.md §3.1 with the run's max_cells / max_time /
+ *    max_iter.
+ *  - Phase 0 starts from the run's initial distribution: bit for bit the plain run of the same parameters, and its
+ *    sample is the plain run's subsample_cells = m sample.
+ *  - End of phase g: the population is sampled by subsample mapping v1 (ecdna_ssa_params_t.subsample_cells above),
+ *    unchanged — counter (i, 0xC0000000 | t, r lo, r hi), stream field 0 — under key seed_g. The population is the
+ *    one that pass sees in an ordinary run (the replicate's final n- and N+ cells, whatever its stop reason; an
+ *    extinct or never-started replicate is N = 0). The sample's statistics and histogram are phase g's measurement.
+ *  - Founders of phase g + 1: n- = the number of N- cells in the sample; the N+ cells are the sample's cells with
+ *    their TRUE copy numbers (not the clipped bins), in ascending copy-number order — the order an initial histogram
+ *    gives (copy numbers ascending), so a phase is replayed by an ordinary run whose initial distribution is the
+ *    founders' histogram.
+ *  - m >= N carries the whole population. An empty sample founds a phase that stops with ECDNA_REP_ERR_EMPTY after
+ *    zero events, exactly like an empty initial distribution; so does a sample the guard ended (2^16 draws, or a
+ *    position the state cannot account for).
+ *  - Bin store: a replicate with more founders of k > bin_kmax than big_cap stops at its start, after zero events,
+ *    with ECDNA_REP_ERR_CELL_CAP; it is reported with no cells (n- = n+ = 0: the founders could not be held), so its
+ *    next phase stops with ECDNA_REP_ERR_EMPTY. (A defence: the founders are a subset of a population that never held
+ *    more than big_cap such cells, so no run reaches it; it keeps a broken invariant from writing off the row.)
+ * Results depend only on (seed, r, parameters): chunks, shards, grids, schedules and rotation reproduce each other
+ * bit for bit, as everywhere else. */
+typedef struct {
+    uint32_t struct_size;                  /* sizeof(ecdna_ssa_passages_t); anything else: ECDNA_E_INVALID */
+    uint32_t n_passages;                   /* G, 1 .. 16 */
+    uint32_t passage_cells;                /* m, 1 .. 4096, <= cell_cap */
+    uint32_t reserved;                     /* must be 0 */
+    const uint64_t* passage_target_hists;  /* host, [G][hist_bins]: phase g's own target; NULL:
+                                              params.stats_target_hist for all */
+} ecdna_ssa_passages_t;
+/* ecdna_ssa_ctx_create_ext with a passage block. passages == NULL: ecdna_ssa_ctx_create_ext. Otherwise the run needs
+ * ECDNA_FLAG_REP_STATS, and these are rejected (ECDNA_E_INVALID, before a device is touched, the message names the
+ * field): params.subsample_cells != 0 (the block owns the sample size), params.n_snapshots != 0, ext->snapshot_stats,
+ * ECDNA_FLAG_REFERENCE_DRAWS (continuing a ChaCha8 stream across phases is a different feature), an all-zero target
+ * row, out-of-range fields.
+ * After a launch, ecdna_ssa_ctx_download, _download_stats, _download_sample and ecdna_ssa_ctx_reduce return the LAST
+ * phase's results (rows included where the run is one chunk); ecdna_ssa_ctx_sync returns times summed over the
+ * phases (hist_ms includes the passage pass). */
+int ecdna_ssa_ctx_create_passages(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                                  const ecdna_ssa_passages_t* passages, ecdna_ssa_ctx** out);
+/* Every phase's results of the last launch of a passage context (else ECDNA_E_STATE, as before a launch). Any buffer
+ * may be NULL. With G = n_passages, n = n_replicates: out_summaries [G][n], out_totals [G][n_param_sets], out_stats
+ * [G][n] (the whole final population of the phase), out_sample_stats [G][n] (its sample, cells = the sample's size),
+ * out_hist and out_sample_hist [G][n_param_sets][hist_bins]. Distances are against phase g's target. Chunked runs are
+ * covered. ecdna_ssa_ctx_reduce reduces the last phase's histogram and totals only: callers sum the shards' per-phase
+ * arrays themselves. */
+int ecdna_ssa_ctx_download_passages(ecdna_ssa_ctx* c, ecdna_rep_summary_t* out_summaries, ecdna_totals_t* out_totals,
+                                    ecdna_rep_stats_t* out_stats, ecdna_rep_stats_t* out_sample_stats,
+                                    uint64_t* out_hist, uint64_t* out_sample_hist);
 /* Use caller-owned DEVICE buffers for the histogram [n_param_sets*hist_bins] u64 and totals
  * [n_param_sets] (e.g. tensors later all-reduced over RCCL). NULL keeps the internal buffer. */
 int ecdna_ssa_ctx_set_outputs(ecdna_ssa_ctx* c, uint64_t* d_hist, ecdna_totals_t* d_totals);
