@@ -31,12 +31,17 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                                \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return fail(_e == hipErrorOutOfMemory ? ECDNA_E_NOMEM : ECDNA_E_HIP,                     \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                          \
+// TRY(expr): return from the calling function with the error of a failed step, which is either a HIP call (the
+// error is recorded here, with the call's text) or a function of this file that returns an ECDNA_* code (and has
+// recorded its own).
+int rc_of(int rc, const char*) { return rc; }
+int rc_of(hipError_t e, const char* what) {
+    if (e == hipSuccess) return ECDNA_OK;
+    return fail(e == hipErrorOutOfMemory ? ECDNA_E_NOMEM : ECDNA_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define TRY(expr)                                         \
+    do {                                                  \
+        if (int _rc = rc_of((expr), #expr)) return _rc;   \
     } while (0)
 
 uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
@@ -58,6 +63,16 @@ InitOfSet init_of_set(const ecdna_ssa_params_t* p, uint64_t s) {
     }
     r.nminus = p->init_set_nminus ? p->init_set_nminus[s] : p->init_nminus;
     return r;
+}
+
+// The index of the first of `count` target histograms ([count][bins]) without a cell; count if there is none, or no
+// targets at all.
+uint32_t first_empty_target(const uint64_t* hists, uint32_t count, uint32_t bins) {
+    for (uint32_t i = 0; hists && i < count; ++i) {
+        const uint64_t* t = hists + (uint64_t)i * bins;
+        if (std::all_of(t, t + bins, [](uint64_t x) { return x == 0; })) return i;
+    }
+    return count;
 }
 
 int validate(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, const ecdna_ssa_passages_t* pas) {
@@ -131,13 +146,9 @@ int validate(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, const ecdn
             if (!p->n_snapshots) return fail(ECDNA_E_INVALID, "ext.snapshot_stats needs n_snapshots > 0");
             if (!(p->flags & ECDNA_FLAG_REP_STATS))
                 return fail(ECDNA_E_INVALID, "ext.snapshot_stats needs ECDNA_FLAG_REP_STATS");
-            for (uint32_t q = 0; ext->snapshot_target_hists && q < p->n_snapshots; ++q) {
-                const uint64_t* t = ext->snapshot_target_hists + (uint64_t)q * p->hist_bins;
-                bool any = false;
-                for (uint32_t b = 0; b < p->hist_bins; ++b) any |= t[b] != 0;
-                if (!any)
-                    return fail(ECDNA_E_INVALID, "ext.snapshot_target_hists[" + std::to_string(q) + "] is empty");
-            }
+            const uint32_t q = first_empty_target(ext->snapshot_target_hists, p->n_snapshots, p->hist_bins);
+            if (q < p->n_snapshots)
+                return fail(ECDNA_E_INVALID, "ext.snapshot_target_hists[" + std::to_string(q) + "] is empty");
         }
     }
     if (pas) {  // the passage block (serial passaging)
@@ -157,13 +168,9 @@ int validate(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, const ecdn
         if (ext && ext->snapshot_stats) return fail(ECDNA_E_INVALID, "passages: ext.snapshot_stats must be 0");
         if (p->flags & ECDNA_FLAG_REFERENCE_DRAWS)
             return fail(ECDNA_E_INVALID, "passages do not run under ECDNA_FLAG_REFERENCE_DRAWS");
-        for (uint32_t g = 0; pas->passage_target_hists && g < pas->n_passages; ++g) {
-            const uint64_t* t = pas->passage_target_hists + (uint64_t)g * p->hist_bins;
-            bool any = false;
-            for (uint32_t b = 0; b < p->hist_bins; ++b) any |= t[b] != 0;
-            if (!any)
-                return fail(ECDNA_E_INVALID, "passages.passage_target_hists[" + std::to_string(g) + "] is empty");
-        }
+        const uint32_t g = first_empty_target(pas->passage_target_hists, pas->n_passages, p->hist_bins);
+        if (g < pas->n_passages)
+            return fail(ECDNA_E_INVALID, "passages.passage_target_hists[" + std::to_string(g) + "] is empty");
     }
     return ECDNA_OK;
 }
@@ -176,23 +183,6 @@ uint64_t passage_seed(uint64_t seed, uint32_t g) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
-}
-
-// A target histogram's CDF over the bins and its mean / entropy / N+ frequency (the overflow bin counts at
-// k = bins - 1), as the kernels compare against them. tot > 0.
-void target_summary(const uint64_t* hist, uint32_t bins, double tot, double* cdf, double* mean, double* entropy,
-                    double* freq) {
-    double acc = 0.0, ksum = 0.0, ent = 0.0;
-    for (uint32_t b = 0; b < bins; ++b) {
-        const double pb = (double)hist[b] / tot;
-        acc += pb;
-        cdf[b] = acc;
-        ksum += (double)b * (double)hist[b];
-        if (pb > 0.0) ent -= pb * std::log(pb);
-    }
-    *mean = ksum / tot;
-    *entropy = ent;
-    *freq = 1.0 - (double)hist[0] / tot;
 }
 
 // Reference draws (ECDNA_FLAG_REFERENCE_DRAWS): rand_core 0.6.4 seed_from_u64 — the 32-byte ChaCha key filled
@@ -266,7 +256,7 @@ struct ecdna_ssa_ctx {
     uint32_t bin_k = 0;
     int bin_c32 = 0;
     int bin_ilp = 0;  // the bin stepper's schedule: 0 default, 1 max-ILP (lone waves), 2 128-VGPR K = 64, 3 max-ILP paired lanes (ssa_launch.h)
-    void* d_bags = nullptr;
+    unsigned char* d_bags = nullptr;
     uint32_t stepper_block = ecdna::kStepperBlock;
     // reference draws (ECDNA_FLAG_REFERENCE_DRAWS): the ChaCha8 key and the BTPE constants per copy number
     bool refdraws = false;
@@ -280,8 +270,7 @@ struct ecdna_ssa_ctx {
     std::vector<uint64_t> init_nminus_set;
     std::vector<uint64_t> snap_cells;
     // ABC statistics target
-    bool has_target = false;
-    double target_mean = 0.0, target_entropy = 0.0, target_freq = 0.0;
+    ecdna::StatsTarget target{};  // (cdf: d_target_cdf)
     double* d_target_cdf = nullptr;
     ecdna_rep_stats_t* d_stats = nullptr;
     // end-of-run subsampling (subsample_cells > 0): the samples' statistics [n] and histogram [n_sets][bins]
@@ -314,7 +303,9 @@ struct ecdna_ssa_ctx {
     uint64_t* d_pas_sample_hist = nullptr;          // [G][n_sets][bins]
     double* d_pas_target_cdf = nullptr;             // [G][bins], or nullptr: no target
     std::vector<double> pas_target_scalars;         // [G][3]: the targets' mean, entropy, N+ frequency
-    // device buffers
+    // device buffers: every one is allocated by ctx_alloc / ctx_upload, which list it in `owned` for free_ctx
+    // (d_hist / d_tot: the caller's output buffers or d_hist_own / d_tot_own, never owned themselves)
+    std::vector<void*> owned;
     float4* d_rates = nullptr;
     uint16_t* d_init = nullptr;
     uint32_t* d_init_off = nullptr;
@@ -344,8 +335,9 @@ struct ecdna_ssa_ctx {
 namespace {
 
 // the flags the kernels see: the caller's, plus the internal snapshot bit that selects the runtime-flags instances
-uint32_t kernel_flags(const ecdna_ssa_params_t& p, bool passages) {
-    return p.flags | (p.n_snapshots ? ecdna::kFlagSnapshotsRt : 0u) | (passages ? ecdna::kFlagPassageRt : 0u);
+// and the passage bit that selects the instances that start from founders
+uint32_t kernel_flags(const ecdna_ssa_ctx& c) {
+    return c.p.flags | (c.p.n_snapshots ? ecdna::kFlagSnapshotsRt : 0u) | (c.n_passages ? ecdna::kFlagPassageRt : 0u);
 }
 
 int pick_device(int dev) {
@@ -389,48 +381,652 @@ void free_ctx(ecdna_ssa_ctx* c) {
     for (auto& ch : c->chunks)
         for (auto& e : ch.ev)
             if (e) (void)hipEventDestroy(e);
-    (void)hipFree(c->d_rates);
-    (void)hipFree(c->d_init);
-    (void)hipFree(c->d_init_off);
-    (void)hipFree(c->d_init_nm);
-    (void)hipFree(c->d_snap_cells);
-    (void)hipFree(c->d_snap_meta);
-    (void)hipFree(c->d_snap_rows);
-    (void)hipFree(c->d_target_cdf);
-    (void)hipFree(c->d_stats);
-    (void)hipFree(c->d_sample_stats);
-    (void)hipFree(c->d_sample_hist);
-    (void)hipFree(c->d_snap_stats);
-    (void)hipFree(c->d_snap_sample_stats);
-    (void)hipFree(c->d_snap_hist);
-    (void)hipFree(c->d_snap_sample_hist);
-    (void)hipFree(c->d_snap_target_cdf);
-    (void)hipFree(c->d_snap_target_scalars);
-    (void)hipFree(c->d_founder_rows);
-    (void)hipFree(c->d_founder_counts);
-    (void)hipFree(c->d_pas_summ);
-    (void)hipFree(c->d_pas_hist);
-    (void)hipFree(c->d_pas_tot);
-    (void)hipFree(c->d_pas_stats);
-    (void)hipFree(c->d_pas_sample_stats);
-    (void)hipFree(c->d_pas_sample_hist);
-    (void)hipFree(c->d_pas_target_cdf);
-    (void)hipFree(c->d_rows);
-    (void)hipFree(c->d_bags);
-    (void)hipFree(c->d_summ);
-    (void)hipFree(c->d_heads);
-    (void)hipFree(c->d_order);
-    (void)hipFree(c->d_rot_parts);
-    (void)hipFree(c->d_rot_flags);
-    (void)hipFree(c->d_rot_park);
-    (void)hipFree(c->d_ref_key);
-    (void)hipFree(c->d_ref_btpe);
-    (void)hipFree(c->d_rng_words);
-    (void)hipFree(c->d_hist_own);
-    (void)hipFree(c->d_tot_own);
+    for (void* d : c->owned) (void)hipFree(d);
     delete c;
 }
 
+// A device buffer of `count` elements that the context owns from here on; ctx_upload: holding a copy of `host`
+// (elements of the same size). Under TRY a failure is reported with the call's text, which names the buffer.
+template <typename T>
+hipError_t ctx_alloc(ecdna_ssa_ctx* c, T** ptr, uint64_t count) {
+    const hipError_t e = hipMalloc(ptr, count * sizeof(T));
+    if (e == hipSuccess) c->owned.push_back(*ptr);
+    return e;
+}
+template <typename T, typename H>
+hipError_t ctx_upload(ecdna_ssa_ctx* c, T** ptr, const std::vector<H>& host) {
+    static_assert(sizeof(T) == sizeof(H), "ctx_upload copies bytes");
+    const hipError_t e = ctx_alloc(c, ptr, host.size());
+    return e != hipSuccess ? e : hipMemcpy(*ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+// `count` elements from the device to the host, and from device to device on a stream.
+template <typename T>
+hipError_t to_host(T* out, const T* dev, uint64_t count) {
+    return hipMemcpy(out, dev, count * sizeof(T), hipMemcpyDeviceToHost);
+}
+template <typename T>
+hipError_t copy_async(T* dst, const T* src, uint64_t count, hipStream_t st) {
+    return hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToDevice, st);
+}
+
+// The preludes of the sync and download functions: a context that was launched; its device current and its stream
+// drained. (Between the two a download checks what else it needs, and returns early when there is nothing to copy.)
+int ctx_launched(const ecdna_ssa_ctx* c, const char* what = "download before launch") {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!c->launched) return fail(ECDNA_E_STATE, what);
+    return ECDNA_OK;
+}
+int ctx_drain(ecdna_ssa_ctx* c) {
+    TRY(hipSetDevice(c->device));
+    TRY(hipStreamSynchronize(c->last_stream));
+    return ECDNA_OK;
+}
+
+// ---- ecdna_ssa_ctx_create_passages, step by step (in this order: each step builds on the ones before, and the chunk
+// size depends on what is allocated before plan_chunks asks for the free memory) ----
+
+// Sum of a target histogram (> 0 for a usable target), and for `count` of them ([count][bins]) what the kernels
+// compare against: the CDFs over the bins ([count][bins]) and the scalars ([count][3]: mean, entropy, N+ frequency;
+// the overflow bin counts at k = bins - 1).
+double target_total(const uint64_t* hist, uint32_t bins) {
+    double tot = 0.0;
+    for (uint32_t b = 0; b < bins; ++b) tot += (double)hist[b];
+    return tot;
+}
+void summarize_targets(const uint64_t* hists, uint64_t count, uint32_t bins, double* cdf_out, double* scalars_out) {
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint64_t* hist = hists + i * bins;
+        const double tot = target_total(hist, bins);
+        double acc = 0.0, ksum = 0.0, ent = 0.0;
+        for (uint32_t b = 0; b < bins; ++b) {
+            const double pb = (double)hist[b] / tot;
+            acc += pb;
+            cdf_out[i * bins + b] = acc;
+            ksum += (double)b * (double)hist[b];
+            if (pb > 0.0) ent -= pb * std::log(pb);
+        }
+        scalars_out[3 * i] = ksum / tot;
+        scalars_out[3 * i + 1] = ent;
+        scalars_out[3 * i + 2] = 1.0 - (double)hist[0] / tot;
+    }
+}
+
+// The context's own copies of the caller's inputs, and what the parameters alone decide: strides and the cell store.
+void adopt_params(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                  const ecdna_ssa_passages_t* pas) {
+    c->p = *p;
+    c->device = p->device;
+    if (pas) {
+        c->n_passages = pas->n_passages;
+        c->passage_m = pas->passage_cells;
+        c->founder_stride = round_up(pas->passage_cells, 64);
+    }
+    c->snap_stats = ext && ext->snapshot_stats;
+    if (c->snap_stats) c->snap_m = ext->snapshot_subsample_cells;
+    c->rates.assign(p->rates, p->rates + p->n_param_sets);
+    uint64_t n_init = p->init_set_offsets ? p->init_set_offsets[p->n_param_sets] : p->init_nplus;
+    c->init_copies.assign(p->init_copies ? p->init_copies : nullptr,
+                          p->init_copies ? p->init_copies + n_init : nullptr);
+    if (c->init_copies.empty()) c->init_copies.push_back(1);
+    if (p->init_set_offsets) c->init_offsets.assign(p->init_set_offsets, p->init_set_offsets + p->n_param_sets + 1);
+    if (p->init_set_nminus) c->init_nminus_set.assign(p->init_set_nminus, p->init_set_nminus + p->n_param_sets);
+    if (p->n_snapshots) c->snap_cells.assign(p->snapshot_cells, p->snapshot_cells + p->n_snapshots);
+    c->p.snapshot_cells = nullptr;
+    c->p.rates = nullptr;
+    c->p.init_copies = nullptr;
+    c->p.init_set_offsets = nullptr;
+    c->p.init_set_nminus = nullptr;
+    c->p.stats_target_hist = nullptr;
+
+    c->row_stride = round_up(p->cell_cap, 64);
+    c->out_stride = c->row_stride;
+    if (p->flags & ECDNA_FLAG_BIN_STORE) {
+        c->big_cap = (p->big_cap && p->big_cap < p->cell_cap) ? p->big_cap : p->cell_cap;
+        c->row_stride = round_up(c->big_cap, 64);
+        c->bin_k = p->bin_kmax ? p->bin_kmax : 64;
+        // u16 counters hold at most 65535 cells per bin/group; K = 32 always uses u32 counters: the same LDS
+        // footprint as K = 64/u16 (144 B per lane), no 16-bit packing in the updates and the scan (C3:
+        // 119 ms against 126 ms with u16, DESIGN.md §8)
+        // (ECDNA_SSA_C32 = 1 forces u32 counters at any K: a development knob, results are the same)
+        c->bin_c32 = (p->cell_cap > 65535u || c->bin_k <= 32 || env_u64("ECDNA_SSA_C32", 0)) ? 1 : 0;
+        c->stepper_block = (uint32_t)ecdna::bin_stepper_block(c->bin_k);
+    }
+}
+
+// bytes of one replicate's bin counters
+uint64_t bag_bytes(const ecdna_ssa_ctx* c) { return (uint64_t)c->bin_k * (c->bin_c32 ? 4u : 2u); }
+
+int upload_inputs(ecdna_ssa_ctx* c) {
+    hipDeviceProp_t prop;
+    TRY(hipGetDeviceProperties(&prop, c->device));
+    c->cus = prop.multiProcessorCount;
+    std::vector<float4> r4(c->rates.size());
+    for (size_t s = 0; s < r4.size(); ++s) r4[s] = make_float4(c->rates[s].b0, c->rates[s].b1, c->rates[s].d0, c->rates[s].d1);
+    TRY(ctx_upload(c, &c->d_rates, r4));
+    TRY(ctx_upload(c, &c->d_init, c->init_copies));
+    if (!c->init_offsets.empty()) TRY(ctx_upload(c, &c->d_init_off, c->init_offsets));
+    if (!c->init_nminus_set.empty()) TRY(ctx_upload(c, &c->d_init_nm, c->init_nminus_set));
+    if (!c->snap_cells.empty()) TRY(ctx_upload(c, &c->d_snap_cells, c->snap_cells));
+    return ECDNA_OK;
+}
+
+// ABC statistics: the statistics themselves, and each target's CDF over the bins and its mean / entropy / N+ frequency
+// (the overflow bin counts at k = bins - 1), computed once on the host: the run's, each phase's, each snapshot's.
+int upload_targets(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                   const ecdna_ssa_passages_t* pas) {
+    const uint32_t bins = p->hist_bins;
+    if ((p->flags & ECDNA_FLAG_REP_STATS) && p->n_replicates) {
+        TRY(ctx_alloc(c, &c->d_stats, p->n_replicates));
+        if (p->stats_target_hist) {
+            if (!(target_total(p->stats_target_hist, bins) > 0.0)) return fail(ECDNA_E_INVALID, "stats_target_hist is empty");
+            std::vector<double> cdf(bins);
+            double sc[3];
+            summarize_targets(p->stats_target_hist, 1, bins, cdf.data(), sc);
+            c->target = ecdna::StatsTarget{nullptr, sc[0], sc[1], sc[2], 1u};
+            TRY(ctx_upload(c, &c->d_target_cdf, cdf));
+            c->target.cdf = c->d_target_cdf;
+        }
+    }
+    if (pas && pas->passage_target_hists) {  // phase g's own target
+        std::vector<double> cdf((uint64_t)pas->n_passages * bins);
+        c->pas_target_scalars.assign(pas->n_passages * 3, 0.0);
+        summarize_targets(pas->passage_target_hists, pas->n_passages, bins, cdf.data(), c->pas_target_scalars.data());
+        TRY(ctx_upload(c, &c->d_pas_target_cdf, cdf));
+    }
+    if (c->snap_stats && ext->snapshot_target_hists) {
+        std::vector<double> cdf((uint64_t)p->n_snapshots * bins), scal(p->n_snapshots * 3);
+        summarize_targets(ext->snapshot_target_hists, p->n_snapshots, bins, cdf.data(), scal.data());
+        TRY(ctx_upload(c, &c->d_snap_target_cdf, cdf));
+        TRY(ctx_upload(c, &c->d_snap_target_scalars, scal));
+    }
+    return ECDNA_OK;
+}
+
+// Outputs sized by the run (not by the chunk).
+int alloc_outputs(ecdna_ssa_ctx* c) {
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t n = p.n_replicates, n1 = std::max<uint64_t>(n, 1);
+    const uint64_t nb = (uint64_t)p.n_param_sets * p.hist_bins;
+    if (p.subsample_cells || c->n_passages) {  // (a passage run: the last phase's sample)
+        TRY(ctx_alloc(c, &c->d_sample_stats, n1));
+        TRY(ctx_alloc(c, &c->d_sample_hist, nb));
+    }
+    if (c->n_passages) {  // every phase's outputs, sized G x run; the last phase's are copied into the ordinary buffers
+        const uint64_t G = c->n_passages;
+        TRY(ctx_alloc(c, &c->d_pas_summ, G * n1));
+        TRY(ctx_alloc(c, &c->d_pas_stats, G * n1));
+        TRY(ctx_alloc(c, &c->d_pas_sample_stats, G * n1));
+        TRY(ctx_alloc(c, &c->d_pas_hist, G * nb));
+        TRY(ctx_alloc(c, &c->d_pas_sample_hist, G * nb));
+        TRY(ctx_alloc(c, &c->d_pas_tot, G * p.n_param_sets));
+    }
+    // per-snapshot statistics: sized by the run (the snapshot rows they are computed from may be one chunk's)
+    if (c->snap_stats) {
+        const uint64_t S = p.n_snapshots;
+        TRY(ctx_alloc(c, &c->d_snap_stats, n1 * S));
+        TRY(ctx_alloc(c, &c->d_snap_hist, S * nb));
+        if (c->snap_m) {
+            TRY(ctx_alloc(c, &c->d_snap_sample_stats, n1 * S));
+            TRY(ctx_alloc(c, &c->d_snap_sample_hist, S * nb));
+        }
+    }
+    TRY(ctx_alloc(c, &c->d_hist_own, nb));
+    TRY(ctx_alloc(c, &c->d_tot_own, p.n_param_sets));
+    TRY(hipMemset(c->d_hist_own, 0, nb * sizeof(uint64_t)));
+    TRY(hipMemset(c->d_tot_own, 0, p.n_param_sets * sizeof(ecdna_totals_t)));
+    c->d_hist = c->d_hist_own;
+    c->d_tot = c->d_tot_own;
+    TRY(ctx_alloc(c, &c->d_summ, n1));
+    if (p.n_snapshots && n) {  // snapshot outputs cover the whole run (not chunked)
+        TRY(ctx_alloc(c, &c->d_snap_meta, n * p.n_snapshots));
+        if (p.flags & ECDNA_FLAG_SNAPSHOT_ROWS) TRY(ctx_alloc(c, &c->d_snap_rows, n * p.n_snapshots * c->out_stride));
+    }
+    return ECDNA_OK;
+}
+
+// rows: one u16 row per replicate of the chunk; chunk bounded by free HBM. Then the chunks, their events and their
+// start order.
+int plan_chunks(ecdna_ssa_ctx* c, const float* set_cost_hint) {
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t n = p.n_replicates;
+    const uint64_t rot_bytes = c->bin_k ? ecdna::kParkVecs * 16u + 4u : 0u;  // parked scalars + state word
+    // (snapshot statistics without ECDNA_FLAG_SNAPSHOT_ROWS: the snapshot rows are the chunk's scratch, n_snapshots
+    // rows of out_stride cells per replicate of the chunk, so a large run chunks instead of failing)
+    c->snap_rows_local = c->snap_stats && !c->d_snap_rows;
+    const uint64_t snap_row_bytes = c->snap_rows_local ? p.n_snapshots * c->out_stride * sizeof(uint16_t) : 0u;
+    // (a passage run: the chunk's founders, one row of passage_cells and {n-, n+} per replicate)
+    const uint64_t founder_bytes = c->n_passages ? c->founder_stride * sizeof(uint16_t) + sizeof(uint2) : 0u;
+    const uint64_t row_bytes =
+        c->row_stride * sizeof(uint16_t) + bag_bytes(c) + rot_bytes + snap_row_bytes + founder_bytes;
+    size_t free_b = 0, total_b = 0;
+    TRY(hipMemGetInfo(&free_b, &total_b));
+    uint64_t budget = (uint64_t)((double)free_b * 0.85);
+    uint64_t cap_budget = env_u64("ECDNA_SSA_MAX_ROW_BYTES", 0);
+    if (cap_budget) budget = std::min<uint64_t>(budget, cap_budget);
+    uint64_t fit = budget / row_bytes;
+    uint64_t max_chunk = env_u64("ECDNA_SSA_MAX_CHUNK", 0);
+    if (max_chunk) fit = std::min<uint64_t>(fit, max_chunk);
+    if (fit == 0) return fail(ECDNA_E_NOMEM, "one replicate row does not fit in device memory");
+    c->chunk_reps = std::min<uint64_t>(std::max<uint64_t>(n, 1), fit);
+    TRY(ctx_alloc(c, &c->d_rows, c->chunk_reps * c->row_stride));
+    if (c->bin_k) TRY(ctx_alloc(c, &c->d_bags, c->chunk_reps * bag_bytes(c)));
+    if (c->snap_rows_local) TRY(ctx_alloc(c, &c->d_snap_rows, c->chunk_reps * p.n_snapshots * c->out_stride));
+    if (c->n_passages) {
+        TRY(ctx_alloc(c, &c->d_founder_rows, c->chunk_reps * c->founder_stride));
+        TRY(ctx_alloc(c, &c->d_founder_counts, c->chunk_reps));
+    }
+
+    const uint64_t n_chunks = n ? (n + c->chunk_reps - 1) / c->chunk_reps : 0;
+    TRY(ctx_alloc(c, &c->d_heads, std::max<uint64_t>(n_chunks, 1)));
+    for (uint64_t k = 0; k < n_chunks; ++k) {
+        Chunk ch{};
+        ch.first = k * c->chunk_reps;
+        ch.n = (uint32_t)std::min<uint64_t>(c->chunk_reps, n - ch.first);
+        c->chunks.push_back(ch);
+        c->chunks.back().ev.assign(3u * std::max<uint32_t>(c->n_passages, 1u), nullptr);
+        for (auto& e : c->chunks.back().ev) TRY(hipEventCreate(&e));
+    }
+
+    // start order (set_cost_hint): within each chunk, replicates of costlier sets first, then by id
+    if (set_cost_hint && n) {
+        const uint64_t stride = p.replicate_stride ? p.replicate_stride : 1u;
+        std::vector<uint32_t> order(n);
+        for (const Chunk& ch : c->chunks) {
+            uint32_t* o = order.data() + ch.first;
+            for (uint32_t i = 0; i < ch.n; ++i) o[i] = i;
+            auto cost = [&](uint32_t i) {
+                const float v = set_cost_hint[(p.first_replicate + (ch.first + i) * stride) / p.reps_per_set];
+                return v == v ? v : 0.0f;  // (NaN: no preference)
+            };
+            std::stable_sort(o, o + ch.n, [&](uint32_t x, uint32_t y) { return cost(x) > cost(y); });
+        }
+        TRY(ctx_upload(c, &c->d_order, order));
+    }
+    return ECDNA_OK;
+}
+
+// persistent stepper grid: as many resident lanes as the occupancy allows; the bin stepper's instruction schedule
+int plan_stepper_grid(ecdna_ssa_ctx* c) {
+    const ecdna_ssa_params_t& p = c->p;
+    c->window = env_u64("ECDNA_SSA_WINDOW", 1) ? 1 : 0;
+    int per_cu = 0;
+    c->refdraws = (p.flags & ECDNA_FLAG_REFERENCE_DRAWS) != 0;
+    if (c->refdraws) {
+        std::vector<uint32_t> key(8);
+        chacha_key_from_u64(p.seed, key.data());
+        TRY(ctx_upload(c, &c->d_ref_key, key));
+        std::vector<double> bt((uint64_t)32768 * kBtpeRow, 0.0);
+        for (uint64_t k = 10; k < 32768; ++k) btpe_setup(2 * k, bt.data() + k * kBtpeRow);
+        TRY(ctx_upload(c, &c->d_ref_btpe, bt));
+        TRY(ctx_alloc(c, &c->d_rng_words, std::max<uint64_t>(p.n_replicates, 1)));
+        c->stepper_block = (uint32_t)ecdna::refdraws_block();
+        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu, ecdna::refdraws_kernel(p.process, p.segregation), (int)c->stepper_block, 0));
+    } else if (c->bin_k) {
+        // Instruction schedule: with at most one wave of replicates per SIMD (every chunk within 256 lanes
+        // per CU) each wave runs alone and waits on its own dependencies, and the max-ILP schedule is faster
+        // (C2 8.6 -> 8.1 ms, C5 8-GPU shard 22.0 -> 21.1 s); with more, issue binds and the default schedule
+        // keeps 4 waves per SIMD (max-ILP: 3, C3 +8 %). The K = 64 / u16 kernel needs 130 VGPRs (3
+        // workgroups per CU); its 128-VGPR build fits 4 and pays once lanes run many replicates each (the
+        // whole C4 sweep on one GPU, 16 per lane: 834 -> 771 ms) but not with few (C4 8-GPU shard, 2 per
+        // lane: a longer drain, 127 -> 134 ms), so auto takes it from 4 replicates per lane of its grid on.
+        // ECDNA_SSA_SCHED = 0 default, 1 max-ILP, 2 auto, 3 the 128-VGPR build (K = 64 / u16; else 0).
+        uint64_t max_chunk = 0;
+        for (const auto& ch : c->chunks) max_chunk = std::max<uint64_t>(max_chunk, ch.n);
+        const uint32_t kflags = kernel_flags(*c);
+        const uint64_t sched = env_u64("ECDNA_SSA_SCHED", 2);
+        // (auto only without f32 time and the event hash: that variant spills 12 B at 128 VGPRs)
+        const bool k64u16 = c->bin_k == 64 && !c->bin_c32;
+        const bool tf0 = (kflags & ecdna::kRuntimeFlagMask) == 0;
+        // Where the max-ILP build keeps the default's occupancy (LDS bounds both: K = 32 / u32 and K = 64 / u32
+        // since the f32 draw mapping v6, K = 256) it is taken too: its schedule then costs no lanes (C3 78.3 ->
+        // 77.3 ms, C5 whole 31.9 -> 30.4 s, same box). With fewer than four replicates per lane of the default
+        // grid it is taken even at one workgroup per CU less (K = 64 / u16, 118 against 134 VGPRs since v6: the
+        // C4 8-GPU shard, two replicates per lane, 127 -> 119 ms), as the drain of the last replicates is
+        // latency-bound (profiles/r04d_v6_suite_and_sched_sweep.txt).
+        int occ_def = 0, occ_ilp = 0;
+        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &occ_def, ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kflags, 0),
+            (int)c->stepper_block, 0));
+        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &occ_ilp, ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kflags, 1),
+            (int)c->stepper_block, 0));
+        // Paired lanes (DESIGN.md §5): with at most half a wave of replicates per SIMD (the C5 8-GPU shard) the
+        // idle half of each wave computes the next event's Philox block and soft log in the N- fast-forward.
+        // Birth-death without snapshots (the fast-forward's domain). ECDNA_SSA_PAIR = 0 off, 1 whenever
+        // possible, 2 auto.
+        const uint64_t pair_mode = env_u64("ECDNA_SSA_PAIR", 2);
+        const bool pair_ok = p.process == ECDNA_BIRTH_DEATH && p.n_snapshots == 0 &&
+                             ecdna::bin_stepper_kernel_pair(p.segregation, c->bin_k, c->bin_c32, kflags) != nullptr;
+        c->bin_ilp = bin_schedule_rule(pair_ok, pair_mode, sched, max_chunk, c->cus, k64u16, tf0, occ_def, occ_ilp,
+                                       c->stepper_block);
+        // bin store: LDS-resident events, bounded by issue and LDS latency: every resident block helps
+        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu,
+            ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kflags, c->bin_ilp),
+            (int)c->stepper_block, 0));
+    } else {
+        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+            &per_cu, ecdna::stepper_kernel(p.process, p.segregation, c->window, kernel_flags(*c)), ecdna::kStepperBlock, 0));
+        // Memory-level parallelism of the random row accesses saturates HBM at about 3 resident 256-lane
+        // blocks per CU (C3 sweep, DESIGN.md §8: 1/2/3/4/7 blocks -> 617/372/329/336/349 ms); fewer
+        // lanes also mean more replicates per lane and a shorter drain once the work queue is empty.
+        per_cu = std::min(per_cu, 3);
+    }
+    uint64_t bpc = env_u64("ECDNA_SSA_BLOCKS_PER_CU", 0);
+    if (bpc) per_cu = (int)bpc;
+    if (per_cu < 1) per_cu = 1;
+    c->stepper_blocks_cap = (uint32_t)(per_cu * c->cus);
+    if (p.max_workgroups) c->stepper_blocks_cap = std::min(c->stepper_blocks_cap, p.max_workgroups);
+    uint64_t max_blocks = env_u64("ECDNA_SSA_MAX_BLOCKS", 0);  // testing: force lane refill
+    if (max_blocks) c->stepper_blocks_cap = (uint32_t)std::min<uint64_t>(c->stepper_blocks_cap, max_blocks);
+    return ECDNA_OK;
+}
+
+// Replicate rotation (bin store, 256-lane blocks): on when lanes have at least three
+// replicates each (ECDNA_SSA_ROTATE = 0 off, 1 on whenever possible, 2 auto); with two (C4 8-GPU shard)
+// the drain control is faster (74 ms against 84). Auto also leaves it off when the caller gave a cost
+// hint: the costliest-first start order then already balances the lanes, and parking only mixes the
+// order up again (C4 whole sweep, same box: 710-718 ms without rotation against 738-750 with it under
+// the 128-VGPR build, 747-749 against 792-805 under the default one). Results do not depend on it.
+// Byte offsets into bags/park are u32 in the kernel: chunks stay below 2 GiB of either.
+int plan_rotation(ecdna_ssa_ctx* c) {
+    uint64_t rot_mode = env_u64("ECDNA_SSA_ROTATE", 2);
+    const bool hinted = c->d_order != nullptr;
+    // Rotation hands a parked replicate only to lanes of the same partition, partition = XCC id mod
+    // kRotParts, and relies on those lanes sharing one L2 (the parked state is read with L1-bypassing
+    // loads). That holds when the agent has at most kRotParts XCCs (gfx950 SPX: 8, CPX: 1); otherwise
+    // two L2s would share a partition, so rotation stays off.
+    {
+        int xccs = 0;
+        if (hipDeviceGetAttribute(&xccs, hipDeviceAttributeNumberOfXccs, c->device) != hipSuccess || xccs < 1 ||
+            xccs > (int)ecdna::kRotParts)
+            rot_mode = 0;
+    }
+    c->rot_tick_log2 = (uint32_t)std::min<uint64_t>(env_u64("ECDNA_SSA_ROT_TICK", 10), 30);
+    bool any_rot = false;
+    for (auto& ch : c->chunks) {
+        const uint64_t need = (ch.n + c->stepper_block - 1) / c->stepper_block;
+        const uint64_t lanes = std::max<uint64_t>(1, std::min<uint64_t>(need, c->stepper_blocks_cap)) * c->stepper_block;
+        const bool ok = c->bin_k && c->stepper_block == ecdna::kStepperBlock &&
+                        (uint64_t)ch.n * std::max<uint64_t>(bag_bytes(c), ecdna::kParkVecs * 16u) < (1ull << 31);
+        if (!ok || rot_mode == 0 || (rot_mode == 2 && (ch.n < 3 * lanes || hinted))) continue;
+        const uint32_t per = (ch.n + ecdna::kRotParts - 1) / ecdna::kRotParts;
+        ch.rot_n_pad = (per + ecdna::kRotBlock - 1) / ecdna::kRotBlock * ecdna::kRotBlock;
+        ch.rot_init.assign(ecdna::kRotParts, ecdna::RotPart{});
+        for (uint32_t x = 0; x < ecdna::kRotParts; ++x) {
+            const int cnt = x < ch.n ? (int)((ch.n - x + ecdna::kRotParts - 1) / ecdna::kRotParts) : 0;  // r = x mod 8
+            ch.rot_init[x].waiting = cnt;
+            ch.rot_init[x].fresh = cnt;
+        }
+        any_rot = true;
+    }
+    if (any_rot) {
+        const uint64_t n_pad_max = (c->chunk_reps + ecdna::kRotParts - 1) / ecdna::kRotParts + ecdna::kRotBlock;
+        TRY(ctx_alloc(c, &c->d_rot_parts, ecdna::kRotParts));
+        TRY(ctx_alloc(c, &c->d_rot_flags, ecdna::kRotParts * n_pad_max));
+        TRY(ctx_alloc(c, &c->d_rot_park, c->chunk_reps * ecdna::kParkVecs));
+        // park only while at least 1.5 partition grids' worth of replicates wait; below that the lanes run
+        // their replicates to the end (C3 sweep, DESIGN.md §5: 0.5 / 1 / 2 / 3 grids -> 88.2 / 87.2 / 87.1 / 97.5 ms)
+        const uint64_t lanes_all = (uint64_t)c->stepper_blocks_cap * c->stepper_block;
+        c->rot_park_min = (int32_t)env_u64("ECDNA_SSA_ROT_PARK_MIN",
+                                           std::max<uint64_t>(1, lanes_all * 3 / 2 / ecdna::kRotParts));
+    }
+    return ECDNA_OK;
+}
+
+// grid and drain control per chunk. Drain control (bin store, 256-lane blocks, one wave per SIMD per block):
+// when lanes run more than two replicates each, the youngest wave slot of every SIMD stops taking fresh
+// replicates once fewer than 1.5 grids' worth are left (C3: 105 -> 101 ms). ECDNA_SSA_ADMIT=0:
+// off. Rotation replaces it.
+void plan_drain_control(ecdna_ssa_ctx* c) {
+    for (auto& ch : c->chunks) {
+        // (paired lanes: owners only)
+        const uint32_t per_block = c->bin_ilp == 3 ? c->stepper_block / 2 : c->stepper_block;
+        const uint32_t need = (ch.n + per_block - 1) / per_block;
+        ch.blocks = std::max<uint32_t>(1, std::min<uint32_t>(need, c->stepper_blocks_cap));
+        const uint64_t lanes = (uint64_t)ch.blocks * c->stepper_block;
+        const uint32_t per_cu = c->cus ? (uint32_t)((ch.blocks + c->cus - 1) / c->cus) : 0u;
+        if (!ch.rot_n_pad && c->bin_k && c->stepper_block == 256 && per_cu >= 2 && ch.n > 2 * lanes &&
+            env_u64("ECDNA_SSA_ADMIT", 1)) {
+            const uint32_t slots = (uint32_t)std::min<uint64_t>(env_u64("ECDNA_SSA_ADMIT_SLOTS", 1), per_cu - 1);
+            ch.admit_slot = per_cu - std::max<uint32_t>(slots, 1u);
+            const uint64_t x8 = env_u64("ECDNA_SSA_ADMIT_X8", 12);  // eighths of a grid (tuning)
+            ch.admit_remaining = (uint32_t)std::min<uint64_t>(lanes * x8 / 8, ch.n);
+        }
+    }
+}
+
+int build_ctx(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+              const ecdna_ssa_passages_t* pas) {
+    adopt_params(c, p, ext, pas);
+    TRY(upload_inputs(c));
+    TRY(upload_targets(c, p, ext, pas));
+    TRY(alloc_outputs(c));
+    TRY(plan_chunks(c, p->set_cost_hint));
+    TRY(plan_stepper_grid(c));
+    TRY(plan_rotation(c));
+    plan_drain_control(c);
+    return ECDNA_OK;
+}
+
+// ---- ecdna_ssa_ctx_launch, piece by piece: per chunk k and growth phase g (one in an ordinary run) the stepper, the
+// histogram pass and the sampling passes the run asks for, in this order on the stream ----
+
+ecdna::StepperArgs stepper_args(const ecdna_ssa_ctx* c, const Chunk& ch, size_t k, uint32_t g) {
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t n_run = std::max<uint64_t>(p.n_replicates, 1);
+    ecdna::StepperArgs a{};
+    a.rows = c->d_rows;
+    a.summaries = (c->n_passages ? c->d_pas_summ + g * n_run : c->d_summ) + ch.first;
+    a.head = c->d_heads + k;
+    a.order = c->d_order ? c->d_order + ch.first : nullptr;
+    a.rates = c->d_rates;
+    a.init_copies = c->d_init;
+    a.init_offsets = c->d_init_off;
+    a.init_nminus_set = c->d_init_nm;
+    a.row_stride = c->row_stride;
+    a.seed = passage_seed(p.seed, g);  // (an ordinary run: the seed)
+    if (g > 0) {  // started from the founders the previous phase's sample left
+        a.founder_rows = c->d_founder_rows;
+        a.founder_counts = c->d_founder_counts;
+        a.founder_stride = c->founder_stride;
+    }
+    const uint64_t stride = p.replicate_stride ? p.replicate_stride : 1u;
+    a.rid0 = p.first_replicate + ch.first * stride;
+    a.rid_stride = stride;
+    a.reps_per_set = p.reps_per_set;
+    a.max_cells = p.max_cells;
+    a.init_nminus = p.init_nminus;
+    a.max_time = p.max_time;
+    a.max_time32 = (float)p.max_time;
+    a.n = ch.n;
+    a.init_nplus = p.init_nplus;
+    a.max_iter = (uint32_t)p.max_iter;
+    a.cell_cap = p.cell_cap;
+    a.flags = kernel_flags(*c);  // (with the internal bits: they select the kernel instance)
+    // (n- + n+) * 2 >= max_cells  <=>  n- + n+ >= ceil(max_cells / 2)
+    a.stop_cells = (p.process == ECDNA_BIRTH_DEATH && (p.flags & ECDNA_FLAG_BD_CAP_COMPAT))
+                       ? p.max_cells / 2 + (p.max_cells & 1)
+                       : p.max_cells;
+    a.n_snap = p.n_snapshots;
+    a.snap_cells = c->d_snap_cells;
+    a.snap_meta = c->d_snap_meta ? c->d_snap_meta + ch.first * p.n_snapshots : nullptr;
+    // (the run's rows at the chunk's offset, or the chunk's scratch)
+    a.snap_rows = c->d_snap_rows;
+    if (a.snap_rows && !c->snap_rows_local) a.snap_rows += ch.first * p.n_snapshots * c->out_stride;
+    a.snap_stride = c->out_stride;
+    a.big_cap = c->big_cap;
+    a.bags = c->d_bags;
+    a.admit_slot = ch.admit_slot;  // (drain control, decided at create)
+    a.admit_remaining = ch.admit_remaining;
+    if (ch.rot_n_pad) {  // rotation replaces the drain control
+        a.rot_parts = c->d_rot_parts;
+        a.rot_flags = c->d_rot_flags;
+        a.rot_park = c->d_rot_park;
+        a.rot_n_pad = ch.rot_n_pad;
+        a.rot_tick_log2 = c->rot_tick_log2;
+        a.rot_park_min = c->rot_park_min;
+    }
+    a.ref_key = c->d_ref_key;
+    a.ref_btpe = c->d_ref_btpe;
+    a.rng_words = c->d_rng_words ? c->d_rng_words + ch.first : nullptr;
+    return a;
+}
+
+// The rotation state of a chunk, as every stepper launch finds it: all its replicates fresh, the padding done.
+int reset_rotation(const ecdna_ssa_ctx* c, const Chunk& ch, hipStream_t st) {
+    const uint64_t n_flags = (uint64_t)ecdna::kRotParts * ch.rot_n_pad;
+    TRY(hipMemsetD32Async(c->d_rot_flags, ecdna::ROT_FRESH, ch.n, st));
+    if (n_flags > ch.n) TRY(hipMemsetD32Async(c->d_rot_flags + ch.n, ecdna::ROT_DONE, n_flags - ch.n, st));
+    TRY(hipMemcpyAsync(c->d_rot_parts, ch.rot_init.data(), ecdna::kRotParts * sizeof(ecdna::RotPart),
+                       hipMemcpyHostToDevice, st));
+    return ECDNA_OK;
+}
+
+// The target phase g is scored against: its own (a passage run with passage_target_hists), else the run's.
+ecdna::StatsTarget phase_target(const ecdna_ssa_ctx* c, uint32_t g) {
+    if (!c->n_passages || !c->d_pas_target_cdf) return c->target;
+    const double* sc = c->pas_target_scalars.data() + 3 * g;
+    return {c->d_pas_target_cdf + (uint64_t)g * c->p.hist_bins, sc[0], sc[1], sc[2], 1u};
+}
+
+// A workgroup's share of the chunk's n replicates in an end-of-run pass: the chunk over eight workgroups per CU, at
+// least `floor`. (Eight per CU for either histogram pass: one per CU made the bin store's lane-per-replicate pass no
+// faster at C3, 0.29 -> 0.30 ms, and C4's 1,024 sets 5 -> 28 ms, each workgroup walking more sets. The sampling
+// passes run one wave per population: at least one per wave of the workgroup, at most the histogram pass's share,
+// which bounds the sets a workgroup walks.)
+uint32_t pass_reps_per_block(const ecdna_ssa_ctx* c, uint32_t n, uint32_t floor) {
+    const uint32_t hist_blocks_max = (uint32_t)c->cus * 8u;
+    return std::max<uint32_t>(floor, (n + hist_blocks_max - 1) / hist_blocks_max);
+}
+uint32_t pass_blocks(const ecdna::ChunkIds& ids) { return (ids.n + ids.reps_per_block - 1) / ids.reps_per_block; }
+
+ecdna::HistArgs hist_args(const ecdna_ssa_ctx* c, const Chunk& ch, uint32_t g, const ecdna::FinalState& fs,
+                          ecdna::ChunkIds ids, const ecdna::StatsTarget& target) {
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t nb = (uint64_t)p.n_param_sets * p.hist_bins, n_run = std::max<uint64_t>(p.n_replicates, 1);
+    const bool pas = c->n_passages != 0;
+    ecdna::HistArgs h{};
+    h.rows = fs.rows;
+    h.summaries = fs.summaries;
+    h.row_stride = fs.row_stride;
+    h.bags = fs.bags;
+    h.bag_k = fs.bag_k;
+    h.bag_c32 = fs.bag_c32;
+    h.hist = pas ? c->d_pas_hist + g * nb : c->d_hist;
+    h.totals = reinterpret_cast<unsigned long long*>(pas ? c->d_pas_tot + (uint64_t)g * p.n_param_sets : c->d_tot);
+    // at least one replicate per lane of a workgroup, or the chunk's replicates of one parameter set if fewer: small
+    // runs otherwise spread over 2,048 workgroups of mostly idle waves, each adding its own nonzero bins to the
+    // same global words (C2: 0.061 -> 0.023 ms per launch at 256, 0.038 at 64, 0.052 at 1,024;
+    // profiles/r06ak_hist_rpb.txt); sweeps of small sets keep about one set per workgroup
+    const uint64_t set_local = std::max<uint64_t>(1, p.reps_per_set / ids.rid_stride);
+    ids.reps_per_block = pass_reps_per_block(
+        c, ch.n, (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(ecdna::kHistBlock, set_local)));
+    h.ids = ids;
+    h.stats = pas ? c->d_pas_stats + g * n_run + ch.first : (c->d_stats ? c->d_stats + ch.first : nullptr);
+    h.target = target;
+    return h;
+}
+
+// the samples' statistics and histogram, from the same final state
+int launch_subsample_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::FinalState& fs, ecdna::ChunkIds ids,
+                          const ecdna::StatsTarget& target, hipStream_t st) {
+    ecdna::SubsampleArgs sa{};
+    sa.state = fs;
+    sa.target = target;
+    sa.stats = c->d_sample_stats + ch.first;
+    sa.sample_hist = c->d_sample_hist;
+    sa.seed = c->p.seed;
+    sa.m = c->p.subsample_cells;
+    sa.table_slots = ecdna::subsample_table_slots(sa.m);
+    ids.reps_per_block =
+        pass_reps_per_block(c, ch.n, ecdna::subsample_waves(ids.bins, fs.bag_k, sa.table_slots, nullptr));
+    sa.ids = ids;
+    TRY(ecdna::launch_subsample(sa, pass_blocks(ids), st));
+    return ECDNA_OK;
+}
+
+// phase g's measurement, and (but for the last phase) the founders of the next
+int launch_passage_pass(const ecdna_ssa_ctx* c, const Chunk& ch, uint32_t g, const ecdna::FinalState& fs,
+                        ecdna::ChunkIds ids, const ecdna::StatsTarget& target, uint64_t seed_g, hipStream_t st) {
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t nb = (uint64_t)p.n_param_sets * p.hist_bins, n_run = std::max<uint64_t>(p.n_replicates, 1);
+    ecdna::PassageArgs pa{};
+    pa.state = fs;
+    pa.target = target;
+    pa.stats = c->d_pas_sample_stats + g * n_run + ch.first;
+    pa.sample_hist = c->d_pas_sample_hist + g * nb;
+    pa.founder_rows = g + 1u < c->n_passages ? c->d_founder_rows : nullptr;
+    pa.founder_counts = c->d_founder_counts;
+    pa.founder_stride = c->founder_stride;
+    pa.seed = seed_g;
+    pa.m = c->passage_m;
+    pa.table_slots = ecdna::subsample_table_slots(pa.m);
+    pa.sort_slots = ecdna::passage_sort_slots(pa.m);
+    ids.reps_per_block = pass_reps_per_block(
+        c, ch.n, ecdna::passage_waves(ids.bins, fs.bag_k, pa.table_slots, pa.sort_slots, nullptr));
+    pa.ids = ids;
+    TRY(ecdna::launch_passage(pa, pass_blocks(ids), st));
+    return ECDNA_OK;
+}
+
+// the statistics of the chunk's snapshots, from the rows the stepper just saved
+int launch_snapstats_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::StepperArgs& a, ecdna::ChunkIds ids,
+                          hipStream_t st) {
+    const ecdna_ssa_params_t& p = c->p;
+    ecdna::SnapStatsArgs ta{};
+    ta.snap_meta = a.snap_meta;
+    ta.snap_rows = a.snap_rows;
+    ta.stats = c->d_snap_stats + ch.first * p.n_snapshots;
+    ta.sample_stats = c->d_snap_sample_stats ? c->d_snap_sample_stats + ch.first * p.n_snapshots : nullptr;
+    ta.hist = c->d_snap_hist;
+    ta.sample_hist = c->d_snap_sample_hist;
+    ta.target_cdf = c->d_snap_target_cdf;
+    ta.target_scalars = c->d_snap_target_scalars;
+    ta.snap_stride = a.snap_stride;
+    ta.seed = p.seed;
+    ta.n_snap = p.n_snapshots;
+    ta.n_sets = p.n_param_sets;
+    ta.m = c->snap_m;
+    ta.table_slots = c->snap_m ? ecdna::subsample_table_slots(c->snap_m) : 0u;
+    ids.reps_per_block =
+        pass_reps_per_block(c, ch.n, ecdna::snapstats_waves(ids.bins, ta.table_slots, nullptr, nullptr));
+    ta.ids = ids;
+    TRY(ecdna::launch_snapstats(ta, pass_blocks(ids), st));
+    return ECDNA_OK;
+}
+
+// One growth phase of one chunk.
+int launch_chunk_phase(ecdna_ssa_ctx* c, size_t k, uint32_t g, hipStream_t st) {
+    const ecdna_ssa_params_t& p = c->p;
+    const Chunk& ch = c->chunks[k];
+    const hipEvent_t* ev = ch.ev.data() + 3u * g;
+    // the chunk's work counter starts every phase at zero (the rotation state is reset below, per launch)
+    if (g > 0) TRY(hipMemsetAsync(c->d_heads + k, 0, sizeof(uint32_t), st));
+    const ecdna::StepperArgs a = stepper_args(c, ch, k, g);
+    if (ch.rot_n_pad) TRY(reset_rotation(c, ch, st));
+    TRY(hipEventRecord(ev[0], st));
+    if (c->refdraws)
+        TRY(ecdna::launch_refdraws(a, p.process, p.segregation, ch.blocks, st));
+    else if (c->bin_k)
+        TRY(ecdna::launch_bin_stepper(a, p.process, p.segregation, c->bin_k, c->bin_c32, c->bin_ilp, ch.blocks, st));
+    else
+        TRY(ecdna::launch_stepper(a, p.process, p.segregation, c->window, ch.blocks, st));
+    TRY(hipEventRecord(ev[1], st));
+
+    // what the passes share, filled once: the final state, the chunk's ids, the phase's target
+    const ecdna::FinalState fs{c->d_rows, a.summaries, c->row_stride, c->d_bags, c->bin_k, (uint32_t)c->bin_c32};
+    const ecdna::ChunkIds ids{a.rid0, a.rid_stride, a.reps_per_set, ch.n, p.hist_bins, 0u};  // (reps_per_block: per pass)
+    const ecdna::StatsTarget target = phase_target(c, g);
+    const ecdna::HistArgs h = hist_args(c, ch, g, fs, ids, target);
+    TRY(ecdna::launch_hist(h, pass_blocks(h.ids), st));
+    if (p.subsample_cells) TRY(launch_subsample_pass(c, ch, fs, ids, target, st));
+    if (c->n_passages) TRY(launch_passage_pass(c, ch, g, fs, ids, target, a.seed, st));
+    if (c->snap_stats) TRY(launch_snapstats_pass(c, ch, a, ids, st));
+    TRY(hipEventRecord(ev[2], st));
+    return ECDNA_OK;
+}
 }  // namespace
 
 // library-internal entry points for ssa_comm.cpp (the RCCL reduction)
@@ -441,8 +1037,7 @@ __attribute__((visibility("hidden"))) int ecdna_ssa_internal_fail(int code, cons
 __attribute__((visibility("hidden"))) int ecdna_ssa_internal_ctx_outputs(ecdna_ssa_ctx* c, uint64_t** d_hist,
                                                                          ecdna_totals_t** d_tot, uint32_t* n_sets,
                                                                          uint32_t* bins, int* device, void** stream) {
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!c->launched) return fail(ECDNA_E_STATE, "reduce before launch");
+    TRY(ctx_launched(c, "reduce before launch"));
     *d_hist = c->d_hist;
     *d_tot = c->d_tot;
     *n_sets = c->p.n_param_sets;
@@ -461,6 +1056,23 @@ int ecdna_dev_bin_schedule(int pair_ok, uint64_t pair_mode, uint64_t sched, uint
                            int k64u16, int tf0, int occ_def, int occ_ilp, uint32_t stepper_block) {
     return bin_schedule_rule(pair_ok != 0, pair_mode, sched, max_chunk, cus, k64u16 != 0, tf0 != 0, occ_def, occ_ilp,
                              stepper_block);
+}
+
+// (development / test entry point, not part of include/ecdna_ssa.h: the sampling passes' LDS plan of ssa_launch.h for
+// the CPU tests. pass 0 = ssa_subsample, 1 = ssa_passage, 2 = ssa_snapstats, where m = 0 means no samples)
+int ecdna_dev_pass_lds(int pass, uint32_t bins, uint32_t bag_k, uint32_t m, uint32_t* waves, uint64_t* lds_bytes,
+                       int* sample_hist_lds) {
+    if (pass < 0 || pass > 2 || (!m && pass != 2) || !waves || !lds_bytes || !sample_hist_lds)
+        return fail(ECDNA_E_INVALID, "ecdna_dev_pass_lds: unknown pass, m = 0 outside pass 2, or a NULL output");
+    const uint32_t slots = m ? ecdna::subsample_table_slots(m) : 0u;
+    size_t lds = 0;
+    bool in_lds = false;
+    *waves = pass == 0   ? ecdna::subsample_waves(bins, bag_k, slots, &lds)
+             : pass == 1 ? ecdna::passage_waves(bins, bag_k, slots, ecdna::passage_sort_slots(m), &lds)
+                         : ecdna::snapstats_waves(bins, slots, &lds, &in_lds);
+    *lds_bytes = lds;
+    *sample_hist_lds = in_lds ? 1 : 0;
+    return ECDNA_OK;
 }
 
 const char* ecdna_ssa_strerror(int code) {
@@ -502,386 +1114,15 @@ int ecdna_ssa_ctx_create_passages(const ecdna_ssa_params_t* p, const ecdna_ssa_e
                                   const ecdna_ssa_passages_t* pas, ecdna_ssa_ctx** out) {
     if (!out) return fail(ECDNA_E_INVALID, "out is NULL");
     *out = nullptr;
-    int rc = validate(p, ext, pas);
-    if (rc) return rc;
-    rc = pick_device(p->device);
-    if (rc) return rc;
-
+    TRY(validate(p, ext, pas));
+    TRY(pick_device(p->device));
     ecdna_ssa_ctx* c = new ecdna_ssa_ctx();
-    c->p = *p;
-    c->device = p->device;
-    if (pas) {
-        c->n_passages = pas->n_passages;
-        c->passage_m = pas->passage_cells;
-        c->founder_stride = round_up(pas->passage_cells, 64);
-    }
-    // own copies of host inputs
-    c->rates.assign(p->rates, p->rates + p->n_param_sets);
-    uint64_t n_init = p->init_set_offsets ? p->init_set_offsets[p->n_param_sets] : p->init_nplus;
-    c->init_copies.assign(p->init_copies ? p->init_copies : nullptr,
-                          p->init_copies ? p->init_copies + n_init : nullptr);
-    if (c->init_copies.empty()) c->init_copies.push_back(1);
-    if (p->init_set_offsets) c->init_offsets.assign(p->init_set_offsets, p->init_set_offsets + p->n_param_sets + 1);
-    if (p->init_set_nminus) c->init_nminus_set.assign(p->init_set_nminus, p->init_set_nminus + p->n_param_sets);
-    if (p->n_snapshots) c->snap_cells.assign(p->snapshot_cells, p->snapshot_cells + p->n_snapshots);
-    c->p.snapshot_cells = nullptr;
-    c->p.rates = nullptr;
-    c->p.init_copies = nullptr;
-    c->p.init_set_offsets = nullptr;
-    c->p.init_set_nminus = nullptr;
-
-    auto bail = [&](int code) {
+    if (int rc = build_ctx(c, p, ext, pas)) {
         free_ctx(c);
-        return code;
-    };
-#define CTX_TRY(expr)                                                                                \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess)                                                                        \
-            return bail(fail(_e == hipErrorOutOfMemory ? ECDNA_E_NOMEM : ECDNA_E_HIP,                \
-                             std::string(#expr) + ": " + hipGetErrorString(_e)));                     \
-    } while (0)
-
-    hipDeviceProp_t prop;
-    CTX_TRY(hipGetDeviceProperties(&prop, c->device));
-    c->cus = prop.multiProcessorCount;
-
-    // inputs
-    std::vector<float4> r4(p->n_param_sets);
-    for (uint32_t s = 0; s < p->n_param_sets; ++s)
-        r4[s] = make_float4(p->rates[s].b0, p->rates[s].b1, p->rates[s].d0, p->rates[s].d1);
-    CTX_TRY(hipMalloc(&c->d_rates, r4.size() * sizeof(float4)));
-    CTX_TRY(hipMemcpy(c->d_rates, r4.data(), r4.size() * sizeof(float4), hipMemcpyHostToDevice));
-    CTX_TRY(hipMalloc(&c->d_init, c->init_copies.size() * sizeof(uint16_t)));
-    CTX_TRY(hipMemcpy(c->d_init, c->init_copies.data(), c->init_copies.size() * sizeof(uint16_t),
-                      hipMemcpyHostToDevice));
-    if (!c->init_offsets.empty()) {
-        CTX_TRY(hipMalloc(&c->d_init_off, c->init_offsets.size() * sizeof(uint32_t)));
-        CTX_TRY(hipMemcpy(c->d_init_off, c->init_offsets.data(), c->init_offsets.size() * sizeof(uint32_t),
-                          hipMemcpyHostToDevice));
-    }
-    if (!c->init_nminus_set.empty()) {
-        CTX_TRY(hipMalloc(&c->d_init_nm, c->init_nminus_set.size() * sizeof(uint64_t)));
-        CTX_TRY(hipMemcpy(c->d_init_nm, c->init_nminus_set.data(), c->init_nminus_set.size() * sizeof(uint64_t),
-                          hipMemcpyHostToDevice));
-    }
-
-    if (!c->snap_cells.empty()) {
-        CTX_TRY(hipMalloc(&c->d_snap_cells, c->snap_cells.size() * sizeof(uint64_t)));
-        CTX_TRY(hipMemcpy(c->d_snap_cells, c->snap_cells.data(), c->snap_cells.size() * sizeof(uint64_t),
-                          hipMemcpyHostToDevice));
-    }
-
-    // ABC statistics: the target's CDF over the bins and its mean / entropy / N+ frequency (the overflow bin
-    // counts at k = bins - 1), computed once on the host
-    if ((p->flags & ECDNA_FLAG_REP_STATS) && p->n_replicates) {
-        CTX_TRY(hipMalloc(&c->d_stats, p->n_replicates * sizeof(ecdna_rep_stats_t)));
-        if (p->stats_target_hist) {
-            const uint32_t bins = p->hist_bins;
-            double tot = 0.0;
-            for (uint32_t b = 0; b < bins; ++b) tot += (double)p->stats_target_hist[b];
-            if (!(tot > 0.0)) return bail(fail(ECDNA_E_INVALID, "stats_target_hist is empty"));
-            std::vector<double> cdf(bins);
-            target_summary(p->stats_target_hist, bins, tot, cdf.data(), &c->target_mean, &c->target_entropy,
-                           &c->target_freq);
-            c->has_target = true;
-            CTX_TRY(hipMalloc(&c->d_target_cdf, bins * sizeof(double)));
-            CTX_TRY(hipMemcpy(c->d_target_cdf, cdf.data(), bins * sizeof(double), hipMemcpyHostToDevice));
-        }
-    }
-    c->p.stats_target_hist = nullptr;
-
-    // outputs
-    const uint64_t n = p->n_replicates;
-    const uint64_t nb = (uint64_t)p->n_param_sets * p->hist_bins;
-    if (p->subsample_cells) {
-        CTX_TRY(hipMalloc(&c->d_sample_stats, std::max<uint64_t>(n, 1) * sizeof(ecdna_rep_stats_t)));
-        CTX_TRY(hipMalloc(&c->d_sample_hist, nb * sizeof(uint64_t)));
-    }
-    if (pas) {  // every phase's outputs, sized G x run; the last phase's are copied into the ordinary buffers
-        const uint64_t G = pas->n_passages, n1 = std::max<uint64_t>(n, 1);
-        const uint32_t bins = p->hist_bins;
-        CTX_TRY(hipMalloc(&c->d_sample_stats, n1 * sizeof(ecdna_rep_stats_t)));
-        CTX_TRY(hipMalloc(&c->d_sample_hist, nb * sizeof(uint64_t)));
-        CTX_TRY(hipMalloc(&c->d_pas_summ, G * n1 * sizeof(ecdna_rep_summary_t)));
-        CTX_TRY(hipMalloc(&c->d_pas_stats, G * n1 * sizeof(ecdna_rep_stats_t)));
-        CTX_TRY(hipMalloc(&c->d_pas_sample_stats, G * n1 * sizeof(ecdna_rep_stats_t)));
-        CTX_TRY(hipMalloc(&c->d_pas_hist, G * nb * sizeof(uint64_t)));
-        CTX_TRY(hipMalloc(&c->d_pas_sample_hist, G * nb * sizeof(uint64_t)));
-        CTX_TRY(hipMalloc(&c->d_pas_tot, G * p->n_param_sets * sizeof(ecdna_totals_t)));
-        if (pas->passage_target_hists) {  // phase g's own target
-            std::vector<double> cdf(G * bins);
-            c->pas_target_scalars.assign(G * 3, 0.0);
-            for (uint64_t g = 0; g < G; ++g) {
-                const uint64_t* t = pas->passage_target_hists + g * bins;
-                double tot = 0.0;
-                for (uint32_t b = 0; b < bins; ++b) tot += (double)t[b];
-                double* sc = c->pas_target_scalars.data() + 3 * g;
-                target_summary(t, bins, tot, cdf.data() + g * bins, sc, sc + 1, sc + 2);
-            }
-            CTX_TRY(hipMalloc(&c->d_pas_target_cdf, cdf.size() * sizeof(double)));
-            CTX_TRY(hipMemcpy(c->d_pas_target_cdf, cdf.data(), cdf.size() * sizeof(double), hipMemcpyHostToDevice));
-        }
-    }
-    // per-snapshot statistics: sized by the run (the snapshot rows they are computed from may be one chunk's, below)
-    c->snap_stats = ext && ext->snapshot_stats;
-    if (c->snap_stats) {
-        const uint64_t S = p->n_snapshots;
-        const uint64_t stats_bytes = std::max<uint64_t>(n, 1) * S * sizeof(ecdna_rep_stats_t);
-        c->snap_m = ext->snapshot_subsample_cells;
-        CTX_TRY(hipMalloc(&c->d_snap_stats, stats_bytes));
-        CTX_TRY(hipMalloc(&c->d_snap_hist, S * nb * sizeof(uint64_t)));
-        if (c->snap_m) {
-            CTX_TRY(hipMalloc(&c->d_snap_sample_stats, stats_bytes));
-            CTX_TRY(hipMalloc(&c->d_snap_sample_hist, S * nb * sizeof(uint64_t)));
-        }
-        if (ext->snapshot_target_hists) {
-            const uint32_t bins = p->hist_bins;
-            std::vector<double> cdf(S * bins), scal(S * 3);
-            for (uint64_t q = 0; q < S; ++q) {
-                const uint64_t* t = ext->snapshot_target_hists + q * bins;
-                double tot = 0.0;
-                for (uint32_t b = 0; b < bins; ++b) tot += (double)t[b];
-                target_summary(t, bins, tot, cdf.data() + q * bins, &scal[3 * q], &scal[3 * q + 1], &scal[3 * q + 2]);
-            }
-            CTX_TRY(hipMalloc(&c->d_snap_target_cdf, cdf.size() * sizeof(double)));
-            CTX_TRY(hipMemcpy(c->d_snap_target_cdf, cdf.data(), cdf.size() * sizeof(double), hipMemcpyHostToDevice));
-            CTX_TRY(hipMalloc(&c->d_snap_target_scalars, scal.size() * sizeof(double)));
-            CTX_TRY(hipMemcpy(c->d_snap_target_scalars, scal.data(), scal.size() * sizeof(double),
-                              hipMemcpyHostToDevice));
-        }
-    }
-    CTX_TRY(hipMalloc(&c->d_hist_own, nb * sizeof(uint64_t)));
-    CTX_TRY(hipMalloc(&c->d_tot_own, p->n_param_sets * sizeof(ecdna_totals_t)));
-    CTX_TRY(hipMemset(c->d_hist_own, 0, nb * sizeof(uint64_t)));
-    CTX_TRY(hipMemset(c->d_tot_own, 0, p->n_param_sets * sizeof(ecdna_totals_t)));
-    c->d_hist = c->d_hist_own;
-    c->d_tot = c->d_tot_own;
-    CTX_TRY(hipMalloc(&c->d_summ, std::max<uint64_t>(n, 1) * sizeof(ecdna_rep_summary_t)));
-
-    c->row_stride = round_up(p->cell_cap, 64);
-    c->out_stride = c->row_stride;
-    if (p->flags & ECDNA_FLAG_BIN_STORE) {
-        c->big_cap = (p->big_cap && p->big_cap < p->cell_cap) ? p->big_cap : p->cell_cap;
-        c->row_stride = round_up(c->big_cap, 64);
-        c->bin_k = p->bin_kmax ? p->bin_kmax : 64;
-        // u16 counters hold at most 65535 cells per bin/group; K = 32 always uses u32 counters: the same LDS
-        // footprint as K = 64/u16 (144 B per lane), no 16-bit packing in the updates and the scan (C3:
-        // 119 ms against 126 ms with u16, DESIGN.md §8)
-        // (ECDNA_SSA_C32 = 1 forces u32 counters at any K: a development knob, results are the same)
-        c->bin_c32 = (p->cell_cap > 65535u || c->bin_k <= 32 || env_u64("ECDNA_SSA_C32", 0)) ? 1 : 0;
-        c->stepper_block = (uint32_t)ecdna::bin_stepper_block(c->bin_k);
-    }
-    const uint64_t bag_bytes = (uint64_t)c->bin_k * (c->bin_c32 ? 4u : 2u);
-    if (p->n_snapshots && n) {  // snapshot outputs cover the whole run (not chunked)
-        CTX_TRY(hipMalloc(&c->d_snap_meta, n * p->n_snapshots * sizeof(ecdna_snapshot_t)));
-        if (p->flags & ECDNA_FLAG_SNAPSHOT_ROWS)
-            CTX_TRY(hipMalloc(&c->d_snap_rows, n * p->n_snapshots * c->out_stride * sizeof(uint16_t)));
-    }
-
-    // rows: one u16 row per replicate of the chunk; chunk bounded by free HBM
-    const uint64_t rot_bytes = c->bin_k ? ecdna::kParkVecs * 16u + 4u : 0u;  // parked scalars + state word
-    // (snapshot statistics without ECDNA_FLAG_SNAPSHOT_ROWS: the snapshot rows are the chunk's scratch, n_snapshots
-    // rows of out_stride cells per replicate of the chunk, so a large run chunks instead of failing)
-    c->snap_rows_local = c->snap_stats && !c->d_snap_rows;
-    const uint64_t snap_row_bytes = c->snap_rows_local ? p->n_snapshots * c->out_stride * sizeof(uint16_t) : 0u;
-    // (a passage run: the chunk's founders, one row of passage_cells and {n-, n+} per replicate)
-    const uint64_t founder_bytes = c->n_passages ? c->founder_stride * sizeof(uint16_t) + sizeof(uint2) : 0u;
-    const uint64_t row_bytes =
-        c->row_stride * sizeof(uint16_t) + bag_bytes + rot_bytes + snap_row_bytes + founder_bytes;
-    size_t free_b = 0, total_b = 0;
-    CTX_TRY(hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = (uint64_t)((double)free_b * 0.85);
-    uint64_t cap_budget = env_u64("ECDNA_SSA_MAX_ROW_BYTES", 0);
-    if (cap_budget) budget = std::min<uint64_t>(budget, cap_budget);
-    uint64_t fit = budget / row_bytes;
-    uint64_t max_chunk = env_u64("ECDNA_SSA_MAX_CHUNK", 0);
-    if (max_chunk) fit = std::min<uint64_t>(fit, max_chunk);
-    if (fit == 0) return bail(fail(ECDNA_E_NOMEM, "one replicate row does not fit in device memory"));
-    c->chunk_reps = std::min<uint64_t>(std::max<uint64_t>(n, 1), fit);
-    CTX_TRY(hipMalloc(&c->d_rows, c->chunk_reps * c->row_stride * sizeof(uint16_t)));
-    if (c->bin_k) CTX_TRY(hipMalloc(&c->d_bags, c->chunk_reps * bag_bytes));
-    if (c->snap_rows_local) CTX_TRY(hipMalloc(&c->d_snap_rows, c->chunk_reps * snap_row_bytes));
-    if (c->n_passages) {
-        CTX_TRY(hipMalloc(&c->d_founder_rows, c->chunk_reps * c->founder_stride * sizeof(uint16_t)));
-        CTX_TRY(hipMalloc(&c->d_founder_counts, c->chunk_reps * sizeof(uint2)));
-    }
-
-    const uint64_t n_chunks = n ? (n + c->chunk_reps - 1) / c->chunk_reps : 0;
-    CTX_TRY(hipMalloc(&c->d_heads, std::max<uint64_t>(n_chunks, 1) * sizeof(uint32_t)));
-    for (uint64_t k = 0; k < n_chunks; ++k) {
-        Chunk ch{};
-        ch.first = k * c->chunk_reps;
-        ch.n = (uint32_t)std::min<uint64_t>(c->chunk_reps, n - ch.first);
-        c->chunks.push_back(ch);
-        c->chunks.back().ev.assign(3u * std::max<uint32_t>(c->n_passages, 1u), nullptr);
-        for (auto& e : c->chunks.back().ev) CTX_TRY(hipEventCreate(&e));
-    }
-
-    // start order (set_cost_hint): within each chunk, replicates of costlier sets first, then by id
-    if (p->set_cost_hint && n) {
-        const uint64_t stride = p->replicate_stride ? p->replicate_stride : 1u;
-        std::vector<uint32_t> order(n);
-        for (const Chunk& ch : c->chunks) {
-            uint32_t* o = order.data() + ch.first;
-            for (uint32_t i = 0; i < ch.n; ++i) o[i] = i;
-            auto cost = [&](uint32_t i) {
-                const float v = p->set_cost_hint[(p->first_replicate + (ch.first + i) * stride) / p->reps_per_set];
-                return v == v ? v : 0.0f;  // (NaN: no preference)
-            };
-            std::stable_sort(o, o + ch.n, [&](uint32_t x, uint32_t y) { return cost(x) > cost(y); });
-        }
-        CTX_TRY(hipMalloc(&c->d_order, n * sizeof(uint32_t)));
-        CTX_TRY(hipMemcpy(c->d_order, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-
-    // persistent stepper grid: as many resident lanes as the occupancy allows
-    c->window = env_u64("ECDNA_SSA_WINDOW", 1) ? 1 : 0;
-    int per_cu = 0;
-    c->refdraws = (p->flags & ECDNA_FLAG_REFERENCE_DRAWS) != 0;
-    if (c->refdraws) {
-        uint32_t key[8];
-        chacha_key_from_u64(p->seed, key);
-        CTX_TRY(hipMalloc(&c->d_ref_key, sizeof(key)));
-        CTX_TRY(hipMemcpy(c->d_ref_key, key, sizeof(key), hipMemcpyHostToDevice));
-        std::vector<double> bt((uint64_t)32768 * kBtpeRow, 0.0);
-        for (uint64_t k = 10; k < 32768; ++k) btpe_setup(2 * k, bt.data() + k * kBtpeRow);
-        CTX_TRY(hipMalloc(&c->d_ref_btpe, bt.size() * sizeof(double)));
-        CTX_TRY(hipMemcpy(c->d_ref_btpe, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice));
-        CTX_TRY(hipMalloc(&c->d_rng_words, std::max<uint64_t>(n, 1) * sizeof(uint64_t)));
-        c->stepper_block = (uint32_t)ecdna::refdraws_block();
-        CTX_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, ecdna::refdraws_kernel(p->process, p->segregation), (int)c->stepper_block, 0));
-    } else if (c->bin_k) {
-        // Instruction schedule: with at most one wave of replicates per SIMD (every chunk within 256 lanes
-        // per CU) each wave runs alone and waits on its own dependencies, and the max-ILP schedule is faster
-        // (C2 8.6 -> 8.1 ms, C5 8-GPU shard 22.0 -> 21.1 s); with more, issue binds and the default schedule
-        // keeps 4 waves per SIMD (max-ILP: 3, C3 +8 %). The K = 64 / u16 kernel needs 130 VGPRs (3
-        // workgroups per CU); its 128-VGPR build fits 4 and pays once lanes run many replicates each (the
-        // whole C4 sweep on one GPU, 16 per lane: 834 -> 771 ms) but not with few (C4 8-GPU shard, 2 per
-        // lane: a longer drain, 127 -> 134 ms), so auto takes it from 4 replicates per lane of its grid on.
-        // ECDNA_SSA_SCHED = 0 default, 1 max-ILP, 2 auto, 3 the 128-VGPR build (K = 64 / u16; else 0).
-        uint64_t max_chunk = 0;
-        for (const auto& ch : c->chunks) max_chunk = std::max<uint64_t>(max_chunk, ch.n);
-        const uint32_t kflags = kernel_flags(*p, c->n_passages != 0);
-        const uint64_t sched = env_u64("ECDNA_SSA_SCHED", 2);
-        // (auto only without f32 time and the event hash: that variant spills 12 B at 128 VGPRs)
-        const bool k64u16 = c->bin_k == 64 && !c->bin_c32;
-        const bool tf0 = (kflags & ecdna::kRuntimeFlagMask) == 0;
-        // Where the max-ILP build keeps the default's occupancy (LDS bounds both: K = 32 / u32 and K = 64 / u32
-        // since the f32 draw mapping v6, K = 256) it is taken too: its schedule then costs no lanes (C3 78.3 ->
-        // 77.3 ms, C5 whole 31.9 -> 30.4 s, same box). With fewer than four replicates per lane of the default
-        // grid it is taken even at one workgroup per CU less (K = 64 / u16, 118 against 134 VGPRs since v6: the
-        // C4 8-GPU shard, two replicates per lane, 127 -> 119 ms), as the drain of the last replicates is
-        // latency-bound (profiles/r04d_v6_suite_and_sched_sweep.txt).
-        int occ_def = 0, occ_ilp = 0;
-        CTX_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &occ_def, ecdna::bin_stepper_kernel(p->process, p->segregation, c->bin_k, c->bin_c32, kflags, 0),
-            (int)c->stepper_block, 0));
-        CTX_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &occ_ilp, ecdna::bin_stepper_kernel(p->process, p->segregation, c->bin_k, c->bin_c32, kflags, 1),
-            (int)c->stepper_block, 0));
-        // Paired lanes (DESIGN.md §5): with at most half a wave of replicates per SIMD (the C5 8-GPU shard) the
-        // idle half of each wave computes the next event's Philox block and soft log in the N- fast-forward.
-        // Birth-death without snapshots (the fast-forward's domain). ECDNA_SSA_PAIR = 0 off, 1 whenever
-        // possible, 2 auto.
-        const uint64_t pair_mode = env_u64("ECDNA_SSA_PAIR", 2);
-        const bool pair_ok = p->process == ECDNA_BIRTH_DEATH && p->n_snapshots == 0 &&
-                             ecdna::bin_stepper_kernel_pair(p->segregation, c->bin_k, c->bin_c32, kflags) != nullptr;
-        c->bin_ilp = bin_schedule_rule(pair_ok, pair_mode, sched, max_chunk, c->cus, k64u16, tf0, occ_def, occ_ilp,
-                                       c->stepper_block);
-        // bin store: LDS-resident events, bounded by issue and LDS latency: every resident block helps
-        CTX_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu,
-            ecdna::bin_stepper_kernel(p->process, p->segregation, c->bin_k, c->bin_c32, kflags, c->bin_ilp),
-            (int)c->stepper_block, 0));
-    } else {
-        CTX_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, ecdna::stepper_kernel(p->process, p->segregation, c->window, kernel_flags(*p, c->n_passages != 0)),
-            ecdna::kStepperBlock, 0));
-        // Memory-level parallelism of the random row accesses saturates HBM at about 3 resident 256-lane
-        // blocks per CU (C3 sweep, DESIGN.md §8: 1/2/3/4/7 blocks -> 617/372/329/336/349 ms); fewer
-        // lanes also mean more replicates per lane and a shorter drain once the work queue is empty.
-        per_cu = std::min(per_cu, 3);
-    }
-    uint64_t bpc = env_u64("ECDNA_SSA_BLOCKS_PER_CU", 0);
-    if (bpc) per_cu = (int)bpc;
-    if (per_cu < 1) per_cu = 1;
-    c->stepper_blocks_cap = (uint32_t)(per_cu * c->cus);
-    if (p->max_workgroups) c->stepper_blocks_cap = std::min(c->stepper_blocks_cap, p->max_workgroups);
-    uint64_t max_blocks = env_u64("ECDNA_SSA_MAX_BLOCKS", 0);  // testing: force lane refill
-    if (max_blocks) c->stepper_blocks_cap = (uint32_t)std::min<uint64_t>(c->stepper_blocks_cap, max_blocks);
-
-    // Replicate rotation (bin store, 256-lane blocks): on when lanes have at least three
-    // replicates each (ECDNA_SSA_ROTATE = 0 off, 1 on whenever possible, 2 auto); with two (C4 8-GPU shard)
-    // the drain control is faster (74 ms against 84). Auto also leaves it off when the caller gave a cost
-    // hint: the costliest-first start order then already balances the lanes, and parking only mixes the
-    // order up again (C4 whole sweep, same box: 710-718 ms without rotation against 738-750 with it under
-    // the 128-VGPR build, 747-749 against 792-805 under the default one). Results do not depend on it.
-    // Byte offsets into bags/park are u32 in the kernel: chunks stay below 2 GiB of either.
-    uint64_t rot_mode = env_u64("ECDNA_SSA_ROTATE", 2);
-    const bool hinted = c->d_order != nullptr;
-    // Rotation hands a parked replicate only to lanes of the same partition, partition = XCC id mod
-    // kRotParts, and relies on those lanes sharing one L2 (the parked state is read with L1-bypassing
-    // loads). That holds when the agent has at most kRotParts XCCs (gfx950 SPX: 8, CPX: 1); otherwise
-    // two L2s would share a partition, so rotation stays off.
-    {
-        int xccs = 0;
-        if (hipDeviceGetAttribute(&xccs, hipDeviceAttributeNumberOfXccs, c->device) != hipSuccess || xccs < 1 ||
-            xccs > (int)ecdna::kRotParts)
-            rot_mode = 0;
-    }
-    c->rot_tick_log2 = (uint32_t)std::min<uint64_t>(env_u64("ECDNA_SSA_ROT_TICK", 10), 30);
-    bool any_rot = false;
-    for (auto& ch : c->chunks) {
-        const uint64_t need = (ch.n + c->stepper_block - 1) / c->stepper_block;
-        const uint64_t lanes = std::max<uint64_t>(1, std::min<uint64_t>(need, c->stepper_blocks_cap)) * c->stepper_block;
-        const bool ok = c->bin_k && c->stepper_block == ecdna::kStepperBlock &&
-                        (uint64_t)ch.n * std::max<uint64_t>(bag_bytes, ecdna::kParkVecs * 16u) < (1ull << 31);
-        if (!ok || rot_mode == 0 || (rot_mode == 2 && (ch.n < 3 * lanes || hinted))) continue;
-        const uint32_t per = (ch.n + ecdna::kRotParts - 1) / ecdna::kRotParts;
-        ch.rot_n_pad = (per + ecdna::kRotBlock - 1) / ecdna::kRotBlock * ecdna::kRotBlock;
-        ch.rot_init.assign(ecdna::kRotParts, ecdna::RotPart{});
-        for (uint32_t x = 0; x < ecdna::kRotParts; ++x) {
-            const int cnt = x < ch.n ? (int)((ch.n - x + ecdna::kRotParts - 1) / ecdna::kRotParts) : 0;  // r = x mod 8
-            ch.rot_init[x].waiting = cnt;
-            ch.rot_init[x].fresh = cnt;
-        }
-        any_rot = true;
-    }
-    if (any_rot) {
-        const uint64_t n_pad_max = (c->chunk_reps + ecdna::kRotParts - 1) / ecdna::kRotParts + ecdna::kRotBlock;
-        CTX_TRY(hipMalloc(&c->d_rot_parts, ecdna::kRotParts * sizeof(ecdna::RotPart)));
-        CTX_TRY(hipMalloc(&c->d_rot_flags, ecdna::kRotParts * n_pad_max * sizeof(uint32_t)));
-        CTX_TRY(hipMalloc(&c->d_rot_park, c->chunk_reps * ecdna::kParkVecs * sizeof(uint4)));
-        // park only while at least 1.5 partition grids' worth of replicates wait; below that the lanes run
-        // their replicates to the end (C3 sweep, DESIGN.md §5: 0.5 / 1 / 2 / 3 grids -> 88.2 / 87.2 / 87.1 / 97.5 ms)
-        const uint64_t lanes_all = (uint64_t)c->stepper_blocks_cap * c->stepper_block;
-        c->rot_park_min = (int32_t)env_u64("ECDNA_SSA_ROT_PARK_MIN",
-                                           std::max<uint64_t>(1, lanes_all * 3 / 2 / ecdna::kRotParts));
-    }
-    // grid and drain control per chunk. Drain control (bin store, 256-lane blocks, one wave per SIMD per block):
-    // when lanes run more than two replicates each, the youngest wave slot of every SIMD stops taking fresh
-    // replicates once fewer than 1.5 grids' worth are left (C3: 105 -> 101 ms). ECDNA_SSA_ADMIT=0:
-    // off. Rotation replaces it.
-    for (auto& ch : c->chunks) {
-        // (paired lanes: owners only)
-        const uint32_t per_block = c->bin_ilp == 3 ? c->stepper_block / 2 : c->stepper_block;
-        const uint32_t need = (ch.n + per_block - 1) / per_block;
-        ch.blocks = std::max<uint32_t>(1, std::min<uint32_t>(need, c->stepper_blocks_cap));
-        const uint64_t lanes = (uint64_t)ch.blocks * c->stepper_block;
-        const uint32_t per_cu = c->cus ? (uint32_t)((ch.blocks + c->cus - 1) / c->cus) : 0u;
-        if (!ch.rot_n_pad && c->bin_k && c->stepper_block == 256 && per_cu >= 2 && ch.n > 2 * lanes &&
-            env_u64("ECDNA_SSA_ADMIT", 1)) {
-            const uint32_t slots = (uint32_t)std::min<uint64_t>(env_u64("ECDNA_SSA_ADMIT_SLOTS", 1), per_cu - 1);
-            ch.admit_slot = per_cu - std::max<uint32_t>(slots, 1u);
-            const uint64_t x8 = env_u64("ECDNA_SSA_ADMIT_X8", 12);  // eighths of a grid (tuning)
-            ch.admit_remaining = (uint32_t)std::min<uint64_t>(lanes * x8 / 8, ch.n);
-        }
+        return rc;
     }
     *out = c;
     return ECDNA_OK;
-#undef CTX_TRY
 }
 
 int ecdna_ssa_ctx_set_outputs(ecdna_ssa_ctx* c, uint64_t* d_hist, ecdna_totals_t* d_totals) {
@@ -893,258 +1134,42 @@ int ecdna_ssa_ctx_set_outputs(ecdna_ssa_ctx* c, uint64_t* d_hist, ecdna_totals_t
 
 int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
     if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    HIP_TRY(hipSetDevice(c->device));
+    TRY(hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;  // NULL = the default (null) stream
     const ecdna_ssa_params_t& p = c->p;
     const uint64_t nb = (uint64_t)p.n_param_sets * p.hist_bins;
-    HIP_TRY(hipMemsetAsync(c->d_hist, 0, nb * sizeof(uint64_t), st));
-    HIP_TRY(hipMemsetAsync(c->d_tot, 0, p.n_param_sets * sizeof(ecdna_totals_t), st));
-    if (c->d_sample_hist) HIP_TRY(hipMemsetAsync(c->d_sample_hist, 0, nb * sizeof(uint64_t), st));
-    if (c->d_snap_hist) HIP_TRY(hipMemsetAsync(c->d_snap_hist, 0, p.n_snapshots * nb * sizeof(uint64_t), st));
+    TRY(hipMemsetAsync(c->d_hist, 0, nb * sizeof(uint64_t), st));
+    TRY(hipMemsetAsync(c->d_tot, 0, p.n_param_sets * sizeof(ecdna_totals_t), st));
+    if (c->d_sample_hist) TRY(hipMemsetAsync(c->d_sample_hist, 0, nb * sizeof(uint64_t), st));
+    if (c->d_snap_hist) TRY(hipMemsetAsync(c->d_snap_hist, 0, p.n_snapshots * nb * sizeof(uint64_t), st));
     if (c->d_snap_sample_hist)
-        HIP_TRY(hipMemsetAsync(c->d_snap_sample_hist, 0, p.n_snapshots * nb * sizeof(uint64_t), st));
+        TRY(hipMemsetAsync(c->d_snap_sample_hist, 0, p.n_snapshots * nb * sizeof(uint64_t), st));
     if (!c->chunks.empty())
-        HIP_TRY(hipMemsetAsync(c->d_heads, 0, c->chunks.size() * sizeof(uint32_t), st));
+        TRY(hipMemsetAsync(c->d_heads, 0, c->chunks.size() * sizeof(uint32_t), st));
     if (c->d_snap_meta)
-        HIP_TRY(hipMemsetAsync(c->d_snap_meta, 0, p.n_replicates * p.n_snapshots * sizeof(ecdna_snapshot_t), st));
+        TRY(hipMemsetAsync(c->d_snap_meta, 0, p.n_replicates * p.n_snapshots * sizeof(ecdna_snapshot_t), st));
     // a passage run: G growth phases per chunk, phase g into its own slice of the per-phase outputs
     const uint32_t G = std::max<uint32_t>(c->n_passages, 1u);
     const uint64_t n_run = std::max<uint64_t>(p.n_replicates, 1);
     if (c->n_passages) {
-        HIP_TRY(hipMemsetAsync(c->d_pas_hist, 0, G * nb * sizeof(uint64_t), st));
-        HIP_TRY(hipMemsetAsync(c->d_pas_sample_hist, 0, G * nb * sizeof(uint64_t), st));
-        HIP_TRY(hipMemsetAsync(c->d_pas_tot, 0, (uint64_t)G * p.n_param_sets * sizeof(ecdna_totals_t), st));
+        TRY(hipMemsetAsync(c->d_pas_hist, 0, G * nb * sizeof(uint64_t), st));
+        TRY(hipMemsetAsync(c->d_pas_sample_hist, 0, G * nb * sizeof(uint64_t), st));
+        TRY(hipMemsetAsync(c->d_pas_tot, 0, (uint64_t)G * p.n_param_sets * sizeof(ecdna_totals_t), st));
     }
 
-    for (size_t k = 0; k < c->chunks.size(); ++k) {
-      for (uint32_t g = 0; g < G; ++g) {
-        Chunk& ch = c->chunks[k];
-        hipEvent_t* const ev = ch.ev.data() + 3u * g;
-        const bool pas = c->n_passages != 0;
-        // the chunk's work counter starts every phase at zero (the rotation state is reset below, per launch)
-        if (g > 0) HIP_TRY(hipMemsetAsync(c->d_heads + k, 0, sizeof(uint32_t), st));
-        ecdna::StepperArgs a{};
-        a.rows = c->d_rows;
-        a.summaries = (pas ? c->d_pas_summ + g * n_run : c->d_summ) + ch.first;
-        a.head = c->d_heads + k;
-        a.order = c->d_order ? c->d_order + ch.first : nullptr;
-        a.rates = c->d_rates;
-        a.init_copies = c->d_init;
-        a.init_offsets = c->d_init_off;
-        a.init_nminus_set = c->d_init_nm;
-        a.row_stride = c->row_stride;
-        a.seed = passage_seed(p.seed, g);  // (an ordinary run: the seed)
-        if (g > 0) {  // started from the founders the previous phase's sample left
-            a.founder_rows = c->d_founder_rows;
-            a.founder_counts = c->d_founder_counts;
-            a.founder_stride = c->founder_stride;
-        }
-        const uint64_t stride = p.replicate_stride ? p.replicate_stride : 1u;
-        a.rid0 = p.first_replicate + ch.first * stride;
-        a.rid_stride = stride;
-        a.reps_per_set = p.reps_per_set;
-        a.max_cells = p.max_cells;
-        a.init_nminus = p.init_nminus;
-        a.max_time = p.max_time;
-        a.max_time32 = (float)p.max_time;
-        a.n = ch.n;
-        a.init_nplus = p.init_nplus;
-        a.max_iter = (uint32_t)p.max_iter;
-        a.cell_cap = p.cell_cap;
-        a.flags = kernel_flags(p, c->n_passages != 0);  // (with the internal snapshot bit: it selects the kernel instance)
-        // (n- + n+) * 2 >= max_cells  <=>  n- + n+ >= ceil(max_cells / 2)
-        a.stop_cells = (p.process == ECDNA_BIRTH_DEATH && (p.flags & ECDNA_FLAG_BD_CAP_COMPAT))
-                           ? p.max_cells / 2 + (p.max_cells & 1)
-                           : p.max_cells;
-        a.n_snap = p.n_snapshots;
-        a.snap_cells = c->d_snap_cells;
-        a.snap_meta = c->d_snap_meta ? c->d_snap_meta + ch.first * p.n_snapshots : nullptr;
-        // (the run's rows at the chunk's offset, or the chunk's scratch)
-        a.snap_rows = c->d_snap_rows;
-        if (a.snap_rows && !c->snap_rows_local) a.snap_rows += ch.first * p.n_snapshots * c->out_stride;
-        a.snap_stride = c->out_stride;
-        a.big_cap = c->big_cap;
-        a.bags = c->d_bags;
-        const uint32_t blocks = ch.blocks;
-        a.admit_slot = ch.admit_slot;  // (drain control, decided at create)
-        a.admit_remaining = ch.admit_remaining;
-        if (ch.rot_n_pad) {  // rotation replaces the drain control
-            a.rot_parts = c->d_rot_parts;
-            a.rot_flags = c->d_rot_flags;
-            a.rot_park = c->d_rot_park;
-            a.rot_n_pad = ch.rot_n_pad;
-            a.rot_tick_log2 = c->rot_tick_log2;
-            a.rot_park_min = c->rot_park_min;
-            const uint64_t n_flags = (uint64_t)ecdna::kRotParts * ch.rot_n_pad;
-            HIP_TRY(hipMemsetD32Async(c->d_rot_flags, ecdna::ROT_FRESH, ch.n, st));
-            if (n_flags > ch.n)
-                HIP_TRY(hipMemsetD32Async(c->d_rot_flags + ch.n, ecdna::ROT_DONE, n_flags - ch.n, st));
-            HIP_TRY(hipMemcpyAsync(c->d_rot_parts, ch.rot_init.data(), ecdna::kRotParts * sizeof(ecdna::RotPart),
-                                   hipMemcpyHostToDevice, st));
-        }
-
-        a.ref_key = c->d_ref_key;
-        a.ref_btpe = c->d_ref_btpe;
-        a.rng_words = c->d_rng_words ? c->d_rng_words + ch.first : nullptr;
-        HIP_TRY(hipEventRecord(ev[0], st));
-        if (c->refdraws)
-            HIP_TRY(ecdna::launch_refdraws(a, p.process, p.segregation, blocks, st));
-        else if (c->bin_k)
-            HIP_TRY(ecdna::launch_bin_stepper(a, p.process, p.segregation, c->bin_k, c->bin_c32, c->bin_ilp, blocks, st));
-        else
-            HIP_TRY(ecdna::launch_stepper(a, p.process, p.segregation, c->window, blocks, st));
-        HIP_TRY(hipEventRecord(ev[1], st));
-
-        ecdna::HistArgs hsa{};
-        hsa.rows = c->d_rows;
-        hsa.summaries = a.summaries;
-        hsa.hist = pas ? c->d_pas_hist + g * nb : c->d_hist;
-        hsa.totals = reinterpret_cast<unsigned long long*>(pas ? c->d_pas_tot + (uint64_t)g * p.n_param_sets : c->d_tot);
-        hsa.row_stride = c->row_stride;
-        hsa.rid0 = p.first_replicate + ch.first * stride;
-        hsa.rid_stride = stride;
-        hsa.reps_per_set = p.reps_per_set;
-        hsa.n = ch.n;
-        hsa.bins = p.hist_bins;
-        // (eight workgroups per CU for either histogram pass: one per CU made the bin store's lane-per-replicate
-        // pass no faster at C3, 0.29 -> 0.30 ms, and C4's 1,024 sets 5 -> 28 ms, each workgroup walking more sets)
-        const uint32_t hist_blocks_max = (uint32_t)c->cus * 8u;
-        uint32_t rpb = (ch.n + hist_blocks_max - 1) / hist_blocks_max;
-        // at least one replicate per lane of a workgroup, or the chunk's replicates of one parameter set if fewer: small
-        // runs otherwise spread over 2,048 workgroups of mostly idle waves, each adding its own nonzero bins to the
-        // same global words (C2: 0.061 -> 0.023 ms per launch at 256, 0.038 at 64, 0.052 at 1,024;
-        // profiles/r06ak_hist_rpb.txt); sweeps of small sets keep about one set per workgroup
-        const uint64_t set_local = std::max<uint64_t>(1, p.reps_per_set / stride);
-        const uint32_t rpb_min = (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(ecdna::kHistBlock, set_local));
-        if (rpb < rpb_min) rpb = rpb_min;
-        hsa.reps_per_block = rpb;
-        hsa.stats = c->d_stats ? c->d_stats + ch.first : nullptr;
-        hsa.target_cdf = c->d_target_cdf;
-        hsa.target_mean = c->target_mean;
-        hsa.target_entropy = c->target_entropy;
-        hsa.target_freq = c->target_freq;
-        hsa.has_target = c->has_target ? 1u : 0u;
-        if (pas) {
-            hsa.stats = c->d_pas_stats + g * n_run + ch.first;
-            if (c->d_pas_target_cdf) {  // phase g's own target (else params.stats_target_hist for all, as above)
-                hsa.target_cdf = c->d_pas_target_cdf + (uint64_t)g * p.hist_bins;
-                hsa.target_mean = c->pas_target_scalars[3 * g];
-                hsa.target_entropy = c->pas_target_scalars[3 * g + 1];
-                hsa.target_freq = c->pas_target_scalars[3 * g + 2];
-                hsa.has_target = 1u;
-            }
-        }
-        hsa.bags = c->d_bags;
-        hsa.bag_k = c->bin_k;
-        hsa.bag_c32 = (uint32_t)c->bin_c32;
-        const uint32_t hblocks = (ch.n + rpb - 1) / rpb;
-        HIP_TRY(ecdna::launch_hist(hsa, hblocks, st));
-        if (p.subsample_cells) {  // the samples' statistics and histogram, from the same final state
-            ecdna::SubsampleArgs sa{};
-            sa.rows = hsa.rows;
-            sa.summaries = hsa.summaries;
-            sa.stats = c->d_sample_stats + ch.first;
-            sa.sample_hist = c->d_sample_hist;
-            sa.row_stride = hsa.row_stride;
-            sa.rid0 = hsa.rid0;
-            sa.rid_stride = hsa.rid_stride;
-            sa.reps_per_set = hsa.reps_per_set;
-            sa.seed = p.seed;
-            sa.n = ch.n;
-            sa.bins = p.hist_bins;
-            sa.m = p.subsample_cells;
-            sa.table_slots = ecdna::subsample_table_slots(p.subsample_cells);
-            sa.has_target = hsa.has_target;
-            sa.target_cdf = hsa.target_cdf;
-            sa.target_mean = hsa.target_mean;
-            sa.target_entropy = hsa.target_entropy;
-            sa.target_freq = hsa.target_freq;
-            sa.bags = hsa.bags;
-            sa.bag_k = hsa.bag_k;
-            sa.bag_c32 = hsa.bag_c32;
-            // one wave per replicate: a workgroup's share is at least one replicate per wave, at most the histogram
-            // pass's (which bounds the sets a workgroup walks)
-            const uint32_t sw = ecdna::subsample_waves(sa.bins, sa.bag_k, sa.table_slots, nullptr);
-            sa.reps_per_block = std::max<uint32_t>(sw, (ch.n + hist_blocks_max - 1) / hist_blocks_max);
-            HIP_TRY(ecdna::launch_subsample(sa, (ch.n + sa.reps_per_block - 1) / sa.reps_per_block, st));
-        }
-        if (pas) {  // the phase's measurement, and (but for the last phase) the founders of the next
-            ecdna::PassageArgs pa{};
-            pa.rows = hsa.rows;
-            pa.summaries = hsa.summaries;
-            pa.stats = c->d_pas_sample_stats + g * n_run + ch.first;
-            pa.sample_hist = c->d_pas_sample_hist + g * nb;
-            pa.founder_rows = g + 1u < G ? c->d_founder_rows : nullptr;
-            pa.founder_counts = c->d_founder_counts;
-            pa.founder_stride = c->founder_stride;
-            pa.row_stride = hsa.row_stride;
-            pa.rid0 = hsa.rid0;
-            pa.rid_stride = hsa.rid_stride;
-            pa.reps_per_set = hsa.reps_per_set;
-            pa.seed = a.seed;
-            pa.n = ch.n;
-            pa.bins = p.hist_bins;
-            pa.m = c->passage_m;
-            pa.table_slots = ecdna::subsample_table_slots(c->passage_m);
-            pa.sort_slots = ecdna::passage_sort_slots(c->passage_m);
-            pa.has_target = hsa.has_target;
-            pa.target_cdf = hsa.target_cdf;
-            pa.target_mean = hsa.target_mean;
-            pa.target_entropy = hsa.target_entropy;
-            pa.target_freq = hsa.target_freq;
-            pa.bags = hsa.bags;
-            pa.bag_k = hsa.bag_k;
-            pa.bag_c32 = hsa.bag_c32;
-            // one wave per replicate: a workgroup's share as the subsampling pass's
-            const uint32_t pw = ecdna::passage_waves(pa.bins, pa.bag_k, pa.table_slots, pa.sort_slots, nullptr);
-            pa.reps_per_block = std::max<uint32_t>(pw, (ch.n + hist_blocks_max - 1) / hist_blocks_max);
-            HIP_TRY(ecdna::launch_passage(pa, (ch.n + pa.reps_per_block - 1) / pa.reps_per_block, st));
-        }
-        if (c->snap_stats) {  // the statistics of the chunk's snapshots, from the rows the stepper just saved
-            ecdna::SnapStatsArgs ta{};
-            ta.snap_meta = a.snap_meta;
-            ta.snap_rows = a.snap_rows;
-            ta.stats = c->d_snap_stats + ch.first * p.n_snapshots;
-            ta.sample_stats = c->d_snap_sample_stats ? c->d_snap_sample_stats + ch.first * p.n_snapshots : nullptr;
-            ta.hist = c->d_snap_hist;
-            ta.sample_hist = c->d_snap_sample_hist;
-            ta.target_cdf = c->d_snap_target_cdf;
-            ta.target_scalars = c->d_snap_target_scalars;
-            ta.snap_stride = a.snap_stride;
-            ta.rid0 = hsa.rid0;
-            ta.rid_stride = hsa.rid_stride;
-            ta.reps_per_set = hsa.reps_per_set;
-            ta.seed = p.seed;
-            ta.n = ch.n;
-            ta.n_snap = p.n_snapshots;
-            ta.n_sets = p.n_param_sets;
-            ta.bins = p.hist_bins;
-            ta.m = c->snap_m;
-            ta.table_slots = c->snap_m ? ecdna::subsample_table_slots(c->snap_m) : 0u;
-            // one wave per (replicate, snapshot): a workgroup's share as the subsampling pass's
-            const uint32_t tw = ecdna::snapstats_waves(ta.bins, ta.table_slots, nullptr, nullptr);
-            ta.reps_per_block = std::max<uint32_t>(tw, (ch.n + hist_blocks_max - 1) / hist_blocks_max);
-            HIP_TRY(ecdna::launch_snapstats(ta, (ch.n + ta.reps_per_block - 1) / ta.reps_per_block, st));
-        }
-        HIP_TRY(hipEventRecord(ev[2], st));
-      }  // (growth phases)
-    }
+    for (size_t k = 0; k < c->chunks.size(); ++k)
+        for (uint32_t g = 0; g < G; ++g) TRY(launch_chunk_phase(c, k, g, st));
     if (c->n_passages && p.n_replicates) {  // the ordinary outputs are the last phase's
-        const uint64_t gl = G - 1u;
-        HIP_TRY(hipMemcpyAsync(c->d_summ, c->d_pas_summ + gl * n_run, p.n_replicates * sizeof(ecdna_rep_summary_t),
-                               hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->d_stats, c->d_pas_stats + gl * n_run, p.n_replicates * sizeof(ecdna_rep_stats_t),
-                               hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->d_sample_stats, c->d_pas_sample_stats + gl * n_run,
-                               p.n_replicates * sizeof(ecdna_rep_stats_t), hipMemcpyDeviceToDevice, st));
+        const uint64_t at = (G - 1u) * n_run;
+        TRY(copy_async(c->d_summ, c->d_pas_summ + at, p.n_replicates, st));
+        TRY(copy_async(c->d_stats, c->d_pas_stats + at, p.n_replicates, st));
+        TRY(copy_async(c->d_sample_stats, c->d_pas_sample_stats + at, p.n_replicates, st));
     }
     if (c->n_passages) {
         const uint64_t gl = G - 1u;
-        HIP_TRY(hipMemcpyAsync(c->d_hist, c->d_pas_hist + gl * nb, nb * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->d_sample_hist, c->d_pas_sample_hist + gl * nb, nb * sizeof(uint64_t),
-                               hipMemcpyDeviceToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->d_tot, c->d_pas_tot + gl * p.n_param_sets, p.n_param_sets * sizeof(ecdna_totals_t),
-                               hipMemcpyDeviceToDevice, st));
+        TRY(copy_async(c->d_hist, c->d_pas_hist + gl * nb, nb, st));
+        TRY(copy_async(c->d_sample_hist, c->d_pas_sample_hist + gl * nb, nb, st));
+        TRY(copy_async(c->d_tot, c->d_pas_tot + gl * p.n_param_sets, p.n_param_sets, st));
     }
     c->last_stream = st;
     c->launched = true;
@@ -1152,16 +1177,14 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
 }
 
 int ecdna_ssa_ctx_sync(ecdna_ssa_ctx* c, float* ssa_ms, float* hist_ms) {
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!c->launched) return fail(ECDNA_E_STATE, "sync before launch");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    TRY(ctx_launched(c, "sync before launch"));
+    TRY(ctx_drain(c));
     float s = 0.f, h = 0.f;
     for (auto& ch : c->chunks) {
         for (size_t e = 0; e + 2 < ch.ev.size(); e += 3) {  // per growth phase (one in an ordinary run)
             float a = 0.f, b = 0.f;
-            HIP_TRY(hipEventElapsedTime(&a, ch.ev[e], ch.ev[e + 1]));
-            HIP_TRY(hipEventElapsedTime(&b, ch.ev[e + 1], ch.ev[e + 2]));
+            TRY(hipEventElapsedTime(&a, ch.ev[e], ch.ev[e + 1]));
+            TRY(hipEventElapsedTime(&b, ch.ev[e + 1], ch.ev[e + 2]));
             s += a;
             h += b;
         }
@@ -1205,14 +1228,14 @@ int ecdna_ssa_ctx_instance(const ecdna_ssa_ctx* c, ecdna_ssa_instance_t* out) {
         r.paired = c->bin_ilp == 3 ? 1 : 0;
         r.bin_kmax = c->bin_k;
         r.bin_c32 = (uint32_t)c->bin_c32;
-        r.runtime_flags = (kernel_flags(p, c->n_passages != 0) & ecdna::kRuntimeFlagMask) ? 1 : 0;
-        fn = ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kernel_flags(p, c->n_passages != 0), c->bin_ilp);
+        r.runtime_flags = (kernel_flags(*c) & ecdna::kRuntimeFlagMask) ? 1 : 0;
+        fn = ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kernel_flags(*c), c->bin_ilp);
     } else {
         r.kernel = ECDNA_KERNEL_ROWS;
         r.schedule = -1;
         r.window = (uint32_t)c->window;
         r.runtime_flags = 1;
-        fn = ecdna::stepper_kernel(p.process, p.segregation, c->window, kernel_flags(p, c->n_passages != 0));
+        fn = ecdna::stepper_kernel(p.process, p.segregation, c->window, kernel_flags(*c));
     }
     for (const auto& ch : c->chunks) {
         r.rotation += ch.rot_n_pad ? 1 : 0;
@@ -1242,42 +1265,33 @@ int ecdna_ssa_ctx_instance(const ecdna_ssa_ctx* c, ecdna_ssa_instance_t* out) {
 
 int ecdna_ssa_ctx_download(ecdna_ssa_ctx* c, ecdna_rep_summary_t* out_summaries, uint64_t* out_hist,
                            ecdna_totals_t* out_totals, uint16_t* out_rows) {
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!c->launched) return fail(ECDNA_E_STATE, "download before launch");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    TRY(ctx_launched(c));
+    TRY(ctx_drain(c));
     const ecdna_ssa_params_t& p = c->p;
-    if (out_summaries && p.n_replicates)
-        HIP_TRY(hipMemcpy(out_summaries, c->d_summ, p.n_replicates * sizeof(ecdna_rep_summary_t),
-                          hipMemcpyDeviceToHost));
-    if (out_hist)
-        HIP_TRY(hipMemcpy(out_hist, c->d_hist, (uint64_t)p.n_param_sets * p.hist_bins * sizeof(uint64_t),
-                          hipMemcpyDeviceToHost));
-    if (out_totals)
-        HIP_TRY(hipMemcpy(out_totals, c->d_tot, p.n_param_sets * sizeof(ecdna_totals_t), hipMemcpyDeviceToHost));
+    const uint64_t n = p.n_replicates;
+    if (out_summaries && n) TRY(to_host(out_summaries, c->d_summ, n));
+    if (out_hist) TRY(to_host(out_hist, c->d_hist, (uint64_t)p.n_param_sets * p.hist_bins));
+    if (out_totals) TRY(to_host(out_totals, c->d_tot, p.n_param_sets));
     if (out_rows) {
         if (c->chunks.size() > 1) return fail(ECDNA_E_STATE, "rows are not downloadable from a chunked run");
-        if (p.n_replicates && !c->bin_k)
-            HIP_TRY(hipMemcpy(out_rows, c->d_rows, p.n_replicates * c->row_stride * sizeof(uint16_t),
-                              hipMemcpyDeviceToHost));
-        if (c->bin_k && p.n_replicates) {
-            std::vector<uint16_t> dev_rows(p.n_replicates * c->row_stride);  // the large-k rows
-            HIP_TRY(hipMemcpy(dev_rows.data(), c->d_rows, dev_rows.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        if (n && !c->bin_k) TRY(to_host(out_rows, c->d_rows, n * c->row_stride));
+        if (c->bin_k && n) {
+            std::vector<uint16_t> dev_rows(n * c->row_stride);  // the large-k rows
+            TRY(to_host(dev_rows.data(), c->d_rows, dev_rows.size()));
             // bin store: canonical rows = the counters expanded (k ascending), then the large-k row
-            std::vector<ecdna_rep_summary_t> summ(p.n_replicates);
-            HIP_TRY(hipMemcpy(summ.data(), c->d_summ, p.n_replicates * sizeof(ecdna_rep_summary_t),
-                              hipMemcpyDeviceToHost));
+            std::vector<ecdna_rep_summary_t> summ(n);
+            TRY(to_host(summ.data(), c->d_summ, n));
             const uint64_t kb = c->bin_k;
-            std::vector<uint32_t> bags(p.n_replicates * kb);
+            std::vector<uint32_t> bags(n * kb);
             if (c->bin_c32) {
-                HIP_TRY(hipMemcpy(bags.data(), c->d_bags, bags.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                TRY(to_host(bags.data(), reinterpret_cast<const uint32_t*>(c->d_bags), bags.size()));
             } else {
                 std::vector<uint16_t> b16(bags.size());
-                HIP_TRY(hipMemcpy(b16.data(), c->d_bags, b16.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+                TRY(to_host(b16.data(), reinterpret_cast<const uint16_t*>(c->d_bags), b16.size()));
                 std::copy(b16.begin(), b16.end(), bags.begin());
             }
             std::vector<uint16_t> big;
-            for (uint64_t i = 0; i < p.n_replicates; ++i) {
+            for (uint64_t i = 0; i < n; ++i) {
                 uint16_t* r = out_rows + i * c->out_stride;
                 const uint16_t* dr = dev_rows.data() + i * c->row_stride;
                 uint64_t small = 0;
@@ -1297,46 +1311,37 @@ int ecdna_ssa_ctx_download(ecdna_ssa_ctx* c, ecdna_rep_summary_t* out_summaries,
 }
 
 int ecdna_ssa_ctx_download_snapshots(ecdna_ssa_ctx* c, ecdna_snapshot_t* meta, uint16_t* rows) {
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!c->launched) return fail(ECDNA_E_STATE, "download before launch");
+    TRY(ctx_launched(c));
     const ecdna_ssa_params_t& p = c->p;
     if (!p.n_snapshots || !p.n_replicates) return ECDNA_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    TRY(ctx_drain(c));
     const uint64_t ns = p.n_replicates * p.n_snapshots;
-    if (meta) HIP_TRY(hipMemcpy(meta, c->d_snap_meta, ns * sizeof(ecdna_snapshot_t), hipMemcpyDeviceToHost));
+    if (meta) TRY(to_host(meta, c->d_snap_meta, ns));
     if (rows) {
         if (!c->d_snap_rows || c->snap_rows_local)
             return fail(ECDNA_E_STATE, "snapshot rows need ECDNA_FLAG_SNAPSHOT_ROWS");
-        HIP_TRY(hipMemcpy(rows, c->d_snap_rows, ns * c->out_stride * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        TRY(to_host(rows, c->d_snap_rows, ns * c->out_stride));
     }
     return ECDNA_OK;
 }
 
 int ecdna_ssa_ctx_download_stats(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out) {
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!c->launched) return fail(ECDNA_E_STATE, "download before launch");
+    TRY(ctx_launched(c));
     if (!c->d_stats) return fail(ECDNA_E_STATE, "statistics need ECDNA_FLAG_REP_STATS");
     if (!out || !c->p.n_replicates) return ECDNA_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(out, c->d_stats, c->p.n_replicates * sizeof(ecdna_rep_stats_t), hipMemcpyDeviceToHost));
+    TRY(ctx_drain(c));
+    TRY(to_host(out, c->d_stats, c->p.n_replicates));
     return ECDNA_OK;
 }
 
 int ecdna_ssa_ctx_download_sample(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats, uint64_t* out_sample_hist) {
     if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
     if (!c->d_sample_hist) return fail(ECDNA_E_STATE, "the sample needs subsample_cells > 0");
-    if (!c->launched) return fail(ECDNA_E_STATE, "download before launch");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    TRY(ctx_launched(c));
+    TRY(ctx_drain(c));
     const ecdna_ssa_params_t& p = c->p;
-    if (out_stats && p.n_replicates)
-        HIP_TRY(hipMemcpy(out_stats, c->d_sample_stats, p.n_replicates * sizeof(ecdna_rep_stats_t),
-                          hipMemcpyDeviceToHost));
-    if (out_sample_hist)
-        HIP_TRY(hipMemcpy(out_sample_hist, c->d_sample_hist,
-                          (uint64_t)p.n_param_sets * p.hist_bins * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (out_stats && p.n_replicates) TRY(to_host(out_stats, c->d_sample_stats, p.n_replicates));
+    if (out_sample_hist) TRY(to_host(out_sample_hist, c->d_sample_hist, (uint64_t)p.n_param_sets * p.hist_bins));
     return ECDNA_OK;
 }
 
@@ -1345,19 +1350,17 @@ int ecdna_ssa_ctx_download_snapshot_stats(ecdna_ssa_ctx* c, ecdna_rep_stats_t* o
                                           uint64_t* out_sample_hist) {
     if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
     if (!c->snap_stats) return fail(ECDNA_E_STATE, "snapshot statistics need ecdna_ssa_ext_t.snapshot_stats");
-    if (!c->launched) return fail(ECDNA_E_STATE, "download before launch");
+    TRY(ctx_launched(c));
     if ((out_sample_stats || out_sample_hist) && !c->snap_m)
         return fail(ECDNA_E_STATE, "the snapshot samples need ecdna_ssa_ext_t.snapshot_subsample_cells > 0");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    TRY(ctx_drain(c));
     const ecdna_ssa_params_t& p = c->p;
-    const uint64_t ns = p.n_replicates * p.n_snapshots * sizeof(ecdna_rep_stats_t);
-    const uint64_t hb = (uint64_t)p.n_snapshots * p.n_param_sets * p.hist_bins * sizeof(uint64_t);
-    if (out_stats && ns) HIP_TRY(hipMemcpy(out_stats, c->d_snap_stats, ns, hipMemcpyDeviceToHost));
-    if (out_sample_stats && ns)
-        HIP_TRY(hipMemcpy(out_sample_stats, c->d_snap_sample_stats, ns, hipMemcpyDeviceToHost));
-    if (out_hist) HIP_TRY(hipMemcpy(out_hist, c->d_snap_hist, hb, hipMemcpyDeviceToHost));
-    if (out_sample_hist) HIP_TRY(hipMemcpy(out_sample_hist, c->d_snap_sample_hist, hb, hipMemcpyDeviceToHost));
+    const uint64_t ns = p.n_replicates * p.n_snapshots;
+    const uint64_t hb = (uint64_t)p.n_snapshots * p.n_param_sets * p.hist_bins;
+    if (out_stats && ns) TRY(to_host(out_stats, c->d_snap_stats, ns));
+    if (out_sample_stats && ns) TRY(to_host(out_sample_stats, c->d_snap_sample_stats, ns));
+    if (out_hist) TRY(to_host(out_hist, c->d_snap_hist, hb));
+    if (out_sample_hist) TRY(to_host(out_sample_hist, c->d_snap_sample_hist, hb));
     return ECDNA_OK;
 }
 
@@ -1366,34 +1369,26 @@ int ecdna_ssa_ctx_download_passages(ecdna_ssa_ctx* c, ecdna_rep_summary_t* out_s
                                     uint64_t* out_hist, uint64_t* out_sample_hist) {
     if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
     if (!c->n_passages) return fail(ECDNA_E_STATE, "per-phase results need ecdna_ssa_ctx_create_passages");
-    if (!c->launched) return fail(ECDNA_E_STATE, "download before launch");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
+    TRY(ctx_launched(c));
+    TRY(ctx_drain(c));
     const ecdna_ssa_params_t& p = c->p;
     const uint64_t G = c->n_passages, n = p.n_replicates;
-    const uint64_t hb = G * p.n_param_sets * p.hist_bins * sizeof(uint64_t);
-    if (out_summaries && n)
-        HIP_TRY(hipMemcpy(out_summaries, c->d_pas_summ, G * n * sizeof(ecdna_rep_summary_t), hipMemcpyDeviceToHost));
-    if (out_totals)
-        HIP_TRY(hipMemcpy(out_totals, c->d_pas_tot, G * p.n_param_sets * sizeof(ecdna_totals_t), hipMemcpyDeviceToHost));
-    if (out_stats && n)
-        HIP_TRY(hipMemcpy(out_stats, c->d_pas_stats, G * n * sizeof(ecdna_rep_stats_t), hipMemcpyDeviceToHost));
-    if (out_sample_stats && n)
-        HIP_TRY(hipMemcpy(out_sample_stats, c->d_pas_sample_stats, G * n * sizeof(ecdna_rep_stats_t),
-                          hipMemcpyDeviceToHost));
-    if (out_hist) HIP_TRY(hipMemcpy(out_hist, c->d_pas_hist, hb, hipMemcpyDeviceToHost));
-    if (out_sample_hist) HIP_TRY(hipMemcpy(out_sample_hist, c->d_pas_sample_hist, hb, hipMemcpyDeviceToHost));
+    const uint64_t hb = G * p.n_param_sets * p.hist_bins;
+    if (out_summaries && n) TRY(to_host(out_summaries, c->d_pas_summ, G * n));
+    if (out_totals) TRY(to_host(out_totals, c->d_pas_tot, G * p.n_param_sets));
+    if (out_stats && n) TRY(to_host(out_stats, c->d_pas_stats, G * n));
+    if (out_sample_stats && n) TRY(to_host(out_sample_stats, c->d_pas_sample_stats, G * n));
+    if (out_hist) TRY(to_host(out_hist, c->d_pas_hist, hb));
+    if (out_sample_hist) TRY(to_host(out_sample_hist, c->d_pas_sample_hist, hb));
     return ECDNA_OK;
 }
 
 int ecdna_ssa_ctx_download_rng_words(ecdna_ssa_ctx* c, uint64_t* out) {
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!c->launched) return fail(ECDNA_E_STATE, "download before launch");
+    TRY(ctx_launched(c));
     if (!c->d_rng_words) return fail(ECDNA_E_STATE, "stream positions need ECDNA_FLAG_REFERENCE_DRAWS");
     if (!out || !c->p.n_replicates) return ECDNA_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->last_stream));
-    HIP_TRY(hipMemcpy(out, c->d_rng_words, c->p.n_replicates * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    TRY(ctx_drain(c));
+    TRY(to_host(out, c->d_rng_words, c->p.n_replicates));
     return ECDNA_OK;
 }
 

@@ -1,7 +1,7 @@
 // ssa_hist.hip — the end-of-run copy-number histogram pass (gfx950): per parameter set the histogram and the totals
 // of a chunk's replicates, and under ECDNA_FLAG_REP_STATS each replicate's ABC statistics. It reads what the
 // steppers left (rows, bags, summaries) and shares nothing with them but ssa_launch.h; the wave-level pieces it
-// shares with ssa_subsample.hip are in ssa_wave.hpp.
+// shares with the sampling passes are in ssa_wave.hpp.
 #include "ssa_launch.h"
 #include "ssa_wave.hpp"
 
@@ -20,27 +20,27 @@ namespace ecdna {
 template <bool STATS, int BAG>
 __global__ void __launch_bounds__(kHistBlock) ssa_hist(const HistArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long lds[];
-    unsigned long long* hb = lds;                // [bins]
-    unsigned long long* tb = lds + a.bins;       // [16] totals words
+    unsigned long long* hb = lds;               // [bins]
+    unsigned long long* tb = lds + a.ids.bins;  // [16] totals words
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t nw = blockDim.x >> 6;
-    uint32_t* wh = reinterpret_cast<uint32_t*>(lds + a.bins + 16) + wave * a.bins;  // STATS: [bins] per wave
-    const uint32_t r_begin = blockIdx.x * a.reps_per_block;
-    if (r_begin >= a.n) return;
-    const uint32_t r_end = min(a.n, r_begin + a.reps_per_block);
-    const uint32_t last = a.bins - 1;
+    uint32_t* wh = reinterpret_cast<uint32_t*>(lds + a.ids.bins + 16) + wave * a.ids.bins;  // STATS: [bins] per wave
+    const uint32_t r_begin = blockIdx.x * a.ids.reps_per_block;
+    if (r_begin >= a.ids.n) return;
+    const uint32_t r_end = min(a.ids.n, r_begin + a.ids.reps_per_block);
+    const uint32_t last = a.ids.bins - 1;
 
     uint32_t r = r_begin;
     while (r < r_end) {
-        const auto [set, seg_end] = set_segment(a.rid0, a.rid_stride, a.reps_per_set, r, r_end);
-        for (uint32_t b = tid; b < a.bins + 16; b += blockDim.x) lds[b] = 0ull;
+        const auto [set, seg_end] = set_segment(a.ids.rid0, a.ids.rid_stride, a.ids.reps_per_set, r, r_end);
+        for (uint32_t b = tid; b < a.ids.bins + 16; b += blockDim.x) lds[b] = 0ull;
         __syncthreads();
         for (uint32_t q = r + wave; q < seg_end; q += nw) {
             const ecdna_rep_summary_t* s = a.summaries + q;
             const uint32_t np = (uint32_t)s->nplus;
             const uint16_t* row = a.rows + (uint64_t)q * a.row_stride;
             if (STATS) {
-                for (uint32_t b = lane; b < a.bins; b += 64u) wh[b] = 0u;
+                for (uint32_t b = lane; b < a.ids.bins; b += 64u) wh[b] = 0u;
                 wave_sync_lds();
             }
             uint64_t ksum = 0;
@@ -82,8 +82,8 @@ __global__ void __launch_bounds__(kHistBlock) ssa_hist(const HistArgs a) {
             if (STATS) {
                 if (lane == 0) atomicAdd(&wh[0], (uint32_t)s->nminus);
                 wave_sync_lds();
-                wave_rep_stats(wh, hb, a.bins, s->nminus + (uint64_t)np, wave_sum(ksum), np, a.has_target, a.target_cdf,
-                               a.target_mean, a.target_entropy, a.target_freq, lane, a.stats + q);
+                wave_rep_stats(wh, hb, a.ids.bins, s->nminus + (uint64_t)np, wave_sum(ksum), np, a.target.has, a.target.cdf,
+                               a.target.mean, a.target.entropy, a.target.freq, lane, a.stats + q);
             }
             if (lane == 0) {
                 if (!STATS) atomicAdd(&hb[0], (unsigned long long)s->nminus);
@@ -101,8 +101,8 @@ __global__ void __launch_bounds__(kHistBlock) ssa_hist(const HistArgs a) {
             }
         }
         __syncthreads();
-        for (uint32_t b = tid; b < a.bins; b += blockDim.x)
-            if (hb[b]) atomicAdd((unsigned long long*)&a.hist[set * a.bins + b], hb[b]);
+        for (uint32_t b = tid; b < a.ids.bins; b += blockDim.x)
+            if (hb[b]) atomicAdd((unsigned long long*)&a.hist[set * a.ids.bins + b], hb[b]);
         if (tid < 16 && tb[tid]) atomicAdd(&a.totals[set * 16 + tid], tb[tid]);
         __syncthreads();
         r = seg_end;
@@ -121,20 +121,20 @@ __global__ void __launch_bounds__(kHistBlock) ssa_hist(const HistArgs a) {
 template <int BAG>
 __global__ void __launch_bounds__(kHistBlock) ssa_hist_bags(const HistArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long lds[];
-    unsigned long long* hb = lds;          // [bins]
-    unsigned long long* tb = lds + a.bins;  // [16] totals words
+    unsigned long long* hb = lds;               // [bins]
+    unsigned long long* tb = lds + a.ids.bins;  // [16] totals words
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t nw = blockDim.x >> 6;
-    const uint32_t r_begin = blockIdx.x * a.reps_per_block;
-    if (r_begin >= a.n) return;
-    const uint32_t r_end = min(a.n, r_begin + a.reps_per_block);
-    const uint32_t last = a.bins - 1;
+    const uint32_t r_begin = blockIdx.x * a.ids.reps_per_block;
+    if (r_begin >= a.ids.n) return;
+    const uint32_t r_end = min(a.ids.n, r_begin + a.ids.reps_per_block);
+    const uint32_t last = a.ids.bins - 1;
     const uint32_t bag_k = a.bag_k;  // 32, 64 or 256
 
     uint32_t r = r_begin;
     while (r < r_end) {
-        const auto [set, seg_end] = set_segment(a.rid0, a.rid_stride, a.reps_per_set, r, r_end);
-        for (uint32_t b = tid; b < a.bins + 16; b += blockDim.x) lds[b] = 0ull;
+        const auto [set, seg_end] = set_segment(a.ids.rid0, a.ids.rid_stride, a.ids.reps_per_set, r, r_end);
+        for (uint32_t b = tid; b < a.ids.bins + 16; b += blockDim.x) lds[b] = 0ull;
         __syncthreads();
         // totals words 0..8 per lane (replicates, iters, events_by_type[4], uneven, n-, n+); the stop reasons and
         // errors by ballot (wave-uniform counts)
@@ -248,8 +248,8 @@ __global__ void __launch_bounds__(kHistBlock) ssa_hist_bags(const HistArgs a) {
             if (t_err) atomicAdd(&tb[15], (unsigned long long)t_err);
         }
         __syncthreads();
-        for (uint32_t b = tid; b < a.bins; b += blockDim.x)
-            if (hb[b]) atomicAdd((unsigned long long*)&a.hist[set * a.bins + b], hb[b]);
+        for (uint32_t b = tid; b < a.ids.bins; b += blockDim.x)
+            if (hb[b]) atomicAdd((unsigned long long*)&a.hist[set * a.ids.bins + b], hb[b]);
         if (tid < 16 && tb[tid]) atomicAdd(&a.totals[set * 16 + tid], tb[tid]);
         __syncthreads();
         r = seg_end;
@@ -259,14 +259,13 @@ __global__ void __launch_bounds__(kHistBlock) ssa_hist_bags(const HistArgs a) {
 hipError_t launch_hist(const HistArgs& a, uint32_t blocks, hipStream_t stream) {
     HistArgs copy = a;
     void* args[] = {&copy};
-    size_t lds = (size_t)(a.bins + 16) * sizeof(unsigned long long);
-    if (a.stats) lds += (size_t)(kHistBlock / 64) * a.bins * sizeof(uint32_t);  // per-wave replicate histograms
+    size_t lds = (size_t)(a.ids.bins + 16) * sizeof(unsigned long long);
+    if (a.stats) lds += (size_t)(kHistBlock / 64) * a.ids.bins * sizeof(uint32_t);  // per-wave replicate histograms
     // (the bin store without statistics: one lane per replicate, ssa_hist_bags)
     static const void* const table[2][3] = {
         {(const void*)ssa_hist<false, 0>, (const void*)ssa_hist_bags<1>, (const void*)ssa_hist_bags<2>},
         {(const void*)ssa_hist<true, 0>, (const void*)ssa_hist<true, 1>, (const void*)ssa_hist<true, 2>}};
-    const int bag = a.bags ? (a.bag_c32 ? 2 : 1) : 0;
-    return hipLaunchKernel(table[a.stats ? 1 : 0][bag], dim3(blocks), dim3(kHistBlock), args, lds, stream);
+    return hipLaunchKernel(table[a.stats ? 1 : 0][bag_index(a.bags, a.bag_c32)], dim3(blocks), dim3(kHistBlock), args, lds, stream);
 }
 
 }  // namespace ecdna

@@ -88,26 +88,50 @@ struct StepperArgs {
     uint64_t founder_stride;        // cells per founder row (passage_cells rounded up to 64)
 };
 
-// Histogram / totals pass over one chunk.
-struct HistArgs {
-    const uint16_t* rows;
-    const ecdna_rep_summary_t* summaries; // chunk-offset
-    uint64_t* hist;                       // [n_sets][bins]
-    unsigned long long* totals;           // [n_sets][16] (ecdna_totals_t as u64 words)
-    uint64_t row_stride;
+// What the end-of-run passes share, embedded by value in their argument blocks and filled once per chunk and phase.
+// The chunk's replicates and how a pass splits them: local replicate r has the global id rid0 + r * rid_stride and
+// belongs to parameter set id / reps_per_set; workgroup w walks replicates [w * reps_per_block, ...).
+struct ChunkIds {
     uint64_t rid0;
     uint64_t rid_stride;                  // >= 1
     uint64_t reps_per_set;
     uint32_t n;
     uint32_t bins;
     uint32_t reps_per_block;
-    // per-replicate ABC statistics (nullptr = off), against target_cdf[bins] when has_target
-    ecdna_rep_stats_t* stats;             // chunk-offset
-    const double* target_cdf;
-    double target_mean, target_entropy, target_freq;
-    uint32_t has_target;
-    // bin store: per-replicate counters [n][bag_k] (u16, or u32 when bag_c32); nullptr = rows only
+};
+// The target of the ABC distances: its CDF over the bins and its mean / entropy / N+ frequency; has = 0: no distances.
+struct StatsTarget {
+    const double* cdf;                    // [bins]
+    double mean, entropy, freq;
+    uint32_t has;
+};
+// The final state the steppers left: rows and summaries, and in the bin store the per-replicate counters
+// [n][bag_k] (u16, or u32 when bag_c32) beside the large-k cells at the head of each row; bags = nullptr: rows only.
+struct FinalState {
+    const uint16_t* rows;
+    const ecdna_rep_summary_t* summaries; // chunk-offset
+    uint64_t row_stride;
     const void* bags;
+    uint32_t bag_k;
+    uint32_t bag_c32;
+};
+// The BAG template parameter of the passes: 0 = rows only, 1 / 2 = u16 / u32 bin counters.
+inline int bag_index(const void* bags, uint32_t bag_c32) { return bags ? (bag_c32 ? 2 : 1) : 0; }
+inline int bag_index(const FinalState& fs) { return bag_index(fs.bags, fs.bag_c32); }
+
+// Histogram / totals pass over one chunk. The final state's fields stand here one by one, hist and totals between
+// them: ssa_hist<false, 0> and ssa_hist_bags (the passes the bench times) read the first 64 bytes with one scalar
+// load, and with FinalState embedded they compiled to other instructions (docs/PERF_LOG.md).
+struct HistArgs {
+    const uint16_t* rows;                 // FinalState.rows, .summaries
+    const ecdna_rep_summary_t* summaries;
+    uint64_t* hist;                       // [n_sets][bins]
+    unsigned long long* totals;           // [n_sets][16] (ecdna_totals_t as u64 words)
+    uint64_t row_stride;                  // FinalState.row_stride
+    ChunkIds ids;
+    ecdna_rep_stats_t* stats;             // chunk-offset: per-replicate ABC statistics (nullptr = off)
+    StatsTarget target;
+    const void* bags;                     // FinalState.bags, .bag_k, .bag_c32
     uint32_t bag_k;
     uint32_t bag_c32;
 };
@@ -115,33 +139,21 @@ struct HistArgs {
 // End-of-run subsampling pass over one chunk (ssa_subsample.hip; params.subsample_cells > 0): per replicate, the
 // statistics of a sample of m cells of its final state, and the per-set sum of the samples' histograms.
 struct SubsampleArgs {
-    const uint16_t* rows;
-    const ecdna_rep_summary_t* summaries; // chunk-offset
+    FinalState state;
+    ChunkIds ids;
+    StatsTarget target;
     ecdna_rep_stats_t* stats;             // chunk-offset: the samples' statistics
     uint64_t* sample_hist;                // [n_sets][bins]
-    uint64_t row_stride;
-    uint64_t rid0;
-    uint64_t rid_stride;                  // >= 1
-    uint64_t reps_per_set;
     uint64_t seed;
-    uint32_t n;
-    uint32_t bins;
-    uint32_t reps_per_block;
     uint32_t m;                           // sample size (cells), 1 .. kMaxSubsampleCells
     uint32_t table_slots;                 // per-wave table of drawn positions: subsample_table_slots(m)
-    uint32_t has_target;
-    const double* target_cdf;
-    double target_mean, target_entropy, target_freq;
-    // bin store: per-replicate counters [n][bag_k] (u16, or u32 when bag_c32); nullptr = rows only
-    const void* bags;
-    uint32_t bag_k;
-    uint32_t bag_c32;
 };
 
 // Per-snapshot ABC statistics over one chunk (ssa_snapstats.hip; ecdna_ssa_ext_t.snapshot_stats): for every replicate
 // and snapshot, the statistics of the saved state (and of a sample of m of its cells), and per snapshot and set the
 // sum of the saved states' (the samples') histograms. A snapshot that was not taken counts as an empty population.
 struct SnapStatsArgs {
+    ChunkIds ids;
     const ecdna_snapshot_t* snap_meta;    // [n][n_snap], chunk-offset
     const uint16_t* snap_rows;            // [n][n_snap][snap_stride]: the chunk's snapshot rows (expanded u16 rows)
     ecdna_rep_stats_t* stats;             // [n][n_snap], chunk-offset
@@ -151,15 +163,9 @@ struct SnapStatsArgs {
     const double* target_cdf;             // [n_snap][bins]: each snapshot's own target, or nullptr (no distances)
     const double* target_scalars;         // [n_snap][3]: the targets' mean, entropy, N+ frequency
     uint64_t snap_stride;
-    uint64_t rid0;
-    uint64_t rid_stride;                  // >= 1
-    uint64_t reps_per_set;
     uint64_t seed;
-    uint32_t n;
     uint32_t n_snap;
     uint32_t n_sets;
-    uint32_t bins;
-    uint32_t reps_per_block;
     uint32_t m;                           // sample size (cells), 0 = no samples, <= kMaxSubsampleCells
     uint32_t table_slots;                 // per-wave table of drawn positions: subsample_table_slots(m), 0 when m == 0
 };
@@ -168,32 +174,19 @@ struct SnapStatsArgs {
 // phase's final state by subsample mapping v1 (statistics and per-set histogram exactly as SubsampleArgs' pass), and,
 // unless this is the last phase, the sample's cells as the next phase's founders.
 struct PassageArgs {
-    const uint16_t* rows;
-    const ecdna_rep_summary_t* summaries; // chunk-offset
+    FinalState state;
+    ChunkIds ids;
+    StatsTarget target;
     ecdna_rep_stats_t* stats;             // chunk-offset: the samples' statistics
     uint64_t* sample_hist;                // [n_sets][bins]
     uint16_t* founder_rows;               // [n][founder_stride], chunk-local: the sample's N+ copy numbers, ascending;
                                           // nullptr: no founders (the last phase)
     uint2* founder_counts;                // [n], chunk-local: {n-, n+} of the sample
     uint64_t founder_stride;              // >= m
-    uint64_t row_stride;
-    uint64_t rid0;
-    uint64_t rid_stride;                  // >= 1
-    uint64_t reps_per_set;
     uint64_t seed;                        // the phase's key seed_g
-    uint32_t n;
-    uint32_t bins;
-    uint32_t reps_per_block;
     uint32_t m;                           // sample size (cells), 1 .. kMaxSubsampleCells
     uint32_t table_slots;                 // per-wave table of drawn positions: subsample_table_slots(m)
     uint32_t sort_slots;                  // per-wave founder array (u16): passage_sort_slots(m)
-    uint32_t has_target;
-    const double* target_cdf;
-    double target_mean, target_entropy, target_freq;
-    // bin store: per-replicate counters [n][bag_k] (u16, or u32 when bag_c32); nullptr = rows only
-    const void* bags;
-    uint32_t bag_k;
-    uint32_t bag_c32;
 };
 
 constexpr uint32_t kMaxSubsampleCells = 4096;  // LDS: 8 B of table per sampled cell and wave (<= 32 KiB)
@@ -237,21 +230,49 @@ int bin_stepper_block(uint32_t bin_k);
 hipError_t launch_bin_stepper(const StepperArgs& a, int birth_death, int segregation, uint32_t bin_k, int c32, int ilp,
                               uint32_t blocks, hipStream_t stream);
 hipError_t launch_hist(const HistArgs& a, uint32_t blocks, hipStream_t stream);
-// The subsampling pass (ssa_subsample.hip): 2 * pow2ceil(m) table slots per wave; 1, 2 or 4 waves per workgroup, as
-// many as keep its dynamic LDS (lds_bytes) within 64 KiB; one wave per replicate.
-uint32_t subsample_table_slots(uint32_t m);
-uint32_t subsample_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, size_t* lds_bytes);
+// The sampling passes (ssa_subsample.hip, ssa_passage.hip, ssa_snapstats.hip) run one wave per population, each wave
+// with its own histogram, table of drawn positions (2 * pow2ceil(m) slots) and, in the passage pass, founder array
+// (pow2ceil(m) u16 slots, at least 64) in dynamic LDS. pass_waves: 1, 2 or 4 waves per workgroup, as many as keep
+// fixed_bytes + waves * per_wave_bytes (*lds_bytes) within 64 KiB; one wave may exceed it, which the launch refuses.
+constexpr size_t kPassLdsMax = 65536;
+inline uint32_t pass_waves(size_t fixed_bytes, size_t per_wave_bytes, size_t* lds_bytes) {
+    uint32_t nw = 4;
+    while (nw > 1u && fixed_bytes + nw * per_wave_bytes > kPassLdsMax) nw >>= 1;
+    if (lds_bytes) *lds_bytes = fixed_bytes + nw * per_wave_bytes;
+    return nw;
+}
+inline uint32_t pow2_from(uint32_t p, uint32_t m) {
+    while (p < m) p <<= 1;
+    return p;
+}
+inline uint32_t subsample_table_slots(uint32_t m) { return 2u * pow2_from(1u, m); }
+inline uint32_t passage_sort_slots(uint32_t m) { return pow2_from(64u, m); }
+// ssa_subsample: the workgroup's u64 sum of the samples' histograms; per wave histogram, prefix sums, table (u32)
+inline uint32_t subsample_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, size_t* lds_bytes) {
+    return pass_waves((size_t)bins * 8u, ((size_t)bins + bag_k + table_slots) * 4u, lds_bytes);
+}
+// ssa_passage: no workgroup histogram (at the limits, 2,048 bins beside m = 4096, one wave takes 49 KiB); per wave
+// histogram, prefix sums, table (u32) and founders (u16)
+inline uint32_t passage_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, uint32_t sort_slots,
+                              size_t* lds_bytes) {
+    return pass_waves(0, ((size_t)bins + bag_k + table_slots + (sort_slots >> 1)) * 4u, lds_bytes);
+}
+// ssa_snapstats: the workgroup's u64 sum of the saved states' histograms and, if any workgroup size leaves room for
+// it (*sample_hist_lds), of the samples' (else the waves add their samples' bins to global memory); per wave
+// histogram and table (u32)
+inline uint32_t snapstats_waves(uint32_t bins, uint32_t table_slots, size_t* lds_bytes, bool* sample_hist_lds) {
+    for (int in_lds = table_slots ? 1 : 0;; --in_lds) {
+        size_t lds = 0;
+        const uint32_t nw = pass_waves((size_t)bins * (in_lds ? 16u : 8u), ((size_t)bins + table_slots) * 4u, &lds);
+        if (lds <= kPassLdsMax || in_lds == 0) {
+            if (lds_bytes) *lds_bytes = lds;
+            if (sample_hist_lds) *sample_hist_lds = in_lds != 0;
+            return nw;
+        }
+    }
+}
 hipError_t launch_subsample(const SubsampleArgs& a, uint32_t blocks, hipStream_t stream);
-// The snapshot statistics pass (ssa_snapstats.hip): one wave per (replicate, snapshot); 1, 2 or 4 waves per workgroup,
-// as many as keep its dynamic LDS (lds_bytes) within 64 KiB. sample_hist_lds: whether the workgroup's sum of the
-// samples' histograms has room in LDS beside the rest (else the waves add their samples' bins to global memory).
-uint32_t snapstats_waves(uint32_t bins, uint32_t table_slots, size_t* lds_bytes, bool* sample_hist_lds);
 hipError_t launch_snapstats(const SnapStatsArgs& a, uint32_t blocks, hipStream_t stream);
-// The passage pass (ssa_passage.hip): one wave per replicate; 1, 2 or 4 waves per workgroup, as many as keep its
-// dynamic LDS (lds_bytes) within 64 KiB. The waves add their samples' bins to global memory (no workgroup histogram:
-// at the limits, 2,048 bins beside m = 4096, the table, the histogram and the founders take 49 KiB of one wave).
-uint32_t passage_sort_slots(uint32_t m);
-uint32_t passage_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, uint32_t sort_slots, size_t* lds_bytes);
 hipError_t launch_passage(const PassageArgs& a, uint32_t blocks, hipStream_t stream);
 // The reference-draws stepper (row store; ssa_refdraws.hip)
 const void* refdraws_kernel(int birth_death, int segregation);

@@ -1,13 +1,17 @@
-// ssa_sampledraw.hpp — the draws of subsample mapping v1 (include/ecdna_ssa.h), shared by the
-// end-of-run sample (ssa_subsample.hip) and the samples at the snapshots (ssa_snapstats.hip): the Lemire draw below N
-// on a tagged Philox stream, the wave's table of the positions drawn so far, and the position -> copy number lookup.
-// One 64-lane wave per population; every lane of the wave calls wave_sample_picks.
+// ssa_sampledraw.hpp — subsample mapping v1 (include/ecdna_ssa.h) for one population, shared by the
+// end-of-run sample (ssa_subsample.hip), the phase boundary of a passage run (ssa_passage.hip) and the samples at the
+// snapshots (ssa_snapstats.hip). The draws: the Lemire draw below N on a tagged Philox stream, the wave's table of the
+// positions drawn so far, and the position -> copy number lookup (wave_sample_picks). Around them: which positions
+// are drawn for a sample of m cells (sample_plan), the population's histogram and prefix sums from the final state
+// (wave_row_hist, wave_load_final_state) and the sample's statistics (wave_sample_stats).
+// One 64-lane wave per population; every lane of the wave calls the wave_ functions.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ssa_device.hpp"
+#include "ssa_launch.h"
 #include "ssa_wave.hpp"
 
 #pragma clang fp contract(off)
@@ -77,6 +81,80 @@ __device__ __forceinline__ bool sample_pos_k(const SamplePop& pop, uint32_t v, u
     if (j >= pop.nrow) return false;
     kk = pop.row[j];
     return true;
+}
+
+// What is drawn for a sample of m cells of a population of cells_all: the sample is the whole population (m >= N, no
+// draws), the mp = m picked positions, or what mp = N - m < m picked positions leave (comp). need_full: the sample is
+// made from the population's full histogram. bad: positions are u32 and 0xffffffff marks an empty table slot.
+struct SamplePlan {
+    bool whole, bad;
+    uint32_t N, mp;
+    bool comp, need_full;
+};
+__device__ __forceinline__ SamplePlan sample_plan(uint32_t m, uint64_t cells_all) {
+    const bool whole = (uint64_t)m >= cells_all;
+    const bool bad = !whole && cells_all >= 0xffffffffull;
+    const uint32_t N = (uint32_t)cells_all;
+    const uint32_t mp = (whole || bad) ? 0u : min(m, N - m);
+    const bool comp = mp != m;
+    return {whole, bad, N, mp, comp, whole || comp};
+}
+
+// row[0 .. n) counted into the wave's histogram wh (bins clip at `last`), 16 bytes (8 cells) per lane and load; ksum
+// gains the lane's sum of k. LDS atomics only: the caller orders them against its plain accesses of wh.
+__device__ __forceinline__ void wave_row_hist(const uint16_t* row, uint32_t n, uint32_t last, uint32_t* wh,
+                                              uint64_t& ksum, uint32_t lane) {
+    for (uint32_t c = lane * 8u; c < n; c += 512u) {
+        const uint4 v = *reinterpret_cast<const uint4*>(row + c);
+        const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (c + (uint32_t)j < n) {
+                const uint32_t kk = (wv[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
+                atomicAdd(&wh[kk < last ? kk : last], 1u);
+                ksum += kk;
+            }
+        }
+    }
+}
+
+// Step 1 of the mapping for replicate q of a final state (nm, np: its summary's N- and N+ cells): wh[bins] is zeroed;
+// the bin counters give pre[bag_k] and, when plan.need_full, enter wh and ksum; the cells the row holds follow
+// (never trust counters past the row, nor the summary past the row's memory: counters that hold more cells than the
+// summary set plan.bad), and lane 0 adds the N- cells. Returns the population for the lookup.
+// The one fence inside orders the plain stores that zero wh (and whatever plain LDS stores the caller made just before
+// the call, ssa_passage's founder padding) before other lanes' atomics on wh; pre is written plainly and wh by atomics
+// after it, so the caller fences (wave_sample_picks does, after clearing its table) before wh or pre are read.
+template <int BAG>
+__device__ __forceinline__ SamplePop wave_load_final_state(const FinalState& fs, uint32_t q, uint64_t nm, uint32_t np,
+                                                           uint32_t bins, SamplePlan& plan, uint32_t* wh, uint32_t* pre,
+                                                           uint64_t& ksum, uint32_t lane) {
+    const uint32_t last = bins - 1u;
+    const uint16_t* row = fs.rows + (uint64_t)q * fs.row_stride;
+    for (uint32_t b = lane; b < bins; b += 64u) wh[b] = 0u;
+    wave_sync_lds();
+    uint32_t small = 0;
+    if (BAG) {
+        for (uint32_t base = 0; base < fs.bag_k; base += 64u) {
+            const uint32_t b = base + lane;
+            const uint32_t cnt = b < fs.bag_k ? bag_counter<BAG>(fs.bags, q, fs.bag_k, b) : 0u;
+            if (plan.need_full && cnt) {
+                const uint32_t kk = b + 1u;
+                atomicAdd(&wh[kk < last ? kk : last], cnt);
+                ksum += (uint64_t)kk * cnt;
+            }
+            const uint32_t scan = wave_inclusive_scan(cnt, lane);
+            if (b < fs.bag_k) pre[b] = small + scan;
+            small += __shfl(scan, 63, 64);
+        }
+        if (!plan.whole && small > np) plan.bad = true;
+    }
+    const uint32_t nrow = (uint32_t)min((uint64_t)(np >= small ? np - small : 0u), fs.row_stride);
+    if (plan.need_full) {
+        wave_row_hist(row, nrow, last, wh, ksum, lane);
+        if (lane == 0) atomicAdd(&wh[0], (uint32_t)nm);
+    }
+    return {nm, pre, fs.bag_k, small, row, nrow};
 }
 
 // The wave's table of drawn positions for m' picks: 2 * pow2ceil(m') slots (load <= 1/2), hashed by the top bits of a
@@ -186,6 +264,29 @@ __device__ __forceinline__ bool wave_sample_picks(uint32_t* wh, uint32_t* tab, u
         wave_sync_lds();
     }
     return bad || count < mp || __any(lane_bad);
+}
+
+// Step 5 of the mapping: the statistics of the sample whose histogram wh holds (the full histogram, the picks, or the
+// full histogram less the picks), written to *out; its non-zero bins are added to `sums` (a workgroup histogram in LDS
+// or the set's row in global memory). ksum / psum: the lanes' sums of k over the full population / the picked positions.
+// bad (the guard, or a state the counters cannot account for): all-zero statistics, nothing added to sums.
+// Reads wh plainly and fences nothing: the caller's wave_sync_lds after the last atomics on wh comes before the call,
+// and another before wh is written again.
+__device__ __forceinline__ void wave_sample_stats(const SamplePlan& plan, bool bad, uint32_t m, uint64_t cells_all,
+                                                  uint32_t np, uint64_t ksum, uint64_t psum, const uint32_t* wh,
+                                                  unsigned long long* sums, uint32_t bins, const StatsTarget& target,
+                                                  uint32_t lane, ecdna_rep_stats_t* out) {
+    ksum = wave_sum(ksum);
+    psum = wave_sum(psum);
+    if (bad) {
+        if (lane == 0) *out = ecdna_rep_stats_t{};
+    } else {
+        const uint64_t cells = plan.whole ? cells_all : (uint64_t)m;
+        const uint64_t ks_sum = plan.whole ? ksum : (plan.comp ? ksum - psum : psum);
+        const uint64_t nplus_s = plan.whole ? (uint64_t)np : cells - (uint64_t)wh[0];
+        wave_rep_stats(wh, sums, bins, cells, ks_sum, nplus_s, target.has, target.cdf, target.mean, target.entropy,
+                       target.freq, lane, out);
+    }
 }
 
 }  // namespace ecdna

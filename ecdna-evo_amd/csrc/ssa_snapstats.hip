@@ -34,31 +34,31 @@ constexpr uint32_t kSnapBlock = 256;
 template <bool SHIST_LDS>
 __global__ void __launch_bounds__(kSnapBlock) ssa_snapstats(const SnapStatsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long lds[];
-    unsigned long long* hb = lds;            // [bins] the saved states' histograms
-    unsigned long long* hbs = lds + a.bins;  // [bins] the samples' (SHIST_LDS and m > 0)
+    const ChunkIds& ids = a.ids;
+    unsigned long long* hb = lds;              // [bins] the saved states' histograms
+    unsigned long long* hbs = lds + ids.bins;  // [bins] the samples' (SHIST_LDS and m > 0)
     const bool sampling = a.m != 0u;
-    const uint32_t n_hb = (sampling && SHIST_LDS) ? 2u * a.bins : a.bins;
+    const uint32_t n_hb = (sampling && SHIST_LDS) ? 2u * ids.bins : ids.bins;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t nw = blockDim.x >> 6;
-    const uint32_t wave_words = a.bins + a.table_slots;
+    const uint32_t wave_words = ids.bins + a.table_slots;
     uint32_t* wh = reinterpret_cast<uint32_t*>(lds + n_hb) + (size_t)wave * wave_words;  // [bins]
-    uint32_t* tab = wh + a.bins;                                                         // [table_slots]
-    const uint32_t r_begin = blockIdx.x * a.reps_per_block;
-    if (r_begin >= a.n) return;
-    const uint32_t r_end = min(a.n, r_begin + a.reps_per_block);
-    const uint32_t last = a.bins - 1;
+    uint32_t* tab = wh + ids.bins;                                                       // [table_slots]
+    const uint32_t r_begin = blockIdx.x * ids.reps_per_block;
+    if (r_begin >= ids.n) return;
+    const uint32_t r_end = min(ids.n, r_begin + ids.reps_per_block);
+    const uint32_t last = ids.bins - 1;
     const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
-    const uint32_t has_target = a.target_cdf ? 1u : 0u;
 
     uint32_t r = r_begin;
     while (r < r_end) {
-        const auto [set, seg_end] = set_segment(a.rid0, a.rid_stride, a.reps_per_set, r, r_end);
+        const auto [set, seg_end] = set_segment(ids.rid0, ids.rid_stride, ids.reps_per_set, r, r_end);
         for (uint32_t s = 0; s < a.n_snap; ++s) {
-            const uint64_t out_bins = ((uint64_t)s * a.n_sets + set) * a.bins;  // hist[s][set][0]
-            const double* cdf = has_target ? a.target_cdf + (uint64_t)s * a.bins : nullptr;
-            const double t_mean = has_target ? a.target_scalars[3u * s] : 0.0;
-            const double t_ent = has_target ? a.target_scalars[3u * s + 1u] : 0.0;
-            const double t_freq = has_target ? a.target_scalars[3u * s + 2u] : 0.0;
+            const uint64_t out_bins = ((uint64_t)s * a.n_sets + set) * ids.bins;  // hist[s][set][0]
+            const StatsTarget target = a.target_cdf ? StatsTarget{a.target_cdf + (uint64_t)s * ids.bins,
+                                                                  a.target_scalars[3u * s], a.target_scalars[3u * s + 1u],
+                                                                  a.target_scalars[3u * s + 2u], 1u}
+                                                    : StatsTarget{};
             for (uint32_t b = tid; b < n_hb; b += blockDim.x) lds[b] = 0ull;
             __syncthreads();
             unsigned long long* sample_sum =
@@ -72,73 +72,44 @@ __global__ void __launch_bounds__(kSnapBlock) ssa_snapstats(const SnapStatsArgs 
                 const uint32_t np = taken ? (uint32_t)min(meta->nplus, a.snap_stride) : 0u;
                 const uint64_t cells_all = nm + (uint64_t)np;
                 const uint16_t* row = a.snap_rows + pair * a.snap_stride;
-                for (uint32_t b = lane; b < a.bins; b += 64u) wh[b] = 0u;
+                for (uint32_t b = lane; b < ids.bins; b += 64u) wh[b] = 0u;
                 wave_sync_lds();
 
                 // 1. the saved state's histogram and statistics
                 uint64_t ksum = 0;
-                for (uint32_t c = lane * 8u; c < np; c += 512u) {
-                    const uint4 v = *reinterpret_cast<const uint4*>(row + c);
-                    const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        if (c + (uint32_t)j < np) {
-                            const uint32_t kk = (wv[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
-                            atomicAdd(&wh[kk < last ? kk : last], 1u);
-                            ksum += kk;
-                        }
-                    }
-                }
+                wave_row_hist(row, np, last, wh, ksum, lane);
                 if (lane == 0 && nm) atomicAdd(&wh[0], (uint32_t)nm);
                 wave_sync_lds();
-                ksum = wave_sum(ksum);
-                wave_rep_stats(wh, hb, a.bins, cells_all, ksum, np, has_target, cdf, t_mean, t_ent, t_freq, lane,
-                               a.stats + pair);
-                if (!sampling) {
-                    wave_sync_lds();  // wh is zeroed again for the wave's next pair
-                    continue;
-                }
+                wave_rep_stats(wh, hb, ids.bins, cells_all, wave_sum(ksum), np, target.has, target.cdf, target.mean,
+                               target.entropy, target.freq, lane, a.stats + pair);
 
                 // 2. the sample: the whole population (m >= N; a snapshot not taken has N = 0), the picked positions
                 // (m' = m) or what they leave of the histogram above (m' < m)
-                const bool whole = (uint64_t)a.m >= cells_all;
-                if (whole) {
-                    wave_rep_stats(wh, sample_sum, a.bins, cells_all, ksum, np, has_target, cdf, t_mean, t_ent, t_freq,
-                                   lane, a.sample_stats + pair);
-                    wave_sync_lds();
-                    continue;
+                if (sampling) {
+                    const SamplePlan plan = sample_plan(a.m, cells_all);
+                    uint64_t psum = 0;  // sum of k over the picked positions
+                    bool bad = plan.bad;
+                    if (!plan.whole) {
+                        wave_sync_lds();  // the statistics above have read wh
+                        if (!plan.comp) {
+                            for (uint32_t b = lane; b < ids.bins; b += 64u) wh[b] = 0u;
+                            wave_sync_lds();
+                        }
+                        if (!bad) {
+                            const uint64_t rid = ids.rid0 + (uint64_t)q * ids.rid_stride;
+                            const SamplePop pop{nm, nullptr, 0u, 0u, row, np};
+                            bad = wave_sample_picks<0>(wh, tab, a.table_slots, pop, plan.N, plan.mp, plan.comp, last,
+                                                       sample_stream_tag(s + 1u), rid, k0, k1, lane, psum);
+                        }
+                        wave_sync_lds();
+                    }
+                    wave_sample_stats(plan, bad, a.m, cells_all, np, ksum, psum, wh, sample_sum, ids.bins, target, lane,
+                                      a.sample_stats + pair);
                 }
-                bool bad = cells_all >= 0xffffffffull;  // positions are u32, 0xffffffff marks an empty slot
-                const uint32_t N = (uint32_t)cells_all;
-                const uint32_t mp = bad ? 0u : min(a.m, N - a.m);
-                const bool comp = mp != a.m;
-                wave_sync_lds();  // the statistics above have read wh
-                if (!comp) {
-                    for (uint32_t b = lane; b < a.bins; b += 64u) wh[b] = 0u;
-                    wave_sync_lds();
-                }
-                uint64_t psum = 0;  // sum of k over the picked positions
-                if (!bad) {
-                    const uint64_t rid = a.rid0 + (uint64_t)q * a.rid_stride;
-                    const SamplePop pop{nm, nullptr, 0u, 0u, row, np};
-                    bad = wave_sample_picks<0>(wh, tab, a.table_slots, pop, N, mp, comp, last, sample_stream_tag(s + 1u),
-                                               rid, k0, k1, lane, psum);
-                }
-                wave_sync_lds();
-                psum = wave_sum(psum);
-                if (bad) {  // the guard: all-zero sample statistics, nothing added to the samples' histogram
-                    if (lane == 0) a.sample_stats[pair] = ecdna_rep_stats_t{};
-                } else {
-                    const uint64_t cells = (uint64_t)a.m;
-                    const uint64_t ks_sum = comp ? ksum - psum : psum;
-                    const uint64_t nplus_s = cells - (uint64_t)wh[0];
-                    wave_rep_stats(wh, sample_sum, a.bins, cells, ks_sum, nplus_s, has_target, cdf, t_mean, t_ent,
-                                   t_freq, lane, a.sample_stats + pair);
-                }
-                wave_sync_lds();
+                wave_sync_lds();  // wh is zeroed again for the wave's next pair
             }
             __syncthreads();
-            for (uint32_t b = tid; b < a.bins; b += blockDim.x) {
+            for (uint32_t b = tid; b < ids.bins; b += blockDim.x) {
                 if (hb[b]) atomicAdd((unsigned long long*)&a.hist[out_bins + b], hb[b]);
                 if (SHIST_LDS && sampling && hbs[b]) atomicAdd((unsigned long long*)&a.sample_hist[out_bins + b], hbs[b]);
             }
@@ -150,30 +121,13 @@ __global__ void __launch_bounds__(kSnapBlock) ssa_snapstats(const SnapStatsArgs 
 
 }  // namespace
 
-uint32_t snapstats_waves(uint32_t bins, uint32_t table_slots, size_t* lds_bytes, bool* sample_hist_lds) {
-    // with the samples' workgroup histogram in LDS if any workgroup size leaves room for it; then 1, 2 or 4 waves
-    // per workgroup, as many as keep the workgroup within 64 KiB of dynamic LDS
-    for (int in_lds = table_slots ? 1 : 0; in_lds >= 0; --in_lds) {
-        for (uint32_t nw = kSnapBlock / 64u; nw >= 1u; nw >>= 1) {
-            const size_t lds = (size_t)bins * (in_lds ? 2u : 1u) * sizeof(unsigned long long) +
-                               (size_t)nw * ((size_t)bins + table_slots) * sizeof(uint32_t);
-            if (lds <= 65536u || (nw == 1u && in_lds == 0)) {
-                if (lds_bytes) *lds_bytes = lds;
-                if (sample_hist_lds) *sample_hist_lds = in_lds != 0;
-                return nw;
-            }
-        }
-    }
-    return 1u;
-}
-
 hipError_t launch_snapstats(const SnapStatsArgs& a, uint32_t blocks, hipStream_t stream) {
     SnapStatsArgs copy = a;
     void* args[] = {&copy};
     size_t lds = 0;
     bool in_lds = false;
-    const uint32_t nw = snapstats_waves(a.bins, a.table_slots, &lds, &in_lds);
-    if (lds > 65536u) return hipErrorInvalidValue;
+    const uint32_t nw = snapstats_waves(a.ids.bins, a.table_slots, &lds, &in_lds);
+    if (lds > kPassLdsMax) return hipErrorInvalidValue;
     const void* fn = in_lds ? (const void*)ssa_snapstats<true> : (const void*)ssa_snapstats<false>;
     return hipLaunchKernel(fn, dim3(blocks), dim3(nw * 64u), args, lds, stream);
 }

@@ -1,5 +1,6 @@
-// ssa_wave.hpp — the wave-level pieces the end-of-run kernels share (ssa_hist.hip, ssa_subsample.hip; wave_sum also
-// the development counters of ssa_refdraws.hip): wave reductions and the inclusive scan, the wave's LDS ordering
+// ssa_wave.hpp — the wave-level pieces the end-of-run kernels share (ssa_hist.hip, ssa_subsample.hip, ssa_passage.hip,
+// ssa_snapstats.hip, the last three through ssa_sampledraw.hpp too; wave_sum also the development counters of
+// ssa_refdraws.hip): wave reductions and the inclusive scan, the wave's LDS ordering
 // point, a chunk's parameter-set segments, the bin-counter read, and the one routine for
 // the per-replicate ABC statistics. Plain functions over one 64-lane wave; every lane of the wave calls them.
 #pragma once

@@ -34,7 +34,7 @@ PB_RATES = ((1.0, 1.0, 0.0, 0.0), (1.0, 1.5, 0.0, 0.0))
 DYING = ((1.0, 1.0, 1.1, 1.1), (0.8, 1.0, 1.0, 1.3))  # d > b: extinctions
 
 
-def _targets():
+def _targets(G=G, BINS=BINS):
     rng = np.random.default_rng(17)
     t = rng.integers(0, 60, (G, BINS)).astype(np.uint64)
     t[:, 0] += 100
@@ -48,15 +48,16 @@ def _flags(store):
 
 
 def _base(store, kmax, process, seg, rates, **kw):
-    """The plain run's keywords (no passages, no sample): two parameter sets of 96 replicates."""
+    """The plain run's keywords (no passages, no sample): two parameter sets of 96 replicates (keywords override)."""
     d = dict(seed=SEED, process=process, segregation=seg, rates=rates, reps_per_set=N // 2, n_replicates=N,
              max_cells=MAX_CELLS, hist_bins=BINS, cell_cap=4096, flags=_flags(store), bin_kmax=kmax)
     d.update(kw)
     return d
 
 
-def _passage_spec(base, m, **kw):
-    return abi.RunSpec(**{**base, "n_passages": G, "passage_cells": m, "passage_targets": _targets(), **kw})
+def _passage_spec(base, m, G=G, **kw):
+    targets = _targets(G, base["hist_bins"])
+    return abi.RunSpec(**{**base, "n_passages": G, "passage_cells": m, "passage_targets": targets, **kw})
 
 
 # (id, store, K, process, segregation, rates, m, extra spec keywords)
@@ -74,6 +75,12 @@ CASES = [
     ("bins32-large-k-founders", "bins", 32, abi.PURE_BIRTH, abi.SEG_BINOMIAL, PB_RATES, 40, dict(init={40: 3})),
     ("bins32-large-k-cell-cap", "bins", 32, abi.PURE_BIRTH, abi.SEG_BINOMIAL, PB_RATES, 40,
      dict(init={1: 5, 40: 3}, big_cap=24)),
+    # K = 256: the prefix sums of the counters take four 64-lane blocks (u16 counters at cell_cap = 4096); the 300-copy
+    # cell lies above K, so both the counters and the large-k row are sampled
+    ("bins256-bd-binomial-picks", "bins", 256, abi.BIRTH_DEATH, abi.SEG_BINOMIAL, BD_RATES, 40,
+     dict(init={1: 3, 300: 1})),
+    ("bins256-bd-deterministic-complement", "bins", 256, abi.BIRTH_DEATH, abi.SEG_DETERMINISTIC, BD_RATES, 200,
+     dict(init={1: 3, 300: 1})),
 ]
 _CHAINS = {}
 
@@ -90,12 +97,13 @@ def _sum_sets(per_rep, sets, rps):
     return out
 
 
-def _chain(oracle_mod, key, base, m):
+def _chain(oracle_mod, key, base, m, N=N, G=G, MAX_CELLS=MAX_CELLS, BINS=BINS):
     """The oracle chain of a case (computed once, shared, left unchanged): per phase the oracle's summaries, histogram
     [sets][bins], totals [sets] and rows, and the restatements' statistics, sample statistics and sample histogram."""
     if key in _CHAINS:
         return _CHAINS[key]
-    targets = _targets()
+    assert (base["n_replicates"], base["max_cells"], base["hist_bins"]) == (N, MAX_CELLS, BINS)
+    targets = _targets(G, BINS)
     sets, rps = len(base["rates"]), base["reps_per_set"]
     rates_of = [base["rates"][i // rps] for i in range(N)]
     phases = []
@@ -124,7 +132,8 @@ def _chain(oracle_mod, key, base, m):
 
 
 def _check_stats(got, want, tag):
-    for i in range(N):
+    assert len(got) == len(want)
+    for i in range(len(want)):
         assert int(got[i]["cells"]) == want[i]["cells"], f"{tag} replicate {i}: cells"
         for f in FLOATS:
             np.testing.assert_allclose(got[i][f], want[i][f], rtol=RTOL, atol=ATOL, err_msg=f"{tag} replicate {i}: {f}")
@@ -178,6 +187,37 @@ def test_oracle_chain(engine_mod, oracle_mod, case):
         capped = s["error"] == abi.REP_ERR_CELL_CAP
         assert capped[0].any() and capped[1].any() and (cells[capped] > 0).all()
         assert (s["iters"][1:][capped[:-1]] > 0).any()  # their populations found phases that run
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("store,kmax", [("rows", 0), ("bins", 64)])
+def test_limits(engine_mod, oracle_mod, store, kmax):
+    """The pass at its LDS limit: the largest table and founder sort (m' = 4096 of 8,200 cells, 4,096 sort slots) beside
+    the largest histogram (2,048 bins), one wave per workgroup. Phase 0 samples by picks; phase 1 starts from 4,096
+    founders. The same oracle chain as test_oracle_chain, two phases of 64 replicates."""
+    n, phases, max_cells, bins, m = 64, 2, 8200, 2048, 4096
+    base = _base(store, kmax, abi.PURE_BIRTH, abi.SEG_BINOMIAL, PB_RATES, n_replicates=n, reps_per_set=n // 2,
+                 max_cells=max_cells, hist_bins=bins, cell_cap=None)
+    want = _chain(oracle_mod, f"limits-{store}", base, m, N=n, G=phases, MAX_CELLS=max_cells, BINS=bins)
+    ps = engine_mod.run(_passage_spec(base, m, G=phases), want_rows=True).passages
+    assert ps.summaries.shape == (phases, n) and ps.sample_hist.shape == (phases, 2, bins)
+    assert np.all(ps.summaries[0]["nminus"] + ps.summaries[0]["nplus"] == max_cells)
+    for ph in range(phases):
+        w = want[ph]
+        for f in abi.SUMMARY_DTYPE.names:
+            a, b = ps.summaries[ph][f], w["summaries"][f]
+            if f == "time":
+                a, b = a.view(np.uint64), b.view(np.uint64)
+            np.testing.assert_array_equal(a, b, err_msg=f"{store} phase {ph}: summaries.{f}")
+        np.testing.assert_array_equal(ps.hist[ph], w["hist"], err_msg=f"{store} phase {ph}: hist")
+        assert ps.totals[ph].tobytes() == w["totals"].tobytes(), f"{store} phase {ph}: totals"
+        _check_stats(ps.stats[ph], w["stats"], f"{store} phase {ph} stats")
+        _check_stats(ps.sample_stats[ph], w["sample_stats"], f"{store} phase {ph} sample stats")
+        assert np.all(ps.sample_stats[ph]["cells"] == m)
+        np.testing.assert_array_equal(ps.sample_hist[ph], w["sample_hist"], err_msg=f"{store} phase {ph}: sample hist")
+    # phase 1 started from the 4,096 cells of phase 0's sample
+    for i in range(n):
+        assert sum(want[0]["founders"][i].values()) == m
 
 
 @pytest.mark.gpu
