@@ -1,7 +1,7 @@
 // ssa_api.cpp — the C ABI of include/ecdna_ssa.h: parameter validation,
 // device-resident run contexts, chunking by HBM capacity, and launches of the
 // stepper and end-of-run kernels (ssa_kernels.hip, ssa_hist.hip, ssa_subsample.hip, ssa_snapstats.hip,
-// ssa_passage.hip).
+// ssa_passage.hip) and of the post-launch acceptance pass (ssa_accept.hip).
 //
 // This file replaces, for one GPU, the per-replicate driver loop of the
 // reference: run_simulations(idx) mapped by rayon over seed*10 .. seed*10+runs
@@ -239,6 +239,13 @@ struct Chunk {
     uint32_t admit_remaining = 0;
 };
 
+// A device buffer of the acceptance pass: it belongs to the context but not to `owned`, as it is allocated at the first
+// ecdna_ssa_ctx_accept that needs it and replaced by a larger one when a later call needs more.
+struct AcceptBuf {
+    void* ptr = nullptr;
+    uint64_t bytes = 0;
+};
+
 }  // namespace
 
 struct ecdna_ssa_ctx {
@@ -330,6 +337,12 @@ struct ecdna_ssa_ctx {
     hipStream_t last_stream = nullptr;
     std::vector<Chunk> chunks;
     bool launched = false;
+    // the acceptance pass (ecdna_ssa_ctx_accept): mask [n] u32, counts [Q][n_sets] u64, workgroup counts, and the list's
+    // ids [cap] and records [cap][T]; what the last call left for ecdna_ssa_ctx_download_accept (a launch invalidates it)
+    AcceptBuf acc_mask, acc_counts, acc_blocks, acc_ids, acc_list;
+    bool accept_valid = false;
+    uint32_t acc_rows = 0, acc_timepoints = 0, acc_list_row = 0;
+    uint64_t acc_list_cap = 0;  // entries of the device list: min(list_capacity, n_replicates)
 };
 
 namespace {
@@ -382,6 +395,8 @@ void free_ctx(ecdna_ssa_ctx* c) {
         for (auto& e : ch.ev)
             if (e) (void)hipEventDestroy(e);
     for (void* d : c->owned) (void)hipFree(d);
+    for (AcceptBuf* b : {&c->acc_mask, &c->acc_counts, &c->acc_blocks, &c->acc_ids, &c->acc_list})
+        if (b->ptr) (void)hipFree(b->ptr);
     delete c;
 }
 
@@ -1027,6 +1042,85 @@ int launch_chunk_phase(ecdna_ssa_ctx* c, size_t k, uint32_t g, hipStream_t st) {
     TRY(hipEventRecord(ev[2], st));
     return ECDNA_OK;
 }
+
+// ---- ecdna_ssa_ctx_accept: the source's records on the device and how they lie, then the pass's own buffers ----
+
+// What an ecdna_accept_source_t names in this context (ssa_launch.h AcceptArgs has the strides' meaning); ECDNA_E_STATE
+// under the conditions of the matching download.
+struct AcceptSource {
+    const ecdna_rep_stats_t* stats = nullptr;
+    const ecdna_rep_summary_t* summaries = nullptr;
+    uint64_t rep_stride = 1, tp_stride = 0, err_stride = 0;
+    uint32_t T = 1;
+    bool has_target = false;
+};
+int accept_source(const ecdna_ssa_ctx* c, uint32_t source, AcceptSource* out) {
+    const uint64_t n_run = std::max<uint64_t>(c->p.n_replicates, 1);
+    AcceptSource s;
+    s.summaries = c->d_summ;
+    // (a passage run scores its phases against their own targets, or the run's)
+    const bool run_target = c->target.has || (c->n_passages && c->d_pas_target_cdf);
+    switch (source) {
+        case ECDNA_ACCEPT_FINAL:
+            if (!c->d_stats) return fail(ECDNA_E_STATE, "accept.source FINAL: statistics need ECDNA_FLAG_REP_STATS");
+            s.stats = c->d_stats;
+            s.has_target = run_target;
+            break;
+        case ECDNA_ACCEPT_SAMPLE:
+            if (!c->d_sample_hist) return fail(ECDNA_E_STATE, "accept.source SAMPLE: the sample needs subsample_cells > 0");
+            s.stats = c->d_sample_stats;
+            s.has_target = run_target;
+            break;
+        case ECDNA_ACCEPT_SNAPSHOTS:
+        case ECDNA_ACCEPT_SNAPSHOT_SAMPLES: {
+            const bool samples = source == ECDNA_ACCEPT_SNAPSHOT_SAMPLES;
+            if (!c->snap_stats)
+                return fail(ECDNA_E_STATE, "accept.source SNAPSHOTS: snapshot statistics need ecdna_ssa_ext_t.snapshot_stats");
+            if (samples && !c->snap_m)
+                return fail(ECDNA_E_STATE, "accept.source SNAPSHOT_SAMPLES: the snapshot samples need "
+                                           "ecdna_ssa_ext_t.snapshot_subsample_cells > 0");
+            s.stats = samples ? c->d_snap_sample_stats : c->d_snap_stats;
+            s.T = c->p.n_snapshots;
+            s.rep_stride = s.T;
+            s.tp_stride = 1;
+            s.has_target = c->d_snap_target_cdf != nullptr;
+            break;
+        }
+        case ECDNA_ACCEPT_PASSAGES:
+        case ECDNA_ACCEPT_PASSAGE_SAMPLES:
+            if (!c->n_passages)
+                return fail(ECDNA_E_STATE, "accept.source PASSAGES: per-phase results need ecdna_ssa_ctx_create_passages");
+            s.stats = source == ECDNA_ACCEPT_PASSAGES ? c->d_pas_stats : c->d_pas_sample_stats;
+            s.summaries = c->d_pas_summ;
+            s.T = c->n_passages;
+            s.tp_stride = n_run;
+            s.err_stride = n_run;
+            s.has_target = run_target;
+            break;
+        default:
+            return fail(ECDNA_E_INVALID, "accept.source is not an ecdna_accept_source_t");
+    }
+    *out = s;
+    return ECDNA_OK;
+}
+
+// At least `bytes` in `b`. A larger buffer is allocated before the old one is freed (hipFree waits for the device, so
+// an earlier pass that still writes the old one has finished): a failure leaves the context as it was.
+int accept_reserve(AcceptBuf* b, uint64_t bytes, const char* what) {
+    if (bytes <= b->bytes) return ECDNA_OK;
+    void* ptr = nullptr;
+    const hipError_t e = hipMalloc(&ptr, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // (the context stays usable)
+        return fail(e == hipErrorOutOfMemory ? ECDNA_E_NOMEM : ECDNA_E_HIP,
+                    std::string("ecdna_ssa_ctx_accept: the ") + what + " buffer (" + std::to_string(bytes) +
+                        " bytes) does not fit: " + hipGetErrorString(e));
+    }
+    if (b->ptr) (void)hipFree(b->ptr);
+    b->ptr = ptr;
+    b->bytes = bytes;
+    return ECDNA_OK;
+}
 }  // namespace
 
 // library-internal entry points for ssa_comm.cpp (the RCCL reduction)
@@ -1173,6 +1267,7 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
     }
     c->last_stream = st;
     c->launched = true;
+    c->accept_valid = false;  // (the acceptance pass's results were the previous launch's)
     return ECDNA_OK;
 }
 
@@ -1380,6 +1475,123 @@ int ecdna_ssa_ctx_download_passages(ecdna_ssa_ctx* c, ecdna_rep_summary_t* out_s
     if (out_sample_stats && n) TRY(to_host(out_sample_stats, c->d_pas_sample_stats, G * n));
     if (out_hist) TRY(to_host(out_hist, c->d_pas_hist, hb));
     if (out_sample_hist) TRY(to_host(out_sample_hist, c->d_pas_sample_hist, hb));
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_accept(ecdna_ssa_ctx* c, const ecdna_ssa_accept_t* a) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!a) return fail(ECDNA_E_INVALID, "accept is NULL");
+    if (a->struct_size != sizeof(ecdna_ssa_accept_t))
+        return fail(ECDNA_E_INVALID, "accept.struct_size must be sizeof(ecdna_ssa_accept_t)");
+    if (a->source > (uint32_t)ECDNA_ACCEPT_PASSAGE_SAMPLES)
+        return fail(ECDNA_E_INVALID, "accept.source is not an ecdna_accept_source_t");
+    if (a->n_thresholds < 1u || a->n_thresholds > ecdna::kMaxAcceptRows)
+        return fail(ECDNA_E_INVALID, "accept.n_thresholds must be in [1, 32]");
+    if (a->list_threshold >= a->n_thresholds)
+        return fail(ECDNA_E_INVALID, "accept.list_threshold must be < n_thresholds");
+    if (!a->thresholds) return fail(ECDNA_E_INVALID, "accept.thresholds is NULL");
+    for (uint32_t q = 0; q < a->n_thresholds; ++q) {
+        const ecdna_accept_threshold_t& t = a->thresholds[q];
+        const double v[4] = {t.ks, t.mean_rel, t.entropy_rel, t.frequency_diff};
+        const char* names[4] = {"ks", "mean_rel", "entropy_rel", "frequency_diff"};
+        for (int k = 0; k < 4; ++k)
+            if (!(v[k] >= 0.0))
+                return fail(ECDNA_E_INVALID, "accept.thresholds[" + std::to_string(q) + "]." + names[k] +
+                                                 " must be >= 0 (+inf switches it off) and not NaN");
+    }
+    if (a->reserved) return fail(ECDNA_E_INVALID, "accept.reserved must be 0");
+    const ecdna_ssa_params_t& p = c->p;
+    if (p.n_replicates >= (1ull << 32)) return fail(ECDNA_E_INVALID, "accept: n_replicates must be < 2^32");
+    AcceptSource src;
+    TRY(accept_source(c, a->source, &src));
+    const uint64_t all = src.T >= 64u ? ~0ull : (1ull << src.T) - 1ull;
+    if (a->timepoint_mask & ~all)
+        return fail(ECDNA_E_INVALID, "accept.timepoint_mask has bits at or above T = " + std::to_string(src.T));
+    TRY(ctx_launched(c, "accept before launch"));
+    if (!src.has_target)
+        return fail(ECDNA_E_STATE, "accept: the source's statistics were computed without a target (every distance is "
+                                   "0: nothing could be rejected)");
+
+    const uint64_t n = p.n_replicates;
+    const uint32_t Q = a->n_thresholds;
+    const uint64_t list_cap = std::min<uint64_t>(a->list_capacity, n);
+    const uint32_t n_blocks = (uint32_t)((n + ecdna::kAcceptBlock - 1) / ecdna::kAcceptBlock);
+    c->accept_valid = false;
+    TRY(hipSetDevice(c->device));
+    TRY(accept_reserve(&c->acc_counts, (uint64_t)Q * p.n_param_sets * sizeof(uint64_t), "counts"));
+    if (n) TRY(accept_reserve(&c->acc_mask, n * sizeof(uint32_t), "mask"));
+    if (list_cap) {
+        TRY(accept_reserve(&c->acc_blocks, (uint64_t)n_blocks * sizeof(uint32_t), "workgroup counts"));
+        TRY(accept_reserve(&c->acc_ids, list_cap * sizeof(uint64_t), "list ids"));
+        TRY(accept_reserve(&c->acc_list, list_cap * src.T * sizeof(ecdna_rep_stats_t), "list records"));
+    }
+
+    hipStream_t st = c->last_stream;
+    TRY(hipMemsetAsync(c->acc_counts.ptr, 0, (uint64_t)Q * p.n_param_sets * sizeof(uint64_t), st));
+    if (n) {
+        ecdna::AcceptArgs k{};
+        k.stats = src.stats;
+        k.summaries = src.summaries;
+        k.rep_stride = src.rep_stride;
+        k.tp_stride = src.tp_stride;
+        k.err_stride = src.err_stride;
+        k.tmask = a->timepoint_mask ? a->timepoint_mask : all;
+        k.rid0 = p.first_replicate;
+        k.rid_stride = p.replicate_stride ? p.replicate_stride : 1u;
+        k.reps_per_set = p.reps_per_set;
+        k.n = (uint32_t)n;
+        k.T = src.T;
+        k.Q = Q;
+        k.n_sets = p.n_param_sets;
+        k.mask = static_cast<uint32_t*>(c->acc_mask.ptr);
+        k.counts = static_cast<unsigned long long*>(c->acc_counts.ptr);
+        k.list_q = a->list_threshold;
+        k.n_blocks = n_blocks;
+        k.block_counts = static_cast<uint32_t*>(c->acc_blocks.ptr);
+        k.list_capacity = list_cap;
+        k.ids = static_cast<uint64_t*>(c->acc_ids.ptr);
+        k.list_stats = static_cast<ecdna_rep_stats_t*>(c->acc_list.ptr);
+        for (uint32_t q = 0; q < Q; ++q) {
+            const ecdna_accept_threshold_t& t = a->thresholds[q];
+            k.thr[q][0] = t.ks;
+            k.thr[q][1] = t.mean_rel;
+            k.thr[q][2] = t.entropy_rel;
+            k.thr[q][3] = t.frequency_diff;
+        }
+        TRY(ecdna::launch_accept_mask(k, st));
+        if (list_cap) TRY(ecdna::launch_accept_list(k, st));
+    }
+    c->acc_rows = Q;
+    c->acc_timepoints = src.T;
+    c->acc_list_row = a->list_threshold;
+    c->acc_list_cap = list_cap;
+    c->accept_valid = true;
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_download_accept(ecdna_ssa_ctx* c, uint64_t* out_counts, uint32_t* out_mask,
+                                  uint64_t* out_n_accepted, uint64_t* out_ids,
+                                  ecdna_rep_stats_t* out_list_stats) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!c->launched || !c->accept_valid)
+        return fail(ECDNA_E_STATE, "download_accept before accept (a launch invalidates the acceptance results)");
+    TRY(ctx_drain(c));
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t* d_counts = static_cast<const uint64_t*>(c->acc_counts.ptr);
+    // the number accepted under the list's row: the sum of its counts over the sets
+    std::vector<uint64_t> row(p.n_param_sets);
+    TRY(to_host(row.data(), d_counts + (uint64_t)c->acc_list_row * p.n_param_sets, p.n_param_sets));
+    uint64_t n_accepted = 0;
+    for (const uint64_t x : row) n_accepted += x;
+    if (out_n_accepted) *out_n_accepted = n_accepted;
+    if (out_counts) TRY(to_host(out_counts, d_counts, (uint64_t)c->acc_rows * p.n_param_sets));
+    if (out_mask && p.n_replicates)
+        TRY(to_host(out_mask, static_cast<const uint32_t*>(c->acc_mask.ptr), p.n_replicates));
+    const uint64_t listed = std::min<uint64_t>(n_accepted, c->acc_list_cap);
+    if (out_ids && listed) TRY(to_host(out_ids, static_cast<const uint64_t*>(c->acc_ids.ptr), listed));
+    if (out_list_stats && listed)
+        TRY(to_host(out_list_stats, static_cast<const ecdna_rep_stats_t*>(c->acc_list.ptr),
+                    listed * c->acc_timepoints));
     return ECDNA_OK;
 }
 

@@ -1,6 +1,7 @@
 // ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by the device
 // code (steppers: ssa_kernels.hip, ssa_refdraws.hip; end-of-run passes: ssa_hist.hip,
-// ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip) and ssa_api.cpp (the C ABI).
+// ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip; the acceptance pass: ssa_accept.hip) and
+// ssa_api.cpp (the C ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -189,6 +190,35 @@ struct PassageArgs {
     uint32_t sort_slots;                  // per-wave founder array (u16): passage_sort_slots(m)
 };
 
+// The acceptance pass over the whole run (ssa_accept.hip; ecdna_ssa_ctx_accept, acceptance mapping v1): ABC rejection
+// over statistics the context already holds. Replicate i's record of timepoint t is stats[i * rep_stride + t * tp_stride]
+// (one record: strides 1, 0; snapshots [n][S]: S, 1; passages [G][n]: 1, n) and the error word of its phase t is
+// summaries[i + t * err_stride].error (err_stride 0: one summary per replicate, whatever t). The thresholds travel in
+// the argument block itself: wave-uniform, read with scalar loads.
+constexpr uint32_t kMaxAcceptRows = 32;  // threshold rows Q: one bit each of a replicate's 32-bit mask
+constexpr int kAcceptBlock = 256;
+struct AcceptArgs {
+    const ecdna_rep_stats_t* stats;
+    const ecdna_rep_summary_t* summaries;
+    uint64_t rep_stride, tp_stride, err_stride;
+    uint64_t tmask;                       // participating timepoints (bits below T; never 0 for T > 0)
+    uint64_t rid0, rid_stride, reps_per_set;  // replicate i of the run has the global id rid0 + i * rid_stride
+    uint32_t n;                           // replicates of the run
+    uint32_t T;                           // timepoints of the source
+    uint32_t Q;                           // threshold rows, 1 .. kMaxAcceptRows
+    uint32_t n_sets;
+    uint32_t* mask;                       // [n]: bit q = accepted under row q
+    unsigned long long* counts;           // [Q][n_sets], zeroed before the launch
+    // the list of the replicates accepted under row list_q, in ascending i (ordered stream compaction)
+    uint32_t list_q;
+    uint32_t n_blocks;                    // workgroups of kAcceptBlock replicates: ceil(n / kAcceptBlock)
+    uint32_t* block_counts;               // [n_blocks]: accepted per workgroup, then (scanned) accepted before it
+    uint64_t list_capacity;               // entries ids / list_stats hold
+    uint64_t* ids;                        // [list_capacity] global ids
+    ecdna_rep_stats_t* list_stats;        // [list_capacity][T]
+    double thr[kMaxAcceptRows][4];        // per row: ks, mean_rel, entropy_rel, frequency_diff (+inf: off)
+};
+
 constexpr uint32_t kMaxSubsampleCells = 4096;  // LDS: 8 B of table per sampled cell and wave (<= 32 KiB)
 constexpr int kStepperBlock = 256;
 constexpr int kBinWideBlock = 64;  // bin store with 256 bins
@@ -274,6 +304,12 @@ inline uint32_t snapstats_waves(uint32_t bins, uint32_t table_slots, size_t* lds
 hipError_t launch_subsample(const SubsampleArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_snapstats(const SnapStatsArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_passage(const PassageArgs& a, uint32_t blocks, hipStream_t stream);
+// The acceptance pass (ssa_accept.hip): every replicate's mask and the per-set counts (a.counts zeroed on the stream
+// before it), and — launch_accept_list, after it on the same stream — the ordered list of the replicates accepted under
+// row a.list_q: per-workgroup counts, their exclusive scan by one workgroup, the scatter. Three launches, no workgroup
+// ever waits for another. a.n > 0.
+hipError_t launch_accept_mask(const AcceptArgs& a, hipStream_t stream);
+hipError_t launch_accept_list(const AcceptArgs& a, hipStream_t stream);
 // The reference-draws stepper (row store; ssa_refdraws.hip)
 const void* refdraws_kernel(int birth_death, int segregation);
 int refdraws_block();

@@ -122,6 +122,33 @@ class Passages(C.Structure):
     ]
 
 
+# ecdna_accept_source_t: the statistics ecdna_ssa_ctx_accept tests (added within ABI v13)
+ACCEPT_FINAL, ACCEPT_SAMPLE, ACCEPT_SNAPSHOTS, ACCEPT_SNAPSHOT_SAMPLES, ACCEPT_PASSAGES, ACCEPT_PASSAGE_SAMPLES = range(6)
+ACCEPT_MAX_THRESHOLDS = 32
+
+
+class AcceptThreshold(C.Structure):
+    """ecdna_accept_threshold_t: one threshold row, the largest accepted value of each distance (inf: off)."""
+
+    _fields_ = [("ks", C.c_double), ("mean_rel", C.c_double), ("entropy_rel", C.c_double),
+                ("frequency_diff", C.c_double)]
+
+
+class Accept(C.Structure):
+    """ecdna_ssa_accept_t: the argument block of ecdna_ssa_ctx_accept (added within ABI v13)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("source", C.c_uint32),
+        ("n_thresholds", C.c_uint32),
+        ("list_threshold", C.c_uint32),
+        ("thresholds", C.POINTER(AcceptThreshold)),
+        ("timepoint_mask", C.c_uint64),
+        ("list_capacity", C.c_uint64),
+        ("reserved", C.c_uint64),
+    ]
+
+
 _MASK64 = (1 << 64) - 1
 
 

@@ -40,6 +40,8 @@ EXPORTS = [
     "ecdna_ssa_ctx_download_sample",
     "ecdna_ssa_ctx_download_snapshot_stats",
     "ecdna_ssa_ctx_download_passages",
+    "ecdna_ssa_ctx_accept",
+    "ecdna_ssa_ctx_download_accept",
     "ecdna_ssa_ctx_download_rng_words",
     "ecdna_ssa_ctx_row_stride",
     "ecdna_ssa_ctx_geometry",
@@ -141,6 +143,13 @@ def lib():
         L.ecdna_ssa_ctx_create_passages.restype = C.c_int
         L.ecdna_ssa_ctx_download_passages.argtypes = [C.c_void_p] * 7
         L.ecdna_ssa_ctx_download_passages.restype = C.c_int
+    # (likewise added within v13: ABC rejection on the GPU; Context.accept raises on an earlier library)
+    if hasattr(L, "ecdna_ssa_ctx_accept"):
+        L.ecdna_ssa_ctx_accept.argtypes = [C.c_void_p, P(abi.Accept)]
+        L.ecdna_ssa_ctx_accept.restype = C.c_int
+        L.ecdna_ssa_ctx_download_accept.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint64), C.c_void_p,
+                                                    C.c_void_p]
+        L.ecdna_ssa_ctx_download_accept.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -243,6 +252,21 @@ class PassageResult:
         self.sample_hist = sample_hist
 
 
+class AcceptResult:
+    """What ecdna_ssa_ctx_accept keeps of a run (acceptance mapping v1, include/ecdna_ssa.h): counts [Q][n_sets] u64,
+    the replicates accepted per threshold row and parameter set (shards' arrays sum to the whole run's); mask [n] u32,
+    bit q = replicate i accepted under row q; n_accepted, the number accepted under the list's row (the whole count,
+    even above the capacity); ids [n_listed] u64 and stats [n_listed][T] abi.STATS_DTYPE, the global ids and the source's
+    records of the first n_listed = min(n_accepted, list_capacity) of them, in call order."""
+
+    def __init__(self, counts, mask, n_accepted, ids, stats):
+        self.counts = counts
+        self.mask = mask
+        self.n_accepted = n_accepted
+        self.ids = ids
+        self.stats = stats
+
+
 class Context:
     """A device-resident run (ecdna_ssa_ctx): create once, launch many times."""
 
@@ -313,6 +337,70 @@ class Context:
 
     def row_stride(self) -> int:
         return int(lib().ecdna_ssa_ctx_row_stride(self.h))
+
+    def accept_timepoints(self, source: int) -> int:
+        """T of an acceptance source: 1, the spec's snapshots, or its passages."""
+        if source in (abi.ACCEPT_SNAPSHOTS, abi.ACCEPT_SNAPSHOT_SAMPLES):
+            return int(self.params.n_snapshots)
+        if source in (abi.ACCEPT_PASSAGES, abi.ACCEPT_PASSAGE_SAMPLES):
+            return int(self.passages.n_passages) if self.passages is not None else 0
+        return 1
+
+    def accept_enqueue(self, source: int, thresholds, timepoints=None, list_threshold: int = 0,
+                       list_capacity: int = 0):
+        """Enqueue the acceptance pass on the stream of the last launch (ecdna_ssa_ctx_accept); download_accept
+        returns its results. Arguments as accept()."""
+        if not hasattr(lib(), "ecdna_ssa_ctx_accept"):
+            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_accept (ABC rejection on the GPU)")
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+        if thr.ndim != 2 or thr.shape[1] != 4:
+            raise ValueError("thresholds must be [Q][4]: ks, mean_rel, entropy_rel, frequency_diff per row")
+        mask = 0
+        for t in (timepoints if timepoints is not None else ()):
+            if not (0 <= int(t) < 64):
+                raise ValueError(f"timepoint {t} does not fit the ABI's 64-bit timepoint_mask")
+            mask |= 1 << int(t)
+        if timepoints is not None and mask == 0:
+            raise ValueError("timepoints is empty (None = all)")
+        for name, v, bits in (("list_threshold", list_threshold, 32), ("list_capacity", list_capacity, 64),
+                              ("source", source, 32), ("n_thresholds", thr.shape[0], 32)):
+            if not (0 <= int(v) < (1 << bits)):
+                raise ValueError(f"{name} = {v} does not fit the ABI's u{bits} field")
+        a = abi.Accept(struct_size=C.sizeof(abi.Accept), source=int(source), n_thresholds=thr.shape[0],
+                       list_threshold=int(list_threshold), timepoint_mask=mask, list_capacity=int(list_capacity))
+        a.thresholds = thr.ctypes.data_as(C.POINTER(abi.AcceptThreshold))
+        self._accept_shape = None
+        _check(lib().ecdna_ssa_ctx_accept(self.h, C.byref(a)), "ecdna_ssa_ctx_accept")
+        self._accept_shape = (thr.shape[0], self.accept_timepoints(int(source)),
+                              min(int(list_capacity), int(self.params.n_replicates)))
+
+    def download_accept(self) -> AcceptResult:
+        """The results of the last accept_enqueue (ecdna_ssa_ctx_download_accept; synchronises)."""
+        shape = getattr(self, "_accept_shape", None)
+        if shape is None:
+            raise EngineError("download_accept before accept")
+        Q, T, cap = shape
+        p = self.params
+        counts = np.zeros((Q, p.n_param_sets), dtype=np.uint64)
+        mask = np.zeros(p.n_replicates, dtype=np.uint32)
+        ids = np.zeros(cap, dtype=np.uint64)
+        stats = np.zeros((cap, T), dtype=abi.STATS_DTYPE)
+        n_acc = C.c_uint64()
+        _check(lib().ecdna_ssa_ctx_download_accept(self.h, counts.ctypes.data, mask.ctypes.data, C.byref(n_acc),
+                                                   ids.ctypes.data if cap else None,
+                                                   stats.ctypes.data if cap else None), "ecdna_ssa_ctx_download_accept")
+        listed = min(int(n_acc.value), cap)
+        return AcceptResult(counts, mask, int(n_acc.value), ids[:listed], stats[:listed])
+
+    def accept(self, source: int, thresholds, timepoints=None, list_threshold: int = 0,
+               list_capacity: int = 0) -> AcceptResult:
+        """ABC rejection on the GPU over the statistics of the last launch (acceptance mapping v1): `source` an
+        abi.ACCEPT_* constant; `thresholds` array-like [Q][4] in the order ks, mean_rel, entropy_rel, frequency_diff
+        (np.inf switches a statistic off); `timepoints` an iterable of the indices that take part (None: all);
+        the replicates accepted under row `list_threshold` are listed, at most `list_capacity` of them. May be called
+        any number of times after one launch."""
+        self.accept_enqueue(source, thresholds, timepoints, list_threshold, list_capacity)
+        return self.download_accept()
 
     def download(self, want_rows: bool = False) -> Result:
         p = self.params

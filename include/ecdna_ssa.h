@@ -43,7 +43,10 @@
 extern "C" {
 #endif
 
-/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): serial passaging —
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): ABC rejection on the
+ * GPU — the acceptance pass ecdna_ssa_ctx_accept / ecdna_ssa_ctx_download_accept over the statistics a context already
+ * holds (below; acceptance mapping v1). A context that never calls it allocates and launches nothing new.
+ * Added within v13 (additive: no layout and no existing function changes, the version stays 13): serial passaging —
  * every replicate regrown from its own sample on the GPU, the reference's cell-line strategy: the passage block
  * ecdna_ssa_passages_t, ecdna_ssa_ctx_create_passages and ecdna_ssa_ctx_download_passages (below; passage mapping v1).
  * ecdna_ssa_ctx_create_ext(p, ext, out) is ecdna_ssa_ctx_create_passages(p, ext, NULL, out).
@@ -463,6 +466,69 @@ int ecdna_ssa_ctx_download_sample(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats
 int ecdna_ssa_ctx_download_snapshot_stats(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats,
                                           ecdna_rep_stats_t* out_sample_stats, uint64_t* out_hist,
                                           uint64_t* out_sample_hist);
+/* ABC rejection on the GPU (added within ABI v13): a post-launch acceptance pass over the statistics a context already
+ * holds on the device. abc.md §Implementation asks for thresholds that can be tuned after the expensive simulations
+ * without re-running them: the statistics stay in HBM after a launch, so the pass may be called any number of times
+ * after one launch, with different thresholds. The host receives only what it keeps — the per-set counts (the
+ * posterior), a 4-byte mask per replicate, and the accepted replicates' ids and records — and a sharded sweep sums one
+ * small integer array over the GPUs instead of gathering every record.
+ *
+ * The source: which statistics are tested, and its T timepoints. */
+typedef enum {
+    ECDNA_ACCEPT_FINAL = 0,            /* ecdna_ssa_ctx_download_stats' array, T = 1 */
+    ECDNA_ACCEPT_SAMPLE = 1,           /* ecdna_ssa_ctx_download_sample's, T = 1 */
+    ECDNA_ACCEPT_SNAPSHOTS = 2,        /* download_snapshot_stats' out_stats, T = n_snapshots */
+    ECDNA_ACCEPT_SNAPSHOT_SAMPLES = 3, /* ... out_sample_stats, T = n_snapshots */
+    ECDNA_ACCEPT_PASSAGES = 4,         /* download_passages' out_stats, T = n_passages */
+    ECDNA_ACCEPT_PASSAGE_SAMPLES = 5   /* ... out_sample_stats, T = n_passages */
+} ecdna_accept_source_t;
+
+/* One threshold row: the largest accepted value of each of the four distances of ecdna_rep_stats_t. Each must be
+ * >= 0 (not NaN); +inf switches that statistic off. */
+typedef struct { double ks, mean_rel, entropy_rel, frequency_diff; } ecdna_accept_threshold_t;
+
+/* Acceptance mapping v1. Replicate i of the call is accepted under threshold row q iff both hold:
+ *  1. It is error-free: for the first four sources summaries[i].error == 0 (ecdna_ssa_ctx_download's summaries); for
+ *     the passage sources error == 0 in the summary of every participating phase (ecdna_ssa_ctx_download_passages').
+ *  2. For every participating timepoint t and each of the four distances x: thr[q].x == +inf, or d[i][t].x <= thr[q].x.
+ *     A distance equal to its threshold passes. A NaN distance fails unless the threshold is +inf.
+ * A snapshot that was not taken and an extinct phase need no special case: both are scored as an empty population
+ * (ks = 1.0) already. */
+typedef struct {
+    uint32_t struct_size;        /* sizeof(ecdna_ssa_accept_t), else ECDNA_E_INVALID */
+    uint32_t source;             /* ecdna_accept_source_t */
+    uint32_t n_thresholds;       /* Q, 1 .. 32 */
+    uint32_t list_threshold;     /* q < Q: the row whose accepted replicates are listed */
+    const ecdna_accept_threshold_t* thresholds; /* host, [Q] */
+    uint64_t timepoint_mask;     /* bit t = timepoint t takes part; 0 = all T */
+    uint64_t list_capacity;      /* records the list may hold; 0 = no list */
+    uint64_t reserved;           /* must be 0 */
+} ecdna_ssa_accept_t;
+
+/* Enqueue the acceptance pass on the stream of the last launch. Asynchronous; a later call replaces the results, a
+ * relaunch invalidates them. The pass's buffers (mask, counts, workgroup counts, list) belong to the context: allocated
+ * at the first call that needs them, grown by later ones, freed at destroy.
+ * ECDNA_E_INVALID (the message names the field): NULL c or a, wrong struct_size, unknown source, n_thresholds outside
+ * 1 .. 32, list_threshold >= n_thresholds, NULL thresholds, a threshold that is negative or NaN, timepoint_mask bits at
+ * or above T, reserved != 0, n_replicates >= 2^32.
+ * ECDNA_E_STATE: before a launch; the context does not hold the source's statistics (whenever the matching download
+ * returns ECDNA_E_STATE); those statistics were computed without a target, so every distance is 0 and nothing could be
+ * rejected.
+ * ECDNA_E_NOMEM: the pass's buffers do not fit; the context stays usable and its other outputs intact. */
+int ecdna_ssa_ctx_accept(ecdna_ssa_ctx* c, const ecdna_ssa_accept_t* a);
+/* The results of the last ecdna_ssa_ctx_accept (ECDNA_E_STATE before one, and after a relaunch until the next).
+ * Synchronises, as the other downloads do. Any pointer may be NULL.
+ *  - out_counts[Q][n_param_sets]: accepted replicates of this call per threshold row and per global parameter set
+ *    s = r / reps_per_set. Shards' arrays sum to the whole run's.
+ *  - out_mask[n_replicates]: bit q is set iff replicate i is accepted under row q.
+ *  - out_n_accepted: the number accepted under list_threshold — the whole count, even above list_capacity.
+ *  - out_ids[list_capacity]: the global ids of the first min(n_accepted, list_capacity) accepted replicates, in
+ *    ascending call order (i ascending): the order is part of the contract. Entries past them are not written.
+ *  - out_list_stats[list_capacity][T]: the listed replicates' records of the source, all T timepoints in timepoint
+ *    order (whatever timepoint_mask): byte for byte the rows of the corresponding download. */
+int ecdna_ssa_ctx_download_accept(ecdna_ssa_ctx* c, uint64_t* out_counts, uint32_t* out_mask,
+                                  uint64_t* out_n_accepted, uint64_t* out_ids,
+                                  ecdna_rep_stats_t* out_list_stats);
 /* Reference draws (ECDNA_FLAG_REFERENCE_DRAWS, ABI v7): per replicate, the number of 32-bit words its ChaCha8
  * stream (seed_from_u64(seed), stream seed*10 + r) had handed out when it stopped — where the reference's
  * end-of-run subsampling continues the same rng (into_subsampled(nb, &mut rng), src/main.rs:110-123, 184-197;
