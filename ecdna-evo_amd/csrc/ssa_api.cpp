@@ -21,6 +21,7 @@
 
 #include "../../include/ecdna_ssa.h"
 #include "ssa_launch.h"
+#include "ssa_plan.hpp"
 
 namespace {
 
@@ -43,8 +44,6 @@ int rc_of(hipError_t e, const char* what) {
     do {                                                  \
         if (int _rc = rc_of((expr), #expr)) return _rc;   \
     } while (0)
-
-uint64_t round_up(uint64_t x, uint64_t m) { return (x + m - 1) / m * m; }
 
 struct InitOfSet {
     const uint16_t* copies;
@@ -226,17 +225,10 @@ void btpe_setup(uint64_t n_u, double* row) {
 }
 constexpr int kBtpeRow = 16;  // refdraws::kBtpeRow
 
-struct Chunk {
-    uint64_t first;  // local index of the first replicate
-    uint32_t n;
+// A chunk as planned (first, n, its grid, rotation's partition size, the drain control), and what the context adds.
+struct Chunk : ecdna::plan::ChunkPlan {
     std::vector<hipEvent_t> ev;  // per growth phase (one in an ordinary run): start, stepper done, passes done
-    // replicate rotation (bin store; 0 = off): partition size and the counters it starts from
-    uint32_t rot_n_pad = 0;
-    std::vector<ecdna::RotPart> rot_init;
-    // persistent grid of the chunk and its drain control (admit_slot 0xffffffff: off)
-    uint32_t blocks = 1;
-    uint32_t admit_slot = 0xffffffffu;
-    uint32_t admit_remaining = 0;
+    std::vector<ecdna::RotPart> rot_init;  // replicate rotation (rot_n_pad > 0): the counters it starts from
 };
 
 // A device buffer of the acceptance pass: it belongs to the context but not to `owned`, as it is allocated at the first
@@ -262,6 +254,7 @@ struct ecdna_ssa_ctx {
     // per-replicate final counters [chunk_reps][bin_k]
     uint32_t bin_k = 0;
     int bin_c32 = 0;
+    uint64_t bag_bytes = 0;  // bytes of one replicate's bin counters
     int bin_ilp = 0;  // the bin stepper's schedule: 0 default, 1 max-ILP (lone waves), 2 128-VGPR K = 64, 3 max-ILP paired lanes (ssa_launch.h)
     unsigned char* d_bags = nullptr;
     uint32_t stepper_block = ecdna::kStepperBlock;
@@ -365,29 +358,6 @@ int pick_device(int dev) {
     return ECDNA_OK;
 }
 
-uint64_t env_u64(const char* name, uint64_t dflt) {
-    const char* v = std::getenv(name);
-    if (!v || !*v) return dflt;
-    return std::strtoull(v, nullptr, 10);
-}
-
-// The bin stepper's instruction-schedule rule, a pure function of the run's shape and the kernels'
-// occupancies so that the CPU tests can walk any shape through it (ecdna_dev_bin_schedule, tests/test_host.py).
-// Returns ecdna_ssa_instance_t.schedule: 0 occupancy-first, 1 max-ILP, 2 the 128-VGPR build (K = 64 / u16), 3 max-ILP
-// paired lanes. pair_ok: birth-death without snapshots and a paired instance exists; pair_mode ECDNA_SSA_PAIR (0 off,
-// 1 pairs whenever possible, 2 auto); sched ECDNA_SSA_SCHED (0, 1, 2 auto, 3);
-// max_chunk the largest chunk's replicates; occ_def / occ_ilp workgroups per CU of the two builds.
-int bin_schedule_rule(bool pair_ok, uint64_t pair_mode, uint64_t sched, uint64_t max_chunk, uint32_t cus, bool k64u16,
-                      bool tf0, int occ_def, int occ_ilp, uint32_t stepper_block) {
-    if (pair_ok && (pair_mode == 1 ||
-                    (pair_mode == 2 && sched == 2 && max_chunk <= (uint64_t)cus * (ecdna::kStepperBlock / 2))))
-        return 3;
-    if (sched == 1 || (sched == 2 && max_chunk <= (uint64_t)cus * 256u)) return 1;
-    if (k64u16 && (sched == 3 || (sched == 2 && tf0 && max_chunk >= 4ull * cus * 4u * ecdna::kStepperBlock))) return 2;
-    if (sched == 2 && (occ_ilp >= occ_def || max_chunk < 4ull * (uint64_t)occ_def * cus * stepper_block)) return 1;
-    return 0;
-}
-
 void free_ctx(ecdna_ssa_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
@@ -437,8 +407,8 @@ int ctx_drain(ecdna_ssa_ctx* c) {
     return ECDNA_OK;
 }
 
-// ---- ecdna_ssa_ctx_create_passages, step by step (in this order: each step builds on the ones before, and the chunk
-// size depends on what is allocated before plan_chunks asks for the free memory) ----
+// ---- ecdna_ssa_ctx_create_passages, step by step (build_ctx has the order: the chunk size depends on what is allocated
+// before gather_facts asks for the free memory) ----
 
 // Sum of a target histogram (> 0 for a usable target), and for `count` of them ([count][bins]) what the kernels
 // compare against: the CDFs over the bins ([count][bins]) and the scalars ([count][3]: mean, entropy, N+ frequency;
@@ -466,15 +436,15 @@ void summarize_targets(const uint64_t* hists, uint64_t count, uint32_t bins, dou
     }
 }
 
-// The context's own copies of the caller's inputs, and what the parameters alone decide: strides and the cell store.
-void adopt_params(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
-                  const ecdna_ssa_passages_t* pas) {
+// The context's own copies of the caller's inputs, and what the parameters alone decide (ssa_plan.hpp run_shape):
+// strides and the cell store.
+ecdna::plan::RunShape adopt_params(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                                   const ecdna_ssa_passages_t* pas, const ecdna::plan::Knobs& knobs) {
     c->p = *p;
     c->device = p->device;
     if (pas) {
         c->n_passages = pas->n_passages;
         c->passage_m = pas->passage_cells;
-        c->founder_stride = round_up(pas->passage_cells, 64);
     }
     c->snap_stats = ext && ext->snapshot_stats;
     if (c->snap_stats) c->snap_m = ext->snapshot_subsample_cells;
@@ -493,23 +463,22 @@ void adopt_params(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa
     c->p.init_set_nminus = nullptr;
     c->p.stats_target_hist = nullptr;
 
-    c->row_stride = round_up(p->cell_cap, 64);
-    c->out_stride = c->row_stride;
-    if (p->flags & ECDNA_FLAG_BIN_STORE) {
-        c->big_cap = (p->big_cap && p->big_cap < p->cell_cap) ? p->big_cap : p->cell_cap;
-        c->row_stride = round_up(c->big_cap, 64);
-        c->bin_k = p->bin_kmax ? p->bin_kmax : 64;
-        // u16 counters hold at most 65535 cells per bin/group; K = 32 always uses u32 counters: the same LDS
-        // footprint as K = 64/u16 (144 B per lane), no 16-bit packing in the updates and the scan (C3:
-        // 119 ms against 126 ms with u16)
-        // (ECDNA_SSA_C32 = 1 forces u32 counters at any K: a development knob, results are the same)
-        c->bin_c32 = (p->cell_cap > 65535u || c->bin_k <= 32 || env_u64("ECDNA_SSA_C32", 0)) ? 1 : 0;
-        c->stepper_block = (uint32_t)ecdna::bin_stepper_block(c->bin_k);
-    }
+    ecdna::plan::RunShape s = ecdna::plan::run_shape(*p, c->snap_stats, c->n_passages, c->passage_m, knobs);
+    s.stepper_block = s.refdraws ? (uint32_t)ecdna::refdraws_block()
+                      : s.bin_k  ? (uint32_t)ecdna::bin_stepper_block(s.bin_k)
+                                 : (uint32_t)ecdna::kStepperBlock;
+    c->refdraws = s.refdraws;
+    c->founder_stride = s.founder_stride;
+    c->row_stride = s.row_stride;
+    c->out_stride = s.out_stride;
+    c->big_cap = s.big_cap;
+    c->bin_k = s.bin_k;
+    c->bin_c32 = s.bin_c32;
+    c->bag_bytes = s.bag_bytes;
+    c->stepper_block = s.stepper_block;
+    c->snap_rows_local = s.snap_rows_local;
+    return s;
 }
-
-// bytes of one replicate's bin counters
-uint64_t bag_bytes(const ecdna_ssa_ctx* c) { return (uint64_t)c->bin_k * (c->bin_c32 ? 4u : 2u); }
 
 int upload_inputs(ecdna_ssa_ctx* c) {
     hipDeviceProp_t prop;
@@ -599,47 +568,70 @@ int alloc_outputs(ecdna_ssa_ctx* c) {
     return ECDNA_OK;
 }
 
-// rows: one u16 row per replicate of the chunk; chunk bounded by free HBM. Then the chunks, their events and their
-// start order.
-int plan_chunks(ecdna_ssa_ctx* c, const float* set_cost_hint) {
-    const ecdna_ssa_params_t& p = c->p;
-    const uint64_t n = p.n_replicates;
-    const uint64_t rot_bytes = c->bin_k ? ecdna::kParkVecs * 16u + 4u : 0u;  // parked scalars + state word
-    // (snapshot statistics without ECDNA_FLAG_SNAPSHOT_ROWS: the snapshot rows are the chunk's scratch, n_snapshots
-    // rows of out_stride cells per replicate of the chunk, so a large run chunks instead of failing)
-    c->snap_rows_local = c->snap_stats && !c->d_snap_rows;
-    const uint64_t snap_row_bytes = c->snap_rows_local ? p.n_snapshots * c->out_stride * sizeof(uint16_t) : 0u;
-    // (a passage run: the chunk's founders, one row of passage_cells and {n-, n+} per replicate)
-    const uint64_t founder_bytes = c->n_passages ? c->founder_stride * sizeof(uint16_t) + sizeof(uint2) : 0u;
-    const uint64_t row_bytes =
-        c->row_stride * sizeof(uint16_t) + bag_bytes(c) + rot_bytes + snap_row_bytes + founder_bytes;
+// The kernel a context of this shape launches under the row store's window variant / the bin stepper's schedule
+// (nullptr: the shape has no such instance), for the occupancy queries and ecdna_ssa_ctx_instance.
+const void* stepper_fn(const ecdna_ssa_ctx& c, int window, int schedule) {
+    const ecdna_ssa_params_t& p = c.p;
+    if (c.refdraws) return ecdna::refdraws_kernel(p.process, p.segregation);
+    if (c.bin_k) return ecdna::bin_stepper_kernel(p.process, p.segregation, c.bin_k, c.bin_c32, kernel_flags(c), schedule);
+    return ecdna::stepper_kernel(p.process, p.segregation, window, kernel_flags(c));
+}
+
+// What the planner asks of the runtime. The free memory is read here: after the run-sized outputs are allocated,
+// before the chunk's buffers.
+int gather_facts(const ecdna_ssa_ctx* c, const ecdna::plan::Knobs& knobs, ecdna::plan::DeviceFacts* f) {
+    f->cus = c->cus;
     size_t free_b = 0, total_b = 0;
     TRY(hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = (uint64_t)((double)free_b * 0.85);
-    uint64_t cap_budget = env_u64("ECDNA_SSA_MAX_ROW_BYTES", 0);
-    if (cap_budget) budget = std::min<uint64_t>(budget, cap_budget);
-    uint64_t fit = budget / row_bytes;
-    uint64_t max_chunk = env_u64("ECDNA_SSA_MAX_CHUNK", 0);
-    if (max_chunk) fit = std::min<uint64_t>(fit, max_chunk);
-    if (fit == 0) return fail(ECDNA_E_NOMEM, "one replicate row does not fit in device memory");
-    c->chunk_reps = std::min<uint64_t>(std::max<uint64_t>(n, 1), fit);
+    f->free_bytes = free_b;
+    if (hipDeviceGetAttribute(&f->xccs, hipDeviceAttributeNumberOfXccs, c->device) != hipSuccess) f->xccs = 0;
+    const int block = (int)c->stepper_block, window = knobs[ecdna::plan::WINDOW] ? 1 : 0;
+    if (c->refdraws) {
+        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&f->occ_refdraws, stepper_fn(*c, window, 0), block, 0));
+    } else if (c->bin_k) {
+        // every instance of the shape (a schedule without an instance of its own launches the default's)
+        for (int s = 0; s < 4; ++s) {
+            const void* fn = stepper_fn(*c, window, s);
+            if (fn && (s == 0 || fn != stepper_fn(*c, window, 0)))
+                TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&f->occ_bins[s], fn, block, 0));
+        }
+    } else {
+        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&f->occ_rows, stepper_fn(*c, window, 0), block, 0));
+    }
+    return ECDNA_OK;
+}
+
+// The chunk's buffers, the chunks with their events and start order, and the buffers of what the plan turned on.
+int alloc_plan(ecdna_ssa_ctx* c, const ecdna::plan::LaunchPlan& pl, const float* set_cost_hint) {
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t n = p.n_replicates;
+    if (pl.chunk_reps == 0) return fail(ECDNA_E_NOMEM, "one replicate row does not fit in device memory");
+    c->chunk_reps = pl.chunk_reps;
+    c->window = pl.window;
+    c->bin_ilp = pl.schedule;
+    c->stepper_blocks_cap = pl.stepper_blocks_cap;
+    c->rot_tick_log2 = pl.rot_tick_log2;
+    c->rot_park_min = pl.rot_park_min;
     TRY(ctx_alloc(c, &c->d_rows, c->chunk_reps * c->row_stride));
-    if (c->bin_k) TRY(ctx_alloc(c, &c->d_bags, c->chunk_reps * bag_bytes(c)));
+    if (c->bin_k) TRY(ctx_alloc(c, &c->d_bags, c->chunk_reps * c->bag_bytes));
     if (c->snap_rows_local) TRY(ctx_alloc(c, &c->d_snap_rows, c->chunk_reps * p.n_snapshots * c->out_stride));
     if (c->n_passages) {
         TRY(ctx_alloc(c, &c->d_founder_rows, c->chunk_reps * c->founder_stride));
         TRY(ctx_alloc(c, &c->d_founder_counts, c->chunk_reps));
     }
 
-    const uint64_t n_chunks = n ? (n + c->chunk_reps - 1) / c->chunk_reps : 0;
-    TRY(ctx_alloc(c, &c->d_heads, std::max<uint64_t>(n_chunks, 1)));
-    for (uint64_t k = 0; k < n_chunks; ++k) {
-        Chunk ch{};
-        ch.first = k * c->chunk_reps;
-        ch.n = (uint32_t)std::min<uint64_t>(c->chunk_reps, n - ch.first);
-        c->chunks.push_back(ch);
-        c->chunks.back().ev.assign(3u * std::max<uint32_t>(c->n_passages, 1u), nullptr);
-        for (auto& e : c->chunks.back().ev) TRY(hipEventCreate(&e));
+    TRY(ctx_alloc(c, &c->d_heads, std::max<uint64_t>(pl.chunks.size(), 1)));
+    for (const ecdna::plan::ChunkPlan& cp : pl.chunks) {
+        c->chunks.emplace_back();
+        Chunk& ch = c->chunks.back();
+        static_cast<ecdna::plan::ChunkPlan&>(ch) = cp;
+        ch.ev.assign(3u * std::max<uint32_t>(c->n_passages, 1u), nullptr);
+        for (auto& e : ch.ev) TRY(hipEventCreate(&e));
+        if (ch.rot_n_pad) {
+            ch.rot_init.assign(ecdna::kRotParts, ecdna::RotPart{});
+            for (uint32_t x = 0; x < ecdna::kRotParts; ++x)
+                ch.rot_init[x].waiting = ch.rot_init[x].fresh = ecdna::plan::rot_part_count(ch.n, x);
+        }
     }
 
     // start order (set_cost_hint): within each chunk, replicates of costlier sets first, then by id
@@ -657,15 +649,7 @@ int plan_chunks(ecdna_ssa_ctx* c, const float* set_cost_hint) {
         }
         TRY(ctx_upload(c, &c->d_order, order));
     }
-    return ECDNA_OK;
-}
 
-// persistent stepper grid: as many resident lanes as the occupancy allows; the bin stepper's instruction schedule
-int plan_stepper_grid(ecdna_ssa_ctx* c) {
-    const ecdna_ssa_params_t& p = c->p;
-    c->window = env_u64("ECDNA_SSA_WINDOW", 1) ? 1 : 0;
-    int per_cu = 0;
-    c->refdraws = (p.flags & ECDNA_FLAG_REFERENCE_DRAWS) != 0;
     if (c->refdraws) {
         std::vector<uint32_t> key(8);
         chacha_key_from_u64(p.seed, key.data());
@@ -673,155 +657,28 @@ int plan_stepper_grid(ecdna_ssa_ctx* c) {
         std::vector<double> bt((uint64_t)32768 * kBtpeRow, 0.0);
         for (uint64_t k = 10; k < 32768; ++k) btpe_setup(2 * k, bt.data() + k * kBtpeRow);
         TRY(ctx_upload(c, &c->d_ref_btpe, bt));
-        TRY(ctx_alloc(c, &c->d_rng_words, std::max<uint64_t>(p.n_replicates, 1)));
-        c->stepper_block = (uint32_t)ecdna::refdraws_block();
-        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, ecdna::refdraws_kernel(p.process, p.segregation), (int)c->stepper_block, 0));
-    } else if (c->bin_k) {
-        // Instruction schedule: with at most one wave of replicates per SIMD (every chunk within 256 lanes
-        // per CU) each wave runs alone and waits on its own dependencies, and the max-ILP schedule is faster
-        // (C2 8.6 -> 8.1 ms, C5 8-GPU shard 22.0 -> 21.1 s); with more, issue binds and the default schedule
-        // keeps 4 waves per SIMD (max-ILP: 3, C3 +8 %). The K = 64 / u16 kernel needs 130 VGPRs (3
-        // workgroups per CU); its 128-VGPR build fits 4 and pays once lanes run many replicates each (the
-        // whole C4 sweep on one GPU, 16 per lane: 834 -> 771 ms) but not with few (C4 8-GPU shard, 2 per
-        // lane: a longer drain, 127 -> 134 ms), so auto takes it from 4 replicates per lane of its grid on.
-        // ECDNA_SSA_SCHED = 0 default, 1 max-ILP, 2 auto, 3 the 128-VGPR build (K = 64 / u16; else 0).
-        uint64_t max_chunk = 0;
-        for (const auto& ch : c->chunks) max_chunk = std::max<uint64_t>(max_chunk, ch.n);
-        const uint32_t kflags = kernel_flags(*c);
-        const uint64_t sched = env_u64("ECDNA_SSA_SCHED", 2);
-        // (auto only without f32 time and the event hash: that variant spills 12 B at 128 VGPRs)
-        const bool k64u16 = c->bin_k == 64 && !c->bin_c32;
-        const bool tf0 = (kflags & ecdna::kRuntimeFlagMask) == 0;
-        // Where the max-ILP build keeps the default's occupancy (LDS bounds both: K = 32 / u32 and K = 64 / u32
-        // since the f32 draw mapping v6, K = 256) it is taken too: its schedule then costs no lanes (C3 78.3 ->
-        // 77.3 ms, C5 whole 31.9 -> 30.4 s, same box). With fewer than four replicates per lane of the default
-        // grid it is taken even at one workgroup per CU less (K = 64 / u16, 118 against 134 VGPRs since v6: the
-        // C4 8-GPU shard, two replicates per lane, 127 -> 119 ms), as the drain of the last replicates is
-        // latency-bound (profiles/r04d_v6_suite_and_sched_sweep.txt).
-        int occ_def = 0, occ_ilp = 0;
-        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &occ_def, ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kflags, 0),
-            (int)c->stepper_block, 0));
-        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &occ_ilp, ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kflags, 1),
-            (int)c->stepper_block, 0));
-        // Paired lanes: with at most half a wave of replicates per SIMD (the C5 8-GPU shard) the
-        // idle half of each wave computes the next event's Philox block and soft log in the N- fast-forward.
-        // Birth-death without snapshots (the fast-forward's domain). ECDNA_SSA_PAIR = 0 off, 1 whenever
-        // possible, 2 auto.
-        const uint64_t pair_mode = env_u64("ECDNA_SSA_PAIR", 2);
-        const bool pair_ok = p.process == ECDNA_BIRTH_DEATH && p.n_snapshots == 0 &&
-                             ecdna::bin_stepper_kernel_pair(p.segregation, c->bin_k, c->bin_c32, kflags) != nullptr;
-        c->bin_ilp = bin_schedule_rule(pair_ok, pair_mode, sched, max_chunk, c->cus, k64u16, tf0, occ_def, occ_ilp,
-                                       c->stepper_block);
-        // bin store: LDS-resident events, bounded by issue and LDS latency: every resident block helps
-        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu,
-            ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kflags, c->bin_ilp),
-            (int)c->stepper_block, 0));
-    } else {
-        TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-            &per_cu, ecdna::stepper_kernel(p.process, p.segregation, c->window, kernel_flags(*c)), ecdna::kStepperBlock, 0));
-        // Memory-level parallelism of the random row accesses saturates HBM at about 3 resident 256-lane
-        // blocks per CU (C3 sweep, DESIGN.md §8: 1/2/3/4/7 blocks -> 617/372/329/336/349 ms); fewer
-        // lanes also mean more replicates per lane and a shorter drain once the work queue is empty.
-        per_cu = std::min(per_cu, 3);
+        TRY(ctx_alloc(c, &c->d_rng_words, std::max<uint64_t>(n, 1)));
     }
-    uint64_t bpc = env_u64("ECDNA_SSA_BLOCKS_PER_CU", 0);
-    if (bpc) per_cu = (int)bpc;
-    if (per_cu < 1) per_cu = 1;
-    c->stepper_blocks_cap = (uint32_t)(per_cu * c->cus);
-    if (p.max_workgroups) c->stepper_blocks_cap = std::min(c->stepper_blocks_cap, p.max_workgroups);
-    uint64_t max_blocks = env_u64("ECDNA_SSA_MAX_BLOCKS", 0);  // testing: force lane refill
-    if (max_blocks) c->stepper_blocks_cap = (uint32_t)std::min<uint64_t>(c->stepper_blocks_cap, max_blocks);
-    return ECDNA_OK;
-}
-
-// Replicate rotation (bin store, 256-lane blocks): on when lanes have at least three
-// replicates each (ECDNA_SSA_ROTATE = 0 off, 1 on whenever possible, 2 auto); with two (C4 8-GPU shard)
-// the drain control is faster (74 ms against 84). Auto also leaves it off when the caller gave a cost
-// hint: the costliest-first start order then already balances the lanes, and parking only mixes the
-// order up again (C4 whole sweep, same box: 710-718 ms without rotation against 738-750 with it under
-// the 128-VGPR build, 747-749 against 792-805 under the default one). Results do not depend on it.
-// Byte offsets into bags/park are u32 in the kernel: chunks stay below 2 GiB of either.
-int plan_rotation(ecdna_ssa_ctx* c) {
-    uint64_t rot_mode = env_u64("ECDNA_SSA_ROTATE", 2);
-    const bool hinted = c->d_order != nullptr;
-    // Rotation hands a parked replicate only to lanes of the same partition, partition = XCC id mod
-    // kRotParts, and relies on those lanes sharing one L2 (the parked state is read with L1-bypassing
-    // loads). That holds when the agent has at most kRotParts XCCs (gfx950 SPX: 8, CPX: 1); otherwise
-    // two L2s would share a partition, so rotation stays off.
-    {
-        int xccs = 0;
-        if (hipDeviceGetAttribute(&xccs, hipDeviceAttributeNumberOfXccs, c->device) != hipSuccess || xccs < 1 ||
-            xccs > (int)ecdna::kRotParts)
-            rot_mode = 0;
-    }
-    c->rot_tick_log2 = (uint32_t)std::min<uint64_t>(env_u64("ECDNA_SSA_ROT_TICK", 10), 30);
-    bool any_rot = false;
-    for (auto& ch : c->chunks) {
-        const uint64_t need = (ch.n + c->stepper_block - 1) / c->stepper_block;
-        const uint64_t lanes = std::max<uint64_t>(1, std::min<uint64_t>(need, c->stepper_blocks_cap)) * c->stepper_block;
-        const bool ok = c->bin_k && c->stepper_block == ecdna::kStepperBlock &&
-                        (uint64_t)ch.n * std::max<uint64_t>(bag_bytes(c), ecdna::kParkVecs * 16u) < (1ull << 31);
-        if (!ok || rot_mode == 0 || (rot_mode == 2 && (ch.n < 3 * lanes || hinted))) continue;
-        const uint32_t per = (ch.n + ecdna::kRotParts - 1) / ecdna::kRotParts;
-        ch.rot_n_pad = (per + ecdna::kRotBlock - 1) / ecdna::kRotBlock * ecdna::kRotBlock;
-        ch.rot_init.assign(ecdna::kRotParts, ecdna::RotPart{});
-        for (uint32_t x = 0; x < ecdna::kRotParts; ++x) {
-            const int cnt = x < ch.n ? (int)((ch.n - x + ecdna::kRotParts - 1) / ecdna::kRotParts) : 0;  // r = x mod 8
-            ch.rot_init[x].waiting = cnt;
-            ch.rot_init[x].fresh = cnt;
-        }
-        any_rot = true;
-    }
-    if (any_rot) {
-        const uint64_t n_pad_max = (c->chunk_reps + ecdna::kRotParts - 1) / ecdna::kRotParts + ecdna::kRotBlock;
+    if (pl.any_rotation) {
         TRY(ctx_alloc(c, &c->d_rot_parts, ecdna::kRotParts));
-        TRY(ctx_alloc(c, &c->d_rot_flags, ecdna::kRotParts * n_pad_max));
+        TRY(ctx_alloc(c, &c->d_rot_flags, ecdna::kRotParts * pl.rot_n_pad_max));
         TRY(ctx_alloc(c, &c->d_rot_park, c->chunk_reps * ecdna::kParkVecs));
-        // park only while at least 1.5 partition grids' worth of replicates wait; below that the lanes run
-        // their replicates to the end (C3 sweep, DESIGN.md §5: 0.5 / 1 / 2 / 3 grids -> 88.2 / 87.2 / 87.1 / 97.5 ms)
-        const uint64_t lanes_all = (uint64_t)c->stepper_blocks_cap * c->stepper_block;
-        c->rot_park_min = (int32_t)env_u64("ECDNA_SSA_ROT_PARK_MIN",
-                                           std::max<uint64_t>(1, lanes_all * 3 / 2 / ecdna::kRotParts));
     }
     return ECDNA_OK;
 }
 
-// grid and drain control per chunk. Drain control (bin store, 256-lane blocks, one wave per SIMD per block):
-// when lanes run more than two replicates each, the youngest wave slot of every SIMD stops taking fresh
-// replicates once fewer than 1.5 grids' worth are left (C3: 105 -> 101 ms). ECDNA_SSA_ADMIT=0:
-// off. Rotation replaces it.
-void plan_drain_control(ecdna_ssa_ctx* c) {
-    for (auto& ch : c->chunks) {
-        // (paired lanes: owners only)
-        const uint32_t per_block = c->bin_ilp == 3 ? c->stepper_block / 2 : c->stepper_block;
-        const uint32_t need = (ch.n + per_block - 1) / per_block;
-        ch.blocks = std::max<uint32_t>(1, std::min<uint32_t>(need, c->stepper_blocks_cap));
-        const uint64_t lanes = (uint64_t)ch.blocks * c->stepper_block;
-        const uint32_t per_cu = c->cus ? (uint32_t)((ch.blocks + c->cus - 1) / c->cus) : 0u;
-        if (!ch.rot_n_pad && c->bin_k && c->stepper_block == 256 && per_cu >= 2 && ch.n > 2 * lanes &&
-            env_u64("ECDNA_SSA_ADMIT", 1)) {
-            const uint32_t slots = (uint32_t)std::min<uint64_t>(env_u64("ECDNA_SSA_ADMIT_SLOTS", 1), per_cu - 1);
-            ch.admit_slot = per_cu - std::max<uint32_t>(slots, 1u);
-            const uint64_t x8 = env_u64("ECDNA_SSA_ADMIT_X8", 12);  // eighths of a grid (tuning)
-            ch.admit_remaining = (uint32_t)std::min<uint64_t>(lanes * x8 / 8, ch.n);
-        }
-    }
-}
-
+// Gather, plan, allocate: what the run's shape and the device say, the plan they give (ssa_plan.hpp: every launch
+// decision of create), and the buffers the plan asks for.
 int build_ctx(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
               const ecdna_ssa_passages_t* pas) {
-    adopt_params(c, p, ext, pas);
+    const ecdna::plan::Knobs knobs = ecdna::plan::knobs_from_env();
+    const ecdna::plan::RunShape shape = adopt_params(c, p, ext, pas, knobs);
     TRY(upload_inputs(c));
     TRY(upload_targets(c, p, ext, pas));
     TRY(alloc_outputs(c));
-    TRY(plan_chunks(c, p->set_cost_hint));
-    TRY(plan_stepper_grid(c));
-    TRY(plan_rotation(c));
-    plan_drain_control(c);
+    ecdna::plan::DeviceFacts facts;
+    TRY(gather_facts(c, knobs, &facts));
+    TRY(alloc_plan(c, ecdna::plan::plan_launch(shape, facts, knobs), p->set_cost_hint));
     return ECDNA_OK;
 }
 
@@ -1148,8 +1005,8 @@ int ecdna_ssa_abi_version(void) { return ECDNA_SSA_ABI_VERSION; }
 // (development / test entry point, not part of include/ecdna_ssa.h: bin_schedule_rule for the CPU tests)
 int ecdna_dev_bin_schedule(int pair_ok, uint64_t pair_mode, uint64_t sched, uint64_t max_chunk, uint32_t cus,
                            int k64u16, int tf0, int occ_def, int occ_ilp, uint32_t stepper_block) {
-    return bin_schedule_rule(pair_ok != 0, pair_mode, sched, max_chunk, cus, k64u16 != 0, tf0 != 0, occ_def, occ_ilp,
-                             stepper_block);
+    return ecdna::plan::bin_schedule_rule(pair_ok != 0, pair_mode, sched, max_chunk, cus, k64u16 != 0, tf0 != 0, occ_def,
+                                          occ_ilp, stepper_block);
 }
 
 // (development / test entry point, not part of include/ecdna_ssa.h: the sampling passes' LDS plan of ssa_launch.h for
@@ -1310,13 +1167,11 @@ int ecdna_ssa_ctx_geometry(const ecdna_ssa_ctx* c, uint64_t* chunk_replicates, u
 
 int ecdna_ssa_ctx_instance(const ecdna_ssa_ctx* c, ecdna_ssa_instance_t* out) {
     if (!c || !out) return fail(ECDNA_E_INVALID, "ctx / out is NULL");
-    const ecdna_ssa_params_t& p = c->p;
     ecdna_ssa_instance_t r{};
-    const void* fn;
+    const void* fn = stepper_fn(*c, c->window, c->bin_ilp);
     if (c->refdraws) {
         r.kernel = ECDNA_KERNEL_REFDRAWS;
         r.schedule = -1;
-        fn = ecdna::refdraws_kernel(p.process, p.segregation);
     } else if (c->bin_k) {
         r.kernel = ECDNA_KERNEL_BINS;
         r.schedule = c->bin_ilp;
@@ -1324,13 +1179,11 @@ int ecdna_ssa_ctx_instance(const ecdna_ssa_ctx* c, ecdna_ssa_instance_t* out) {
         r.bin_kmax = c->bin_k;
         r.bin_c32 = (uint32_t)c->bin_c32;
         r.runtime_flags = (kernel_flags(*c) & ecdna::kRuntimeFlagMask) ? 1 : 0;
-        fn = ecdna::bin_stepper_kernel(p.process, p.segregation, c->bin_k, c->bin_c32, kernel_flags(*c), c->bin_ilp);
     } else {
         r.kernel = ECDNA_KERNEL_ROWS;
         r.schedule = -1;
         r.window = (uint32_t)c->window;
         r.runtime_flags = 1;
-        fn = ecdna::stepper_kernel(p.process, p.segregation, c->window, kernel_flags(*c));
     }
     for (const auto& ch : c->chunks) {
         r.rotation += ch.rot_n_pad ? 1 : 0;

@@ -169,3 +169,26 @@ def test_cli_extra_flag_table_matches_help():
     assert doc_flags == help_flags, (sorted(doc_flags - help_flags), sorted(help_flags - doc_flags))
     ref_row = next(ln for ln in table.splitlines() if ln.startswith("| `--draws"))
     assert "ChaCha8" in ref_row and "Philox side stream" not in ref_row
+
+
+def test_knob_table_names_the_planner_knobs(tmp_path):
+    """INTEGRATION.md §6 lists exactly the ECDNA_SSA_* variables the library reads (the planner's knob table,
+    ecdna-evo_amd/csrc/ssa_plan.hpp, printed by tests/native/plan_check.cpp), both ways."""
+    import shutil
+    import subprocess
+
+    import pytest
+
+    if shutil.which("hipcc") is None:
+        pytest.skip("hipcc absent")
+    from test_launch_plan import build_plan_check
+
+    out = subprocess.run([build_plan_check(tmp_path), "knobs"], capture_output=True, text=True, check=True)
+    knobs = set(out.stdout.split())
+    assert len(knobs) == 14 and all(k.startswith("ECDNA_SSA_") for k in knobs), knobs
+    with open(DOC) as f:
+        doc = f.read()
+    table = doc[doc.index("| variable | default | effect |"):]
+    table = table[:table.index("\n\n")]
+    doc_knobs = {name for ln in table.splitlines()[2:] for name in re.findall(r"`(ECDNA_SSA_[A-Z0-9_]+)`", ln.split("|")[1])}
+    assert doc_knobs == knobs, (sorted(doc_knobs - knobs), sorted(knobs - doc_knobs))
