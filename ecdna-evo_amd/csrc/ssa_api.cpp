@@ -22,6 +22,7 @@
 #include "../../include/ecdna_ssa.h"
 #include "ssa_launch.h"
 #include "ssa_plan.hpp"
+#include "ssa_select.hpp"
 
 namespace {
 
@@ -336,6 +337,13 @@ struct ecdna_ssa_ctx {
     bool accept_valid = false;
     uint32_t acc_rows = 0, acc_timepoints = 0, acc_list_row = 0;
     uint64_t acc_list_cap = 0;  // entries of the device list: min(list_capacity, n_replicates)
+    // the select passes (ecdna_ssa_ctx_select / _select_digits): the keys [4][n] u64 of one (source, timepoint mask),
+    // kept between passes and calls until a launch replaces the records they were made from, and one pass's histogram
+    // [4][kMaxSelectGroups][256] u64. Allocated at the first call, freed at destroy.
+    AcceptBuf sel_keys, sel_hist;
+    bool sel_keys_valid = false;
+    uint32_t sel_source = 0;
+    uint64_t sel_tmask = 0;
 };
 
 namespace {
@@ -365,7 +373,8 @@ void free_ctx(ecdna_ssa_ctx* c) {
         for (auto& e : ch.ev)
             if (e) (void)hipEventDestroy(e);
     for (void* d : c->owned) (void)hipFree(d);
-    for (AcceptBuf* b : {&c->acc_mask, &c->acc_counts, &c->acc_blocks, &c->acc_ids, &c->acc_list})
+    for (AcceptBuf* b : {&c->acc_mask, &c->acc_counts, &c->acc_blocks, &c->acc_ids, &c->acc_list, &c->sel_keys,
+                         &c->sel_hist})
         if (b->ptr) (void)hipFree(b->ptr);
     delete c;
 }
@@ -963,19 +972,106 @@ int accept_source(const ecdna_ssa_ctx* c, uint32_t source, AcceptSource* out) {
 
 // At least `bytes` in `b`. A larger buffer is allocated before the old one is freed (hipFree waits for the device, so
 // an earlier pass that still writes the old one has finished): a failure leaves the context as it was.
-int accept_reserve(AcceptBuf* b, uint64_t bytes, const char* what) {
+int accept_reserve(AcceptBuf* b, uint64_t bytes, const char* what, const char* who = "ecdna_ssa_ctx_accept") {
     if (bytes <= b->bytes) return ECDNA_OK;
     void* ptr = nullptr;
     const hipError_t e = hipMalloc(&ptr, bytes);
     if (e != hipSuccess) {
         (void)hipGetLastError();  // (the context stays usable)
         return fail(e == hipErrorOutOfMemory ? ECDNA_E_NOMEM : ECDNA_E_HIP,
-                    std::string("ecdna_ssa_ctx_accept: the ") + what + " buffer (" + std::to_string(bytes) +
+                    std::string(who) + ": the " + what + " buffer (" + std::to_string(bytes) +
                         " bytes) does not fit: " + hipGetErrorString(e));
     }
     if (b->ptr) (void)hipFree(b->ptr);
     b->ptr = ptr;
     b->bytes = bytes;
+    return ECDNA_OK;
+}
+
+// ---- ecdna_ssa_ctx_select / _select_digits: what both check after their own arguments, and one digit pass ----
+
+// The source's records and the participating timepoints, under the checks and in the order of ecdna_ssa_ctx_accept.
+// `who`: "select" or "select_digits", the prefix of the messages' field names.
+struct SelectSource {
+    AcceptSource src;
+    uint64_t tmask = 0;
+};
+int select_source(const ecdna_ssa_ctx* c, uint32_t source, uint64_t timepoint_mask, const std::string& who,
+                  SelectSource* out) {
+    if (source > (uint32_t)ECDNA_ACCEPT_PASSAGE_SAMPLES)
+        return fail(ECDNA_E_INVALID, who + ".source is not an ecdna_accept_source_t");
+    if (c->p.n_replicates >= (1ull << 32)) return fail(ECDNA_E_INVALID, who + ": n_replicates must be < 2^32");
+    TRY(accept_source(c, source, &out->src));
+    const uint32_t T = out->src.T;
+    const uint64_t all = T >= 64u ? ~0ull : (1ull << T) - 1ull;
+    if (timepoint_mask & ~all)
+        return fail(ECDNA_E_INVALID, who + ".timepoint_mask has bits at or above T = " + std::to_string(T));
+    TRY(ctx_launched(c, (who + " before launch").c_str()));
+    if (!out->src.has_target)
+        return fail(ECDNA_E_STATE, who + ": the source's statistics were computed without a target (every distance is "
+                                         "0: no quantile tells replicates apart)");
+    out->tmask = timepoint_mask ? timepoint_mask : all;
+    return ECDNA_OK;
+}
+
+// Replicates a workgroup of ssa_select_digits walks: eight rounds of its 256 lanes, so that the flush of its LDS table
+// to the global histogram is shared by 2,048 keys (the C4 sweep: 2,048 workgroups per distance).
+constexpr uint32_t kSelectRepsPerBlock = 8u * ecdna::kSelectBlock;
+
+// One digit pass: out_hist[x][j][d], j < K, for the prefixes[x * stride + j]. Makes the keys first unless the context
+// holds those of this source and mask. Synchronises.
+int select_pass(ecdna_ssa_ctx* c, uint32_t source, const SelectSource& s, uint32_t pass, uint32_t K,
+                const uint64_t* prefixes, uint32_t stride, uint64_t* out_hist, const char* who) {
+    namespace sel = ecdna::select;
+    const uint64_t n = c->p.n_replicates;
+    std::fill(out_hist, out_hist + (uint64_t)sel::kDistances * K * sel::kDigits, 0ull);
+    if (!n) return ECDNA_OK;
+    TRY(hipSetDevice(c->device));
+    hipStream_t st = c->last_stream;
+    const bool cached = c->sel_keys_valid && c->sel_source == source && c->sel_tmask == s.tmask;
+    if (!cached) {
+        c->sel_keys_valid = false;
+        TRY(accept_reserve(&c->sel_keys, sel::kDistances * n * sizeof(uint64_t), "keys", who));
+    }
+    constexpr uint64_t hist_words = (uint64_t)sel::kDistances * ecdna::kMaxSelectGroups * sel::kDigits;
+    TRY(accept_reserve(&c->sel_hist, hist_words * sizeof(uint64_t), "histogram", who));
+    if (!cached) {
+        ecdna::SelectKeyArgs k{};
+        k.stats = s.src.stats;
+        k.summaries = s.src.summaries;
+        k.rep_stride = s.src.rep_stride;
+        k.tp_stride = s.src.tp_stride;
+        k.err_stride = s.src.err_stride;
+        k.tmask = s.tmask;
+        k.keys = static_cast<uint64_t*>(c->sel_keys.ptr);
+        k.n = (uint32_t)n;
+        k.T = s.src.T;
+        TRY(ecdna::launch_select_keys(k, st));
+        c->sel_source = source;
+        c->sel_tmask = s.tmask;
+        c->sel_keys_valid = true;
+    }
+    ecdna::SelectArgs a{};
+    a.keys = static_cast<const uint64_t*>(c->sel_keys.ptr);
+    a.hist = static_cast<unsigned long long*>(c->sel_hist.ptr);
+    a.n = (uint32_t)n;
+    a.pass = pass;
+    a.reps_per_block = kSelectRepsPerBlock;
+    uint32_t group[sel::kDistances][sel::kMaxRanks];
+    for (uint32_t x = 0; x < sel::kDistances; ++x) {
+        uint64_t top[sel::kMaxRanks];
+        for (uint32_t j = 0; j < K; ++j) top[j] = sel::key_top(prefixes[(uint64_t)x * stride + j], pass);
+        a.n_groups[x] = sel::dedup(top, K, a.prefix[x], group[x]);
+    }
+    TRY(hipMemsetAsync(c->sel_hist.ptr, 0, hist_words * sizeof(uint64_t), st));
+    TRY(ecdna::launch_select_digits(a, st));
+    TRY(hipStreamSynchronize(st));
+    std::vector<uint64_t> dev(hist_words);
+    TRY(to_host(dev.data(), static_cast<const uint64_t*>(c->sel_hist.ptr), hist_words));
+    for (uint32_t x = 0; x < sel::kDistances; ++x)
+        for (uint32_t j = 0; j < K; ++j)
+            std::copy_n(dev.data() + ((uint64_t)x * ecdna::kMaxSelectGroups + group[x][j]) * sel::kDigits, sel::kDigits,
+                        out_hist + ((uint64_t)x * K + j) * sel::kDigits);
     return ECDNA_OK;
 }
 }  // namespace
@@ -1125,6 +1221,7 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
     c->last_stream = st;
     c->launched = true;
     c->accept_valid = false;  // (the acceptance pass's results were the previous launch's)
+    c->sel_keys_valid = false;  // (and the select passes' keys were made from its records)
     return ECDNA_OK;
 }
 
@@ -1445,6 +1542,60 @@ int ecdna_ssa_ctx_download_accept(ecdna_ssa_ctx* c, uint64_t* out_counts, uint32
     if (out_list_stats && listed)
         TRY(to_host(out_list_stats, static_cast<const ecdna_rep_stats_t*>(c->acc_list.ptr),
                     listed * c->acc_timepoints));
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_select_digits(ecdna_ssa_ctx* c, uint32_t source, uint64_t timepoint_mask, uint32_t pass,
+                                uint32_t n_prefixes, const uint64_t* prefixes, uint64_t* out_hist) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (pass >= ecdna::select::kPasses) return fail(ECDNA_E_INVALID, "select_digits.pass must be in [0, 7]");
+    if (n_prefixes < 1u || n_prefixes > ecdna::select::kMaxRanks)
+        return fail(ECDNA_E_INVALID, "select_digits.n_prefixes must be in [1, 32]");
+    if (!prefixes) return fail(ECDNA_E_INVALID, "select_digits.prefixes is NULL");
+    if (!out_hist) return fail(ECDNA_E_INVALID, "select_digits.out_hist is NULL");
+    SelectSource src;
+    TRY(select_source(c, source, timepoint_mask, "select_digits", &src));
+    return select_pass(c, source, src, pass, n_prefixes, prefixes, n_prefixes, out_hist, "ecdna_ssa_ctx_select_digits");
+}
+
+int ecdna_ssa_ctx_select(ecdna_ssa_ctx* c, const ecdna_ssa_select_t* s, uint64_t* out_population, uint64_t* out_ranks,
+                         double* out_values, uint64_t* out_counts_le) {
+    namespace sel = ecdna::select;
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!s) return fail(ECDNA_E_INVALID, "select is NULL");
+    if (s->struct_size != sizeof(ecdna_ssa_select_t))
+        return fail(ECDNA_E_INVALID, "select.struct_size must be sizeof(ecdna_ssa_select_t)");
+    if (s->source > (uint32_t)ECDNA_ACCEPT_PASSAGE_SAMPLES)
+        return fail(ECDNA_E_INVALID, "select.source is not an ecdna_accept_source_t");
+    const uint32_t K = s->n_ranks;
+    if (K < 1u || K > sel::kMaxRanks) return fail(ECDNA_E_INVALID, "select.n_ranks must be in [1, 32]");
+    if ((s->ranks != nullptr) == (s->fractions != nullptr))
+        return fail(ECDNA_E_INVALID, "exactly one of select.ranks and select.fractions must be given");
+    for (uint32_t j = 0; j < K; ++j) {
+        if (s->ranks && s->ranks[j] == 0u)
+            return fail(ECDNA_E_INVALID, "select.ranks[" + std::to_string(j) + "] must be >= 1");
+        if (s->fractions && !(s->fractions[j] > 0.0 && s->fractions[j] <= 1.0))
+            return fail(ECDNA_E_INVALID, "select.fractions[" + std::to_string(j) + "] must be in (0, 1] and not NaN");
+    }
+    if (s->reserved) return fail(ECDNA_E_INVALID, "select.reserved must be 0");
+    SelectSource src;
+    TRY(select_source(c, s->source, s->timepoint_mask, "select", &src));
+
+    sel::Walk walk;
+    walk.start(K, s->ranks, s->fractions);
+    std::vector<uint64_t> hist((uint64_t)sel::kDistances * K * sel::kDigits);
+    for (uint32_t pass = 0; pass < sel::kPasses; ++pass) {
+        TRY(select_pass(c, s->source, src, pass, K, walk.prefixes(), sel::kMaxRanks, hist.data(), "ecdna_ssa_ctx_select"));
+        walk.feed(hist.data());
+    }
+    if (out_population) *out_population = walk.M;
+    for (uint32_t j = 0; j < K; ++j) {
+        if (out_ranks) out_ranks[j] = walk.rank[j];
+        for (uint32_t x = 0; x < sel::kDistances; ++x) {
+            if (out_values) out_values[(uint64_t)x * K + j] = walk.value(x, j);
+            if (out_counts_le) out_counts_le[(uint64_t)x * K + j] = walk.counts_le(x, j);
+        }
+    }
     return ECDNA_OK;
 }
 

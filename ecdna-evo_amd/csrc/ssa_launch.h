@@ -1,7 +1,7 @@
 // ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by the device
 // code (steppers: ssa_kernels.hip, ssa_refdraws.hip; end-of-run passes: ssa_hist.hip,
-// ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip; the acceptance pass: ssa_accept.hip) and
-// ssa_api.cpp (the C ABI).
+// ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip; the acceptance pass: ssa_accept.hip; the
+// select passes: ssa_select.hip) and ssa_api.cpp (the C ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -219,6 +219,32 @@ struct AcceptArgs {
     double thr[kMaxAcceptRows][4];        // per row: ks, mean_rel, entropy_rel, frequency_diff (+inf: off)
 };
 
+// The select passes over the whole run (ssa_select.hip; ecdna_ssa_ctx_select / _select_digits, select mapping v1): an
+// 8-bit radix select of order statistics of the four distances. ssa_select_keys writes every replicate's key per
+// distance once per (source, timepoint mask), from records and error words that lie as AcceptArgs' do;
+// ssa_select_digits counts, per pass, distance and distinct prefix, the keys with that prefix by their next 8 bits.
+constexpr uint32_t kMaxSelectGroups = 32;  // distinct prefixes per distance and pass (the ranks K of a call at most)
+constexpr int kSelectBlock = 256;
+struct SelectKeyArgs {
+    const ecdna_rep_stats_t* stats;
+    const ecdna_rep_summary_t* summaries;
+    uint64_t rep_stride, tp_stride, err_stride;
+    uint64_t tmask;                       // participating timepoints (bits below T; never 0 for T > 0)
+    uint64_t* keys;                       // [4][n]: per distance the maximum key over the participating timepoints,
+                                          // select::kExcluded for a replicate with an error
+    uint32_t n;                           // replicates of the run
+    uint32_t T;                           // timepoints of the source
+};
+struct SelectArgs {
+    const uint64_t* keys;                 // [4][n]
+    unsigned long long* hist;             // [4][kMaxSelectGroups][256], zeroed before the launch
+    uint32_t n;
+    uint32_t pass;                        // 0 .. 7: the keys' bits 63 - 8 * pass .. 56 - 8 * pass are the digit
+    uint32_t reps_per_block;              // consecutive replicates a workgroup walks (>= 1)
+    uint32_t n_groups[4];                 // per distance, distinct prefixes: 1 .. kMaxSelectGroups (pass 0: 1)
+    uint64_t prefix[4][kMaxSelectGroups]; // their top 8 * pass bits, shifted down (pass 0: 0); wave-uniform reads
+};
+
 constexpr uint32_t kMaxSubsampleCells = 4096;  // LDS: 8 B of table per sampled cell and wave (<= 32 KiB)
 constexpr int kStepperBlock = 256;
 constexpr int kBinWideBlock = 64;  // bin store with 256 bins
@@ -310,6 +336,10 @@ hipError_t launch_passage(const PassageArgs& a, uint32_t blocks, hipStream_t str
 // ever waits for another. a.n > 0.
 hipError_t launch_accept_mask(const AcceptArgs& a, hipStream_t stream);
 hipError_t launch_accept_list(const AcceptArgs& a, hipStream_t stream);
+// The select passes (ssa_select.hip): the keys of every replicate (a.n > 0), and one digit pass over them (a.hist zeroed
+// on the stream before it; the dynamic LDS table is 1 KiB per group of the distance with most, 32 KiB at most).
+hipError_t launch_select_keys(const SelectKeyArgs& a, hipStream_t stream);
+hipError_t launch_select_digits(const SelectArgs& a, hipStream_t stream);
 // The reference-draws stepper (row store; ssa_refdraws.hip)
 const void* refdraws_kernel(int birth_death, int segregation);
 int refdraws_block();

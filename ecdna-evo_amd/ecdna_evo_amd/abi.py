@@ -149,6 +149,25 @@ class Accept(C.Structure):
     ]
 
 
+SELECT_MAX_RANKS = 32
+SELECT_PASSES = 8  # 8 bits of the 64-bit key per pass
+SELECT_FIELDS = ("ks", "mean_rel", "entropy_rel", "frequency_diff")  # the distance order of the select's arrays
+
+
+class Select(C.Structure):
+    """ecdna_ssa_select_t: the argument block of ecdna_ssa_ctx_select (added within ABI v13)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("source", C.c_uint32),
+        ("timepoint_mask", C.c_uint64),
+        ("n_ranks", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("ranks", C.POINTER(C.c_uint64)),
+        ("fractions", C.POINTER(C.c_double)),
+    ]
+
+
 _MASK64 = (1 << 64) - 1
 
 

@@ -42,6 +42,8 @@ EXPORTS = [
     "ecdna_ssa_ctx_download_passages",
     "ecdna_ssa_ctx_accept",
     "ecdna_ssa_ctx_download_accept",
+    "ecdna_ssa_ctx_select",
+    "ecdna_ssa_ctx_select_digits",
     "ecdna_ssa_ctx_download_rng_words",
     "ecdna_ssa_ctx_row_stride",
     "ecdna_ssa_ctx_geometry",
@@ -150,6 +152,13 @@ def lib():
         L.ecdna_ssa_ctx_download_accept.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint64), C.c_void_p,
                                                     C.c_void_p]
         L.ecdna_ssa_ctx_download_accept.restype = C.c_int
+    # (likewise added within v13: ABC thresholds on the GPU; Context.select raises on an earlier library)
+    if hasattr(L, "ecdna_ssa_ctx_select"):
+        L.ecdna_ssa_ctx_select.argtypes = [C.c_void_p, P(abi.Select), P(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ecdna_ssa_ctx_select.restype = C.c_int
+        L.ecdna_ssa_ctx_select_digits.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.c_void_p]
+        L.ecdna_ssa_ctx_select_digits.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -267,6 +276,51 @@ class AcceptResult:
         self.stats = stats
 
 
+class SelectResult:
+    """Order statistics of the four distances among the error-free replicates (select mapping v1, include/ecdna_ssa.h):
+    population, their number M; ranks [K] u64, those asked for or those the fractions map to; values [4][K] f64 and
+    counts_le [4][K] u64 in the distance order abi.SELECT_FIELDS: the number whose key is the ranks[j]-th smallest, and
+    how many of the M are <= it (a rank above M: +inf and M)."""
+
+    def __init__(self, population, ranks, values, counts_le):
+        self.population = population
+        self.ranks = ranks
+        self.values = values
+        self.counts_le = counts_le
+
+
+def timepoint_mask(timepoints) -> int:
+    """The ABI's timepoint_mask of an iterable of participating timepoints (None: 0 = all)."""
+    mask = 0
+    for t in (timepoints if timepoints is not None else ()):
+        if not (0 <= int(t) < 64):
+            raise ValueError(f"timepoint {t} does not fit the ABI's 64-bit timepoint_mask")
+        mask |= 1 << int(t)
+    if timepoints is not None and mask == 0:
+        raise ValueError("timepoints is empty (None = all)")
+    return mask
+
+
+def select_ranks(ranks=None, fractions=None):
+    """The checked arguments of a select, (ranks [K] u64 or None, fractions [K] f64 or None): exactly one of the two,
+    K in 1 .. 32, every rank >= 1 and below 2^64, every fraction in (0, 1]. Raises ValueError otherwise."""
+    if (ranks is None) == (fractions is None):
+        raise ValueError("exactly one of ranks and fractions must be given")
+    given = ranks if ranks is not None else fractions
+    K = len(given)
+    if not (1 <= K <= abi.SELECT_MAX_RANKS):
+        raise ValueError(f"{K} ranks: a select takes 1 .. {abi.SELECT_MAX_RANKS}")
+    if ranks is not None:
+        for k in ranks:
+            if not (1 <= int(k) < (1 << 64)):
+                raise ValueError(f"rank {k} must be >= 1 and fit the ABI's u64")
+        return np.asarray([int(k) for k in ranks], dtype=np.uint64), None
+    fr = np.ascontiguousarray(fractions, dtype=np.float64)
+    if not np.all((fr > 0.0) & (fr <= 1.0)):
+        raise ValueError("every fraction must be in (0, 1]")
+    return None, fr
+
+
 class Context:
     """A device-resident run (ecdna_ssa_ctx): create once, launch many times."""
 
@@ -355,13 +409,7 @@ class Context:
         thr = np.ascontiguousarray(thresholds, dtype=np.float64)
         if thr.ndim != 2 or thr.shape[1] != 4:
             raise ValueError("thresholds must be [Q][4]: ks, mean_rel, entropy_rel, frequency_diff per row")
-        mask = 0
-        for t in (timepoints if timepoints is not None else ()):
-            if not (0 <= int(t) < 64):
-                raise ValueError(f"timepoint {t} does not fit the ABI's 64-bit timepoint_mask")
-            mask |= 1 << int(t)
-        if timepoints is not None and mask == 0:
-            raise ValueError("timepoints is empty (None = all)")
+        mask = timepoint_mask(timepoints)
         for name, v, bits in (("list_threshold", list_threshold, 32), ("list_capacity", list_capacity, 64),
                               ("source", source, 32), ("n_thresholds", thr.shape[0], 32)):
             if not (0 <= int(v) < (1 << bits)):
@@ -401,6 +449,50 @@ class Context:
         any number of times after one launch."""
         self.accept_enqueue(source, thresholds, timepoints, list_threshold, list_capacity)
         return self.download_accept()
+
+    def select(self, source: int, ranks=None, fractions=None, timepoints=None) -> SelectResult:
+        """ABC thresholds on the GPU (ecdna_ssa_ctx_select, select mapping v1): the exact `ranks`-th smallest values
+        (ranks >= 1), or those at `fractions` in (0, 1] of the population, of each of the four distances among the
+        error-free replicates of `source` (an abi.ACCEPT_* constant), the maximum over `timepoints` (None: all) standing
+        for a replicate. accept() with a finite value as the one threshold accepts exactly its counts_le replicates."""
+        if not hasattr(lib(), "ecdna_ssa_ctx_select"):
+            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_select (ABC thresholds on the GPU)")
+        rk, fr = select_ranks(ranks, fractions)
+        if not (0 <= int(source) < (1 << 32)):
+            raise ValueError(f"source = {source} does not fit the ABI's u32 field")
+        K = len(rk) if rk is not None else len(fr)
+        s = abi.Select(struct_size=C.sizeof(abi.Select), source=int(source), timepoint_mask=timepoint_mask(timepoints),
+                       n_ranks=K)
+        if rk is not None:
+            s.ranks = rk.ctypes.data_as(C.POINTER(C.c_uint64))
+        else:
+            s.fractions = fr.ctypes.data_as(C.POINTER(C.c_double))
+        population = C.c_uint64()
+        out_ranks = np.zeros(K, dtype=np.uint64)
+        values = np.zeros((4, K), dtype=np.float64)
+        counts_le = np.zeros((4, K), dtype=np.uint64)
+        _check(lib().ecdna_ssa_ctx_select(self.h, C.byref(s), C.byref(population), out_ranks.ctypes.data,
+                                          values.ctypes.data, counts_le.ctypes.data), "ecdna_ssa_ctx_select")
+        return SelectResult(int(population.value), out_ranks, values, counts_le)
+
+    def select_digits(self, source: int, pass_: int, prefixes, timepoints=None) -> np.ndarray:
+        """One pass of the select on this context's replicates (ecdna_ssa_ctx_select_digits), the shard primitive:
+        `prefixes` [4][K] u64 keys (shard.SelectWalk.prefixes), the result [4][K][256] u64: per distance and prefix, the
+        population's keys that share the prefix's top 8 * pass_ bits, counted by their next 8 bits. Shards' arrays sum."""
+        if not hasattr(lib(), "ecdna_ssa_ctx_select_digits"):
+            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_select_digits (ABC thresholds on the GPU)")
+        pre = np.ascontiguousarray(prefixes, dtype=np.uint64)
+        if pre.ndim != 2 or pre.shape[0] != 4 or not (1 <= pre.shape[1] <= abi.SELECT_MAX_RANKS):
+            raise ValueError(f"prefixes must be [4][K], K in 1 .. {abi.SELECT_MAX_RANKS}")
+        if not (0 <= int(pass_) < abi.SELECT_PASSES):
+            raise ValueError(f"pass_ = {pass_} must be in 0 .. {abi.SELECT_PASSES - 1}")
+        if not (0 <= int(source) < (1 << 32)):
+            raise ValueError(f"source = {source} does not fit the ABI's u32 field")
+        hist = np.zeros((4, pre.shape[1], 256), dtype=np.uint64)
+        _check(lib().ecdna_ssa_ctx_select_digits(self.h, int(source), timepoint_mask(timepoints), int(pass_),
+                                                 pre.shape[1], pre.ctypes.data, hist.ctypes.data),
+               "ecdna_ssa_ctx_select_digits")
+        return hist
 
     def download(self, want_rows: bool = False) -> Result:
         p = self.params

@@ -138,3 +138,104 @@ def gather_structured(arr, total: int, layout: str = "contiguous", device=None, 
         t = t.to(device)
     g = gather_records(t, total, layout, group).cpu().numpy()
     return np.ascontiguousarray(g).view(arr.dtype).reshape((-1,) + tuple(arr.shape[1:]))
+
+
+class SelectWalk:
+    """The rank walk of the 8-bit radix select (select mapping v1, include/ecdna_ssa.h) over digit histograms summed
+    over the shards: the walk ecdna_ssa_ctx_select makes on one context (csrc/ssa_select.hpp), in Python, so that a
+    sharded sweep finds the global order statistics of its distances from eight small sums instead of a gather of every
+    record. Per pass: `prefixes` ([4][K] u64 keys) is the input of every shard's Context.select_digits, and feed() takes
+    the sum of their [4][K][256] results. Pass 0's row sum is the population M, which turns fractions into ranks. After
+    the eighth feed result() returns the engine.SelectResult."""
+
+    PASSES = 8
+
+    def __init__(self, K: int, ranks=None, fractions=None):
+        from .engine import select_ranks
+
+        rk, fr = select_ranks(ranks, fractions)
+        if K != (len(rk) if rk is not None else len(fr)):
+            raise ValueError(f"K = {K}, but {len(rk) if rk is not None else len(fr)} ranks are given")
+        self.K = K
+        self.pass_ = 0
+        self.population = None
+        self._fractions = None if fr is None else [float(f) for f in fr]
+        self.ranks = None if rk is None else [int(k) for k in rk]
+        self._prefix = [[0] * K for _ in range(4)]
+        self._remaining = [[0] * K for _ in range(4)]
+        self._less = [[0] * K for _ in range(4)]
+        self._count = [[0] * K for _ in range(4)]
+
+    @property
+    def prefixes(self):
+        import numpy as np
+
+        return np.array(self._prefix, dtype=np.uint64)
+
+    def feed(self, hist) -> None:
+        import math
+
+        import numpy as np
+
+        if self.pass_ >= self.PASSES:
+            raise ValueError("the walk has had its eight passes")
+        hist = np.asarray(hist).astype(np.uint64).reshape(4, self.K, 256)
+        if self.pass_ == 0:
+            M = self.population = int(hist[0, 0].sum(dtype=np.uint64))
+            if self._fractions is not None:  # k = max(1, ceil(f * M)) in f64
+                self.ranks = [max(1, int(math.ceil(f * float(M)))) for f in self._fractions]
+            self._remaining = [list(self.ranks) for _ in range(4)]
+        shift = 56 - 8 * self.pass_
+        keep = ((1 << 64) - 1) ^ ((1 << (shift + 8)) - 1)  # the bits above this pass's digit
+        for x in range(4):
+            for j in range(self.K):
+                if self.ranks[j] > self.population:
+                    continue
+                cum = np.cumsum(hist[x, j], dtype=np.uint64)
+                # the smallest digit whose cumulative count reaches the remaining rank
+                d = min(int(np.searchsorted(cum, np.uint64(self._remaining[x][j]), side="left")), 255)
+                below = int(cum[d - 1]) if d else 0
+                self._prefix[x][j] = (self._prefix[x][j] & keep) | (d << shift)
+                self._remaining[x][j] -= below
+                self._less[x][j] += below
+                self._count[x][j] = int(hist[x, j, d])
+        self.pass_ += 1
+
+    def result(self):
+        import numpy as np
+
+        from .engine import SelectResult
+
+        if self.pass_ != self.PASSES:
+            raise ValueError(f"the walk has had {self.pass_} of its {self.PASSES} passes")
+        M = self.population
+        keys = np.array(self._prefix, dtype=np.uint64)
+        sign = np.uint64(1 << 63)
+        bits = np.where(keys & sign != 0, keys ^ sign, ~keys)  # the key map's inverse
+        values = bits.view(np.float64).copy()
+        counts_le = np.array(self._less, dtype=np.uint64) + np.array(self._count, dtype=np.uint64)
+        over = np.array(self.ranks, dtype=object) > M
+        values[:, over] = np.inf
+        counts_le[:, over] = M
+        return SelectResult(M, np.array(self.ranks, dtype=np.uint64), values, counts_le)
+
+
+def select(ctx, source: int, ranks=None, fractions=None, timepoints=None, group=None, device=None):
+    """Context.select over every rank's shard: the exact order statistics of the whole run's distances, the same
+    engine.SelectResult on every rank. Per pass each rank counts its own replicates (Context.select_digits) and one
+    all-reduce (int64, sum) of the [4][K][256] array joins them: integer sums, exact in any order. Nothing else is
+    exchanged. `device`: where the exchange buffer lives ("cuda" under RCCL, None = CPU for gloo)."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    K = len(ranks) if ranks is not None else len(fractions if fractions is not None else ())
+    walk = SelectWalk(K, ranks=ranks, fractions=fractions)
+    for p in range(SelectWalk.PASSES):
+        hist = ctx.select_digits(source, p, walk.prefixes, timepoints)
+        t = torch.from_numpy(hist.view(np.int64))  # (counts stay far below 2^63)
+        if device is not None:
+            t = t.to(device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        walk.feed(t.cpu().numpy().view(np.uint64))
+    return walk.result()

@@ -43,7 +43,11 @@
 extern "C" {
 #endif
 
-/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): ABC rejection on the
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): ABC thresholds on the
+ * GPU — exact order statistics of the distances among the error-free replicates by an 8-bit radix select over the
+ * statistics a context already holds, ecdna_ssa_ctx_select and its shard primitive ecdna_ssa_ctx_select_digits (below;
+ * select mapping v1). A context that never calls them allocates and launches nothing new.
+ * Added within v13 (additive: no layout and no existing function changes, the version stays 13): ABC rejection on the
  * GPU — the acceptance pass ecdna_ssa_ctx_accept / ecdna_ssa_ctx_download_accept over the statistics a context already
  * holds (below; acceptance mapping v1). A context that never calls it allocates and launches nothing new.
  * Added within v13 (additive: no layout and no existing function changes, the version stays 13): serial passaging —
@@ -529,6 +533,64 @@ int ecdna_ssa_ctx_accept(ecdna_ssa_ctx* c, const ecdna_ssa_accept_t* a);
 int ecdna_ssa_ctx_download_accept(ecdna_ssa_ctx* c, uint64_t* out_counts, uint32_t* out_mask,
                                   uint64_t* out_n_accepted, uint64_t* out_ids,
                                   ecdna_rep_stats_t* out_list_stats);
+/* ABC thresholds on the GPU (added within ABI v13): exact order statistics of the four distances over the statistics a
+ * context already holds, so that "keep the closest 1 % of the runs" needs neither a download of every record nor, on
+ * several GPUs, a gather of them. An 8-bit radix select: each of eight passes leaves a small integer histogram, and
+ * shards' histograms sum exactly, as the counts of ecdna_ssa_ctx_accept do.
+ *
+ * Select mapping v1.
+ *  - Source, timepoints, population. The source is an ecdna_accept_source_t; its T timepoints, timepoint_mask (0 = all)
+ *    and strides mean what they mean for ecdna_ssa_ctx_accept. The population is the replicates that rule 1 of
+ *    acceptance mapping v1 calls error-free (error == 0 in the one summary, or, for the passage sources, in the summary
+ *    of every participating phase), pooled over all parameter sets of the call. Its size is M.
+ *  - Key. Of a distance value d: -0.0 becomes +0.0 and any NaN the canonical quiet NaN, bits 0x7FF8000000000000; then
+ *    key(d) = bits(d) ^ 0x8000000000000000 when the sign bit is clear and ~bits(d) when it is set: the usual
+ *    order-preserving map, and NaN sorts above +inf. Replicate i's key for distance x is the maximum, over the
+ *    participating timepoints t, of key(d[i][t].x): a replicate passes threshold v on x at every participating
+ *    timepoint iff key_x[i] <= key(v).
+ *  - Order statistic. For rank k >= 1 and distance x, value_x(k) is the number whose key is the k-th smallest of the M
+ *    keys, and counts_le_x(k) the number of the M keys <= that key: >= k, and > k on a tie. For k > M, and for every k
+ *    when M = 0, value = +inf and counts_le = M (+inf switches a statistic off in accept, which then accepts all M). A
+ *    NaN value means that fewer than k replicates have a number for that distance; it is reported as NaN and must not
+ *    be fed to accept.
+ *  - Consequence, part of the contract. For a finite value_x(k), ecdna_ssa_ctx_accept with that threshold on x and +inf
+ *    on the other three, on the same source and timepoint_mask, accepts exactly counts_le_x(k) replicates, and no
+ *    smaller threshold accepts k or more.
+ *  - Ranks from fractions. f in (0, 1] maps to k = max(1, (uint64)ceil(f * (double)M)), evaluated in f64.
+ * The distance order is that of ecdna_accept_threshold_t: ks, mean_rel, entropy_rel, frequency_diff. */
+typedef struct {
+    uint32_t struct_size;        /* sizeof(ecdna_ssa_select_t), else ECDNA_E_INVALID */
+    uint32_t source;             /* ecdna_accept_source_t */
+    uint64_t timepoint_mask;     /* bit t = timepoint t takes part; 0 = all T */
+    uint32_t n_ranks;            /* K, 1 .. 32 */
+    uint32_t reserved;           /* must be 0 */
+    const uint64_t* ranks;       /* host, [K], each >= 1; or NULL */
+    const double* fractions;     /* host, [K], each in (0, 1]; or NULL: exactly one of the two is given */
+} ecdna_ssa_select_t;
+
+/* The order statistics of one context's replicates: eight digit passes and the walk over their histograms. Synchronous,
+ * as the downloads are; any output may be NULL. out_population: M. out_ranks[K]: the ranks (those given, or those the
+ * fractions map to). out_values[4][K] and out_counts_le[4][K]: value_x(k_j) and counts_le_x(k_j).
+ * Both calls keep scratch that belongs to the context (the keys, 32 bytes per replicate, and one pass's histogram):
+ * allocated at the first call, freed at destroy. The keys are kept between passes and calls for one (source,
+ * timepoint_mask) and dropped by a relaunch. The results of ecdna_ssa_ctx_accept are not touched.
+ * ECDNA_E_INVALID (the message names the field): NULL c or s, wrong struct_size, unknown source, n_ranks outside 1 .. 32,
+ * both or neither of ranks and fractions, a rank of 0, a fraction outside (0, 1] or NaN, timepoint_mask bits at or above
+ * T, reserved != 0, n_replicates >= 2^32; for select_digits also pass > 7, n_prefixes outside 1 .. 32, NULL prefixes or
+ * out_hist.
+ * ECDNA_E_STATE: exactly where ecdna_ssa_ctx_accept returns it (before a launch; a source the context does not hold;
+ * statistics computed without a target).
+ * ECDNA_E_NOMEM: the scratch does not fit; the context stays usable and its other outputs intact. */
+int ecdna_ssa_ctx_select(ecdna_ssa_ctx* c, const ecdna_ssa_select_t* s, uint64_t* out_population,
+                         uint64_t* out_ranks, double* out_values, uint64_t* out_counts_le);
+/* One pass of the select, the shard primitive: out_hist[4][K][256], where out_hist[x][j][d] counts the population's
+ * keys of distance x whose top 8 * pass bits equal those of prefixes[x][j] (host, [4][K]; lower bits are ignored) and
+ * whose next 8 bits are d. Pass 0 counts everything, so the sum of any row is M. Shards' arrays sum to the whole
+ * run's: a sharded sweep sums each pass's array over its GPUs, walks it to the next pass's prefixes (per row: the
+ * smallest digit whose cumulative count reaches the remaining rank) and finds the global order statistics with eight
+ * small all-reduces instead of a gather of every record. Synchronous. */
+int ecdna_ssa_ctx_select_digits(ecdna_ssa_ctx* c, uint32_t source, uint64_t timepoint_mask, uint32_t pass,
+                                uint32_t n_prefixes, const uint64_t* prefixes, uint64_t* out_hist);
 /* Reference draws (ECDNA_FLAG_REFERENCE_DRAWS, ABI v7): per replicate, the number of 32-bit words its ChaCha8
  * stream (seed_from_u64(seed), stream seed*10 + r) had handed out when it stopped — where the reference's
  * end-of-run subsampling continues the same rng (into_subsampled(nb, &mut rng), src/main.rs:110-123, 184-197;
