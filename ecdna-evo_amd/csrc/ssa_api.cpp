@@ -1,7 +1,7 @@
 // ssa_api.cpp — the C ABI of include/ecdna_ssa.h: parameter validation,
 // device-resident run contexts, chunking by HBM capacity, and launches of the
 // stepper and end-of-run kernels (ssa_kernels.hip, ssa_hist.hip, ssa_subsample.hip, ssa_snapstats.hip,
-// ssa_passage.hip) and of the post-launch acceptance pass (ssa_accept.hip).
+// ssa_passage.hip, ssa_cohort.hip) and of the post-launch acceptance pass (ssa_accept.hip).
 //
 // This file replaces, for one GPU, the per-replicate driver loop of the
 // reference: run_simulations(idx) mapped by rayon over seed*10 .. seed*10+runs
@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/ecdna_ssa.h"
+#include "ssa_cohort.hpp"
 #include "ssa_launch.h"
 #include "ssa_plan.hpp"
 #include "ssa_select.hpp"
@@ -304,6 +305,15 @@ struct ecdna_ssa_ctx {
     uint64_t* d_pas_sample_hist = nullptr;          // [G][n_sets][bins]
     double* d_pas_target_cdf = nullptr;             // [G][bins], or nullptr: no target
     std::vector<double> pas_target_scalars;         // [G][3]: the targets' mean, entropy, N+ frequency
+    // a cohort of targets (ecdna_ssa_cohort_t; 0 = none): every replicate's final state scored against each of P targets
+    // (ssa_cohort.hip). Records [P][n], the samples' only with sample sizes (cohort_groups.n_groups > 0); each target's
+    // CDF [P][bins] and scalars [P][3]
+    uint32_t n_cohort = 0;
+    ecdna::cohort::Groups cohort_groups;
+    ecdna_rep_stats_t* d_coh_stats = nullptr;
+    ecdna_rep_stats_t* d_coh_sample_stats = nullptr;
+    double* d_coh_target_cdf = nullptr;
+    double* d_coh_target_scalars = nullptr;
     // device buffers: every one is allocated by ctx_alloc / ctx_upload, which list it in `owned` for free_ctx
     // (d_hist / d_tot: the caller's output buffers or d_hist_own / d_tot_own, never owned themselves)
     std::vector<void*> owned;
@@ -416,7 +426,7 @@ int ctx_drain(ecdna_ssa_ctx* c) {
     return ECDNA_OK;
 }
 
-// ---- ecdna_ssa_ctx_create_passages, step by step (build_ctx has the order: the chunk size depends on what is allocated
+// ---- ecdna_ssa_ctx_create_cohort, step by step (build_ctx has the order: the chunk size depends on what is allocated
 // before gather_facts asks for the free memory) ----
 
 // Sum of a target histogram (> 0 for a usable target), and for `count` of them ([count][bins]) what the kernels
@@ -531,6 +541,31 @@ int upload_targets(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ss
         summarize_targets(ext->snapshot_target_hists, p->n_snapshots, bins, cdf.data(), scal.data());
         TRY(ctx_upload(c, &c->d_snap_target_cdf, cdf));
         TRY(ctx_upload(c, &c->d_snap_target_scalars, scal));
+    }
+    return ECDNA_OK;
+}
+
+// The cohort block: the targets' CDFs and scalars, the grouping by sample size, and the records, sized by the run.
+int adopt_cohort(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_cohort_t* co) {
+    const uint32_t bins = p->hist_bins, P = co->n_targets;
+    c->n_cohort = P;
+    c->cohort_groups = ecdna::cohort::group_by_sample_size(co->sample_cells, P);
+    std::vector<double> cdf((uint64_t)P * bins), scal(P * 3);
+    summarize_targets(co->target_hists, P, bins, cdf.data(), scal.data());
+    TRY(ctx_upload(c, &c->d_coh_target_cdf, cdf));
+    TRY(ctx_upload(c, &c->d_coh_target_scalars, scal));
+    const uint64_t records = (uint64_t)P * std::max<uint64_t>(p->n_replicates, 1);
+    // (the samples' records only with sample sizes)
+    for (ecdna_rep_stats_t** buf : {&c->d_coh_stats, c->cohort_groups.n_groups ? &c->d_coh_sample_stats : nullptr}) {
+        if (!buf) continue;
+        const hipError_t e = ctx_alloc(c, buf, records);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(e == hipErrorOutOfMemory ? ECDNA_E_NOMEM : ECDNA_E_HIP,
+                        "ecdna_ssa_ctx_create_cohort: the cohort records (" +
+                            std::to_string(records * sizeof(ecdna_rep_stats_t)) + " bytes) do not fit: " +
+                            hipGetErrorString(e));
+        }
     }
     return ECDNA_OK;
 }
@@ -679,11 +714,12 @@ int alloc_plan(ecdna_ssa_ctx* c, const ecdna::plan::LaunchPlan& pl, const float*
 // Gather, plan, allocate: what the run's shape and the device say, the plan they give (ssa_plan.hpp: every launch
 // decision of create), and the buffers the plan asks for.
 int build_ctx(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
-              const ecdna_ssa_passages_t* pas) {
+              const ecdna_ssa_passages_t* pas, const ecdna_ssa_cohort_t* co) {
     const ecdna::plan::Knobs knobs = ecdna::plan::knobs_from_env();
     const ecdna::plan::RunShape shape = adopt_params(c, p, ext, pas, knobs);
     TRY(upload_inputs(c));
     TRY(upload_targets(c, p, ext, pas));
+    if (co) TRY(adopt_cohort(c, p, co));
     TRY(alloc_outputs(c));
     ecdna::plan::DeviceFacts facts;
     TRY(gather_facts(c, knobs, &facts));
@@ -828,6 +864,32 @@ int launch_subsample_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::
     return ECDNA_OK;
 }
 
+// the final state against every target of the cohort, and its samples against theirs
+int launch_cohort_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::FinalState& fs, ecdna::ChunkIds ids,
+                       hipStream_t st) {
+    const ecdna::cohort::Groups& g = c->cohort_groups;
+    const ecdna::cohort::LdsPlan lp = ecdna::cohort::lds_plan(ids.bins, fs.bag_k, g.max_m);
+    ecdna::CohortArgs ca{};
+    ca.state = fs;
+    ca.stats = c->d_coh_stats + ch.first;
+    ca.sample_stats = c->d_coh_sample_stats ? c->d_coh_sample_stats + ch.first : nullptr;
+    ca.out_stride = std::max<uint64_t>(c->p.n_replicates, 1);
+    ca.target_cdf = c->d_coh_target_cdf;
+    ca.target_scalars = c->d_coh_target_scalars;
+    ca.seed = c->p.seed;
+    ca.n_targets = c->n_cohort;
+    ca.n_groups = g.n_groups;
+    ca.table_slots = lp.table_slots;
+    ca.scratch_words = lp.scratch_words;
+    std::copy(std::begin(g.m), std::end(g.m), ca.group_m);
+    std::copy(std::begin(g.offset), std::end(g.offset), ca.group_offset);
+    std::copy(std::begin(g.targets), std::end(g.targets), ca.group_targets);
+    ids.reps_per_block = pass_reps_per_block(c, ch.n, lp.waves);
+    ca.ids = ids;
+    TRY(ecdna::launch_cohort(ca, pass_blocks(ids), st));
+    return ECDNA_OK;
+}
+
 // phase g's measurement, and (but for the last phase) the founders of the next
 int launch_passage_pass(const ecdna_ssa_ctx* c, const Chunk& ch, uint32_t g, const ecdna::FinalState& fs,
                         ecdna::ChunkIds ids, const ecdna::StatsTarget& target, uint64_t seed_g, hipStream_t st) {
@@ -903,6 +965,7 @@ int launch_chunk_phase(ecdna_ssa_ctx* c, size_t k, uint32_t g, hipStream_t st) {
     const ecdna::HistArgs h = hist_args(c, ch, g, fs, ids, target);
     TRY(ecdna::launch_hist(h, pass_blocks(h.ids), st));
     if (p.subsample_cells) TRY(launch_subsample_pass(c, ch, fs, ids, target, st));
+    if (c->n_cohort) TRY(launch_cohort_pass(c, ch, fs, ids, st));
     if (c->n_passages) TRY(launch_passage_pass(c, ch, g, fs, ids, target, a.seed, st));
     if (c->snap_stats) TRY(launch_snapstats_pass(c, ch, a, ids, st));
     TRY(hipEventRecord(ev[2], st));
@@ -913,6 +976,12 @@ int launch_chunk_phase(ecdna_ssa_ctx* c, size_t k, uint32_t g, hipStream_t st) {
 
 // What an ecdna_accept_source_t names in this context (ssa_launch.h AcceptArgs has the strides' meaning); ECDNA_E_STATE
 // under the conditions of the matching download.
+// Whether a number names a source: the one predicate of ecdna_ssa_ctx_accept, select_source and ecdna_ssa_ctx_select (6
+// and 7 are not sources).
+bool is_accept_source(uint32_t source) {
+    return source <= (uint32_t)ECDNA_ACCEPT_PASSAGE_SAMPLES || source == (uint32_t)ECDNA_ACCEPT_COHORT ||
+           source == (uint32_t)ECDNA_ACCEPT_COHORT_SAMPLES;
+}
 struct AcceptSource {
     const ecdna_rep_stats_t* stats = nullptr;
     const ecdna_rep_summary_t* summaries = nullptr;
@@ -963,6 +1032,20 @@ int accept_source(const ecdna_ssa_ctx* c, uint32_t source, AcceptSource* out) {
             s.err_stride = n_run;
             s.has_target = run_target;
             break;
+        case ECDNA_ACCEPT_COHORT:
+        case ECDNA_ACCEPT_COHORT_SAMPLES: {
+            const bool samples = source == ECDNA_ACCEPT_COHORT_SAMPLES;
+            if (!c->n_cohort)
+                return fail(ECDNA_E_STATE, "accept.source COHORT: the cohort records need ecdna_ssa_ctx_create_cohort");
+            if (samples && !c->d_coh_sample_stats)
+                return fail(ECDNA_E_STATE, "accept.source COHORT_SAMPLES: the cohort samples need "
+                                           "ecdna_ssa_cohort_t.sample_cells");
+            s.stats = samples ? c->d_coh_sample_stats : c->d_coh_stats;
+            s.T = c->n_cohort;
+            s.tp_stride = n_run;  // [P][n]; one summary per replicate, whatever the target
+            s.has_target = true;
+            break;
+        }
         default:
             return fail(ECDNA_E_INVALID, "accept.source is not an ecdna_accept_source_t");
     }
@@ -998,7 +1081,7 @@ struct SelectSource {
 };
 int select_source(const ecdna_ssa_ctx* c, uint32_t source, uint64_t timepoint_mask, const std::string& who,
                   SelectSource* out) {
-    if (source > (uint32_t)ECDNA_ACCEPT_PASSAGE_SAMPLES)
+    if (!is_accept_source(source))
         return fail(ECDNA_E_INVALID, who + ".source is not an ecdna_accept_source_t");
     if (c->p.n_replicates >= (1ull << 32)) return fail(ECDNA_E_INVALID, who + ": n_replicates must be < 2^32");
     TRY(accept_source(c, source, &out->src));
@@ -1159,12 +1242,21 @@ int ecdna_ssa_ctx_create_ext(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t*
 
 int ecdna_ssa_ctx_create_passages(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
                                   const ecdna_ssa_passages_t* pas, ecdna_ssa_ctx** out) {
+    return ecdna_ssa_ctx_create_cohort(p, ext, pas, nullptr, out);
+}
+
+int ecdna_ssa_ctx_create_cohort(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                                const ecdna_ssa_passages_t* pas, const ecdna_ssa_cohort_t* co, ecdna_ssa_ctx** out) {
     if (!out) return fail(ECDNA_E_INVALID, "out is NULL");
     *out = nullptr;
     TRY(validate(p, ext, pas));
+    if (co) {  // the cohort block
+        const std::string why = ecdna::cohort::invalid(*p, ext, pas, *co);
+        if (!why.empty()) return fail(ECDNA_E_INVALID, why);
+    }
     TRY(pick_device(p->device));
     ecdna_ssa_ctx* c = new ecdna_ssa_ctx();
-    if (int rc = build_ctx(c, p, ext, pas)) {
+    if (int rc = build_ctx(c, p, ext, pas, co)) {
         free_ctx(c);
         return rc;
     }
@@ -1428,12 +1520,25 @@ int ecdna_ssa_ctx_download_passages(ecdna_ssa_ctx* c, ecdna_rep_summary_t* out_s
     return ECDNA_OK;
 }
 
+int ecdna_ssa_ctx_download_cohort(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats, ecdna_rep_stats_t* out_sample_stats) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!c->n_cohort) return fail(ECDNA_E_STATE, "the cohort records need ecdna_ssa_ctx_create_cohort");
+    TRY(ctx_launched(c));
+    if (out_sample_stats && !c->d_coh_sample_stats)
+        return fail(ECDNA_E_STATE, "the cohort samples need ecdna_ssa_cohort_t.sample_cells");
+    TRY(ctx_drain(c));
+    const uint64_t records = (uint64_t)c->n_cohort * c->p.n_replicates;
+    if (out_stats && records) TRY(to_host(out_stats, c->d_coh_stats, records));
+    if (out_sample_stats && records) TRY(to_host(out_sample_stats, c->d_coh_sample_stats, records));
+    return ECDNA_OK;
+}
+
 int ecdna_ssa_ctx_accept(ecdna_ssa_ctx* c, const ecdna_ssa_accept_t* a) {
     if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
     if (!a) return fail(ECDNA_E_INVALID, "accept is NULL");
     if (a->struct_size != sizeof(ecdna_ssa_accept_t))
         return fail(ECDNA_E_INVALID, "accept.struct_size must be sizeof(ecdna_ssa_accept_t)");
-    if (a->source > (uint32_t)ECDNA_ACCEPT_PASSAGE_SAMPLES)
+    if (!is_accept_source(a->source))
         return fail(ECDNA_E_INVALID, "accept.source is not an ecdna_accept_source_t");
     if (a->n_thresholds < 1u || a->n_thresholds > ecdna::kMaxAcceptRows)
         return fail(ECDNA_E_INVALID, "accept.n_thresholds must be in [1, 32]");
@@ -1565,7 +1670,7 @@ int ecdna_ssa_ctx_select(ecdna_ssa_ctx* c, const ecdna_ssa_select_t* s, uint64_t
     if (!s) return fail(ECDNA_E_INVALID, "select is NULL");
     if (s->struct_size != sizeof(ecdna_ssa_select_t))
         return fail(ECDNA_E_INVALID, "select.struct_size must be sizeof(ecdna_ssa_select_t)");
-    if (s->source > (uint32_t)ECDNA_ACCEPT_PASSAGE_SAMPLES)
+    if (!is_accept_source(s->source))
         return fail(ECDNA_E_INVALID, "select.source is not an ecdna_accept_source_t");
     const uint32_t K = s->n_ranks;
     if (K < 1u || K > sel::kMaxRanks) return fail(ECDNA_E_INVALID, "select.n_ranks must be in [1, 32]");

@@ -1,6 +1,6 @@
 // ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by the device
 // code (steppers: ssa_kernels.hip, ssa_refdraws.hip; end-of-run passes: ssa_hist.hip,
-// ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip; the acceptance pass: ssa_accept.hip; the
+// ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip, ssa_cohort.hip; the acceptance pass: ssa_accept.hip; the
 // select passes: ssa_select.hip) and ssa_api.cpp (the C ABI).
 #pragma once
 
@@ -190,6 +190,31 @@ struct PassageArgs {
     uint32_t sort_slots;                  // per-wave founder array (u16): passage_sort_slots(m)
 };
 
+// The cohort pass over one chunk (ssa_cohort.hip; ecdna_ssa_cohort_t, cohort mapping v1): per replicate, the statistics
+// of its final state against each of P targets, and of its sample of m_p cells against target p. The targets are grouped
+// by distinct sample size in order of first appearance (ssa_cohort.hpp): group g draws one sample of group_m[g] cells and
+// scores it against the targets group_targets[group_offset[g] .. group_offset[g + 1]). The groups travel in the argument
+// block itself: wave-uniform, read with scalar loads. Records lie [P][out_stride].
+constexpr uint32_t kMaxCohortTargets = 64;  // P: one bit each of a 64-bit timepoint mask, one lane each of a wave
+struct CohortArgs {
+    FinalState state;
+    ChunkIds ids;
+    ecdna_rep_stats_t* stats;             // [P][out_stride], offset to the chunk: the full populations' statistics
+    ecdna_rep_stats_t* sample_stats;      // likewise the samples'; nullptr when n_groups == 0
+    uint64_t out_stride;                  // records per target: the run's replicates
+    const double* target_cdf;             // [P][bins]
+    const double* target_scalars;         // [P][3]: the targets' mean, entropy, N+ frequency
+    uint64_t seed;
+    uint32_t n_targets;                   // P, 1 .. kMaxCohortTargets
+    uint32_t n_groups;                    // distinct sample sizes, 0 (no samples) .. P
+    uint32_t table_slots;                 // per-wave table of drawn positions: subsample_table_slots(largest m), or 0
+    uint32_t scratch_words;               // per-wave u32 words shared by that table and the population's CDF (f64 per
+                                          // bin): cohort_scratch_words(bins, table_slots)
+    uint32_t group_m[kMaxCohortTargets];
+    uint32_t group_offset[kMaxCohortTargets + 1];
+    uint32_t group_targets[kMaxCohortTargets];
+};
+
 // The acceptance pass over the whole run (ssa_accept.hip; ecdna_ssa_ctx_accept, acceptance mapping v1): ABC rejection
 // over statistics the context already holds. Replicate i's record of timepoint t is stats[i * rep_stride + t * tp_stride]
 // (one record: strides 1, 0; snapshots [n][S]: S, 1; passages [G][n]: 1, n) and the error word of its phase t is
@@ -327,7 +352,17 @@ inline uint32_t snapstats_waves(uint32_t bins, uint32_t table_slots, size_t* lds
         }
     }
 }
+// ssa_cohort: no workgroup histogram (the cohort keeps none); per wave the full histogram, the sample's histogram,
+// prefix sums, and one scratch area that holds the table (u32) while a sample is drawn and the population's CDF (f64
+// per bin) while it is scored (at the limits, 2,048 bins beside m = 4096 and K = 256, one wave takes 49 KiB)
+inline uint32_t cohort_scratch_words(uint32_t bins, uint32_t table_slots) {
+    return table_slots > 2u * bins ? table_slots : 2u * bins;
+}
+inline uint32_t cohort_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, size_t* lds_bytes) {
+    return pass_waves(0, (2u * (size_t)bins + bag_k + cohort_scratch_words(bins, table_slots)) * 4u, lds_bytes);
+}
 hipError_t launch_subsample(const SubsampleArgs& a, uint32_t blocks, hipStream_t stream);
+hipError_t launch_cohort(const CohortArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_snapstats(const SnapStatsArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_passage(const PassageArgs& a, uint32_t blocks, hipStream_t stream);
 // The acceptance pass (ssa_accept.hip): every replicate's mask and the per-set counts (a.counts zeroed on the stream

@@ -124,7 +124,22 @@ class Passages(C.Structure):
 
 # ecdna_accept_source_t: the statistics ecdna_ssa_ctx_accept tests (added within ABI v13)
 ACCEPT_FINAL, ACCEPT_SAMPLE, ACCEPT_SNAPSHOTS, ACCEPT_SNAPSHOT_SAMPLES, ACCEPT_PASSAGES, ACCEPT_PASSAGE_SAMPLES = range(6)
+# (6 and 7 are not sources.) The cohort's records, T = n_targets: timepoint p is target p (ecdna_ssa_cohort_t)
+ACCEPT_COHORT, ACCEPT_COHORT_SAMPLES = 8, 9
 ACCEPT_MAX_THRESHOLDS = 32
+COHORT_MAX_TARGETS = 64
+
+
+class Cohort(C.Structure):
+    """ecdna_ssa_cohort_t: the cohort block of ecdna_ssa_ctx_create_cohort (added within ABI v13)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_targets", C.c_uint32),
+        ("target_hists", C.POINTER(C.c_uint64)),
+        ("sample_cells", C.POINTER(C.c_uint32)),
+        ("reserved", C.c_uint64),
+    ]
 
 
 class AcceptThreshold(C.Structure):
@@ -325,7 +340,14 @@ class RunSpec:
     n_passages: int = 0
     passage_cells: int = 0
     passage_targets: Optional[Sequence[Sequence[int]]] = None
+    # a cohort of targets scored against this one run on the GPU (ecdna_ssa_cohort_t, within ABI v13; cohort mapping
+    # v1): cohort_targets [P][hist_bins], P <= 64 — several patients, or biopsies, each with its own histogram — and
+    # cohort_sample_cells [P], target p's number of measured cells (None: no samples). Result.cohort holds every
+    # replicate's records against every target. Needs FLAG_REP_STATS; no passages, no snapshot_stats
+    cohort_targets: Optional[Sequence[Sequence[int]]] = None
+    cohort_sample_cells: Optional[Sequence[int]] = None
     _keep: list = field(default_factory=list, repr=False)
+    _keep_cohort: list = field(default_factory=list, repr=False)
     _keep_ext: list = field(default_factory=list, repr=False)
     _keep_pas: list = field(default_factory=list, repr=False)
 
@@ -483,6 +505,33 @@ class RunSpec:
                 raise ValueError("passage_targets must have one histogram of hist_bins entries per passage")
             self._keep_pas.append(tgt)
             b.passage_target_hists = _ptr(tgt, C.c_uint64)
+        return b
+
+    def cohort(self) -> Optional[Cohort]:
+        """The cohort block this spec asks for, or None (no cohort_targets): the context is then made without
+        ecdna_ssa_ctx_create_cohort."""
+        if self.cohort_targets is None:
+            if self.cohort_sample_cells is not None:
+                raise ValueError("cohort_sample_cells needs cohort_targets")
+            return None
+        self._keep_cohort = []
+        tgt = np.ascontiguousarray(self.cohort_targets, dtype=np.uint64)
+        if tgt.ndim != 2 or tgt.shape[1] != self.hist_bins:
+            raise ValueError("cohort_targets must be [P][hist_bins]: one histogram of hist_bins entries per target")
+        b = Cohort()
+        b.struct_size = C.sizeof(Cohort)
+        b.n_targets = tgt.shape[0]
+        self._keep_cohort.append(tgt)
+        b.target_hists = _ptr(tgt, C.c_uint64)
+        if self.cohort_sample_cells is not None:
+            for m in self.cohort_sample_cells:
+                if not (0 <= int(m) < (1 << 32)):
+                    raise ValueError(f"cohort_sample_cells entry {m} does not fit the ABI's u32 field")
+            cells = np.asarray([int(m) for m in self.cohort_sample_cells], dtype=np.uint32)
+            if cells.shape != (tgt.shape[0],):
+                raise ValueError("cohort_sample_cells needs one sample size per target")
+            self._keep_cohort.append(cells)
+            b.sample_cells = _ptr(cells, C.c_uint32)
         return b
 
 

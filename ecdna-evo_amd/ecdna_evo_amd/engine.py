@@ -30,6 +30,7 @@ EXPORTS = [
     "ecdna_ssa_ctx_create",
     "ecdna_ssa_ctx_create_ext",
     "ecdna_ssa_ctx_create_passages",
+    "ecdna_ssa_ctx_create_cohort",
     "ecdna_ssa_ctx_set_outputs",
     "ecdna_ssa_ctx_launch",
     "ecdna_ssa_ctx_sync",
@@ -40,6 +41,7 @@ EXPORTS = [
     "ecdna_ssa_ctx_download_sample",
     "ecdna_ssa_ctx_download_snapshot_stats",
     "ecdna_ssa_ctx_download_passages",
+    "ecdna_ssa_ctx_download_cohort",
     "ecdna_ssa_ctx_accept",
     "ecdna_ssa_ctx_download_accept",
     "ecdna_ssa_ctx_select",
@@ -159,6 +161,13 @@ def lib():
         L.ecdna_ssa_ctx_select_digits.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
                                                   C.c_void_p, C.c_void_p]
         L.ecdna_ssa_ctx_select_digits.restype = C.c_int
+    # (likewise added within v13: a cohort of targets; Context raises when a spec asks an earlier library for it)
+    if hasattr(L, "ecdna_ssa_ctx_create_cohort"):
+        L.ecdna_ssa_ctx_create_cohort.argtypes = [P(abi.Params), P(abi.Ext), P(abi.Passages), P(abi.Cohort),
+                                                  P(C.c_void_p)]
+        L.ecdna_ssa_ctx_create_cohort.restype = C.c_int
+        L.ecdna_ssa_ctx_download_cohort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ecdna_ssa_ctx_download_cohort.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -239,6 +248,8 @@ class Result:
         # RunSpec.n_passages = G > 0: every growth phase's results (PassageResult), each array with a leading G axis;
         # the fields above are then the last phase's
         self.passages = None
+        # RunSpec.cohort_targets (P of them): every replicate's records against every target (CohortResult)
+        self.cohort = None
 
     def row(self, i: int) -> np.ndarray:
         return self.rows[i, : int(self.summaries[i]["nplus"])]
@@ -259,6 +270,16 @@ class PassageResult:
         self.sample_stats = sample_stats
         self.hist = hist
         self.sample_hist = sample_hist
+
+
+class CohortResult:
+    """One run scored against a cohort of P targets (ecdna_ssa_ctx_download_cohort, cohort mapping v1): stats [P][n]
+    abi.STATS_DTYPE, replicate i's whole final population against target p, and sample_stats [P][n], its sample of
+    cohort_sample_cells[p] cells against target p (None without sample sizes)."""
+
+    def __init__(self, stats, sample_stats):
+        self.stats = stats
+        self.sample_stats = sample_stats
 
 
 class AcceptResult:
@@ -325,15 +346,25 @@ class Context:
     """A device-resident run (ecdna_ssa_ctx): create once, launch many times."""
 
     def __init__(self, spec: "abi.RunSpec", ext: Optional["abi.Ext"] = None,
-                 passages: Optional["abi.Passages"] = None):
+                 passages: Optional["abi.Passages"] = None, cohort: Optional["abi.Cohort"] = None):
         """`ext`: an explicit extension block (ecdna_ssa_ctx_create_ext); default: the one `spec` asks for, if any.
-        `passages`: likewise the passage block (ecdna_ssa_ctx_create_passages)."""
+        `passages`: likewise the passage block (ecdna_ssa_ctx_create_passages), `cohort`: the cohort block
+        (ecdna_ssa_ctx_create_cohort)."""
         self.spec = spec
         self.params = spec.params()
         self.ext = ext if ext is not None else spec.ext()
         self.passages = passages if passages is not None else spec.passages()
+        self.cohort = cohort if cohort is not None else spec.cohort()
         h = C.c_void_p()
-        if self.passages is not None:  # (only a spec that asks for passages goes through _passages)
+        if self.cohort is not None:  # (only a spec that asks for a cohort goes through _cohort)
+            if not hasattr(lib(), "ecdna_ssa_ctx_create_cohort"):
+                raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_cohort (a cohort of targets)")
+            _check(lib().ecdna_ssa_ctx_create_cohort(C.byref(self.params),
+                                                     C.byref(self.ext) if self.ext is not None else None,
+                                                     C.byref(self.passages) if self.passages is not None else None,
+                                                     C.byref(self.cohort), C.byref(h)),
+                   "ecdna_ssa_ctx_create_cohort")
+        elif self.passages is not None:  # (only a spec that asks for passages goes through _passages)
             if not hasattr(lib(), "ecdna_ssa_ctx_create_passages"):
                 raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_passages (serial passaging)")
             _check(lib().ecdna_ssa_ctx_create_passages(C.byref(self.params),
@@ -393,7 +424,9 @@ class Context:
         return int(lib().ecdna_ssa_ctx_row_stride(self.h))
 
     def accept_timepoints(self, source: int) -> int:
-        """T of an acceptance source: 1, the spec's snapshots, or its passages."""
+        """T of an acceptance source: 1, the spec's snapshots, its passages, or its cohort's targets."""
+        if source in (abi.ACCEPT_COHORT, abi.ACCEPT_COHORT_SAMPLES):
+            return int(self.cohort.n_targets) if self.cohort is not None else 0
         if source in (abi.ACCEPT_SNAPSHOTS, abi.ACCEPT_SNAPSHOT_SAMPLES):
             return int(self.params.n_snapshots)
         if source in (abi.ACCEPT_PASSAGES, abi.ACCEPT_PASSAGE_SAMPLES):
@@ -494,6 +527,20 @@ class Context:
                "ecdna_ssa_ctx_select_digits")
         return hist
 
+    def download_cohort(self) -> CohortResult:
+        """The cohort records of the last launch (ecdna_ssa_ctx_download_cohort): stats and sample_stats [P][n]."""
+        if not hasattr(lib(), "ecdna_ssa_ctx_download_cohort"):
+            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_download_cohort (a cohort of targets)")
+        if self.cohort is None:  # (the library refuses: ECDNA_E_STATE)
+            _check(lib().ecdna_ssa_ctx_download_cohort(self.h, None, None), "ecdna_ssa_ctx_download_cohort")
+            raise EngineError("ecdna_ssa_ctx_download_cohort: the context has no cohort block")
+        P_, n = int(self.cohort.n_targets), int(self.params.n_replicates)
+        st = np.zeros((P_, n), dtype=abi.STATS_DTYPE)
+        sst = np.zeros((P_, n), dtype=abi.STATS_DTYPE) if self.cohort.sample_cells else None
+        _check(lib().ecdna_ssa_ctx_download_cohort(self.h, st.ctypes.data, sst.ctypes.data if sst is not None else None),
+               "ecdna_ssa_ctx_download_cohort")
+        return CohortResult(st, sst)
+
     def download(self, want_rows: bool = False) -> Result:
         p = self.params
         summ = abi.summaries_array(p.n_replicates)
@@ -553,6 +600,8 @@ class Context:
                 self.h, out.summaries.ctypes.data, out.totals.ctypes.data, out.stats.ctypes.data,
                 out.sample_stats.ctypes.data, out.hist.ctypes.data, out.sample_hist.ctypes.data), "download_passages")
             res.passages = out
+        if self.cohort is not None:
+            res.cohort = self.download_cohort()
         if p.flags & abi.FLAG_REFERENCE_DRAWS:
             w = np.zeros(p.n_replicates, dtype=np.uint64)
             _check(lib().ecdna_ssa_ctx_download_rng_words(self.h, w.ctypes.data), "download_rng_words")

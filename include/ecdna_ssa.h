@@ -43,7 +43,13 @@
 extern "C" {
 #endif
 
-/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): ABC thresholds on the
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): one sweep scored
+ * against a cohort of targets on the GPU — several patients, or several biopsies of one tumour, each with its own
+ * copy-number histogram and its own number of measured cells: the cohort block ecdna_ssa_cohort_t,
+ * ecdna_ssa_ctx_create_cohort and ecdna_ssa_ctx_download_cohort, and the acceptance sources ECDNA_ACCEPT_COHORT and
+ * ECDNA_ACCEPT_COHORT_SAMPLES (below; cohort mapping v1). ecdna_ssa_ctx_create_passages(p, ext, passages, out) is
+ * ecdna_ssa_ctx_create_cohort(p, ext, passages, NULL, out): a context without the block allocates and launches nothing new.
+ * Added within v13 (additive: no layout and no existing function changes, the version stays 13): ABC thresholds on the
  * GPU — exact order statistics of the distances among the error-free replicates by an 8-bit radix select over the
  * statistics a context already holds, ecdna_ssa_ctx_select and its shard primitive ecdna_ssa_ctx_select_digits (below;
  * select mapping v1). A context that never calls them allocates and launches nothing new.
@@ -426,6 +432,48 @@ int ecdna_ssa_ctx_create_passages(const ecdna_ssa_params_t* p, const ecdna_ssa_e
 int ecdna_ssa_ctx_download_passages(ecdna_ssa_ctx* c, ecdna_rep_summary_t* out_summaries, ecdna_totals_t* out_totals,
                                     ecdna_rep_stats_t* out_stats, ecdna_rep_stats_t* out_sample_stats,
                                     uint64_t* out_hist, uint64_t* out_sample_hist);
+
+/* A cohort of targets (added within ABI v13): several patients, or several biopsies of one tumour, each with its own
+ * copy-number histogram and its own number of measured cells, scored against ONE sweep. The simulations are the
+ * expensive part of an ABC inference and do not depend on the target: with the block, one more end-of-run pass per chunk
+ * scores every replicate's final state against all P targets, so one sweep serves P inferences. The records stay on the
+ * device for ecdna_ssa_ctx_accept / ecdna_ssa_ctx_select (the sources ECDNA_ACCEPT_COHORT and
+ * ECDNA_ACCEPT_COHORT_SAMPLES below, where timepoint p is target p), so chunked sweeps are covered.
+ *
+ * Cohort mapping v1. With P = n_targets, n = n_replicates:
+ *  - Full records. stats[p][i] is the ecdna_rep_stats_t of replicate i's whole final population, scored against target
+ *    p: byte for byte the record ecdna_ssa_ctx_download_stats returns for the same run with stats_target_hist =
+ *    target_hists[p]. mean, entropy, frequency and cells are therefore the same for every p.
+ *  - Sample records (sample_cells != NULL). sample_stats[p][i] is byte for byte the record ecdna_ssa_ctx_download_sample
+ *    returns for the same run with stats_target_hist = target_hists[p] and subsample_cells = sample_cells[p]. It follows
+ *    subsample mapping v1 (ecdna_ssa_params_t.subsample_cells above) unchanged: stream field 0, counter
+ *    (i, 0xC0000000 | t, r lo, r hi), the run's key, r the GLOBAL id. Two targets with equal sample_cells see the same
+ *    sample. The records do not depend on chunk, shard, grid or device.
+ *  - params.stats_target_hist and params.subsample_cells keep their meaning: ecdna_ssa_ctx_download_stats and
+ *    ecdna_ssa_ctx_download_sample are unchanged and independent of the block, as is every other output.
+ *  - The cohort adds no pooled histograms: the pooled histogram does not depend on a target.
+ *  - Buffers are sized by the run — [P][n] records of 64 B, twice when samples are on — and allocated at create:
+ *    ECDNA_E_NOMEM if they do not fit (the message says how many bytes were asked for). Chunked runs are covered.
+ * Rejected at create (ECDNA_E_INVALID, before a device is touched, the message names the field): a wrong struct_size,
+ * n_targets outside 1 .. 64, NULL target_hists, an all-zero target row, a sample_cells[p] outside 1 .. 4096,
+ * reserved != 0, ECDNA_FLAG_REP_STATS missing, and a non-NULL passages, or ext->snapshot_stats, together with a cohort
+ * block (cohorts of longitudinal targets are a different feature). */
+typedef struct {
+    uint32_t struct_size;            /* sizeof(ecdna_ssa_cohort_t); anything else: ECDNA_E_INVALID */
+    uint32_t n_targets;              /* P, 1 .. 64 (one bit each of a timepoint mask) */
+    const uint64_t* target_hists;    /* host, [P][hist_bins], binned as stats_target_hist */
+    const uint32_t* sample_cells;    /* host, [P], each 1 .. 4096: target p's sample size m_p; NULL: no samples */
+    uint64_t reserved;               /* must be 0 */
+} ecdna_ssa_cohort_t;
+/* ecdna_ssa_ctx_create_passages with a cohort block. cohort == NULL: exactly ecdna_ssa_ctx_create_passages — nothing
+ * more is allocated or launched. The three older create calls forward to this one. */
+int ecdna_ssa_ctx_create_cohort(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                                const ecdna_ssa_passages_t* passages, const ecdna_ssa_cohort_t* cohort,
+                                ecdna_ssa_ctx** out);
+/* The cohort records of the last launch, [P][n] each (cohort mapping v1); either buffer may be NULL. ECDNA_E_STATE:
+ * before a launch, on a context without the block, and when out_sample_stats is asked for with sample_cells == NULL. */
+int ecdna_ssa_ctx_download_cohort(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats /* [P][n] */,
+                                  ecdna_rep_stats_t* out_sample_stats /* [P][n] */);
 /* Use caller-owned DEVICE buffers for the histogram [n_param_sets*hist_bins] u64 and totals
  * [n_param_sets] (e.g. tensors later all-reduced over RCCL). NULL keeps the internal buffer. */
 int ecdna_ssa_ctx_set_outputs(ecdna_ssa_ctx* c, uint64_t* d_hist, ecdna_totals_t* d_totals);
@@ -435,7 +483,7 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream);
 /* Block until the last launch finished; returns its device time in ms (HIP events on the launch
  * stream): ssa_ms = SSA stepper kernels only, hist_ms = histogram/summary kernels (and the
  * subsampling pass when params.subsample_cells > 0, and the snapshot statistics pass under
- * ecdna_ssa_ext_t.snapshot_stats). Either may be NULL. */
+ * ecdna_ssa_ext_t.snapshot_stats, and the cohort pass under ecdna_ssa_cohort_t). Either may be NULL. */
 int ecdna_ssa_ctx_sync(ecdna_ssa_ctx* c, float* ssa_ms, float* hist_ms);
 /* Device pointers of the current outputs. */
 int ecdna_ssa_ctx_device_outputs(ecdna_ssa_ctx* c, uint64_t** d_hist, ecdna_totals_t** d_totals);
@@ -484,8 +532,15 @@ typedef enum {
     ECDNA_ACCEPT_SNAPSHOTS = 2,        /* download_snapshot_stats' out_stats, T = n_snapshots */
     ECDNA_ACCEPT_SNAPSHOT_SAMPLES = 3, /* ... out_sample_stats, T = n_snapshots */
     ECDNA_ACCEPT_PASSAGES = 4,         /* download_passages' out_stats, T = n_passages */
-    ECDNA_ACCEPT_PASSAGE_SAMPLES = 5   /* ... out_sample_stats, T = n_passages */
+    ECDNA_ACCEPT_PASSAGE_SAMPLES = 5,  /* ... out_sample_stats, T = n_passages */
+    /* (6 and 7 are not sources: ECDNA_E_INVALID) */
+    ECDNA_ACCEPT_COHORT = 8,           /* download_cohort's out_stats, T = n_targets: timepoint p is target p */
+    ECDNA_ACCEPT_COHORT_SAMPLES = 9    /* ... out_sample_stats, T = n_targets (needs sample_cells) */
 } ecdna_accept_source_t;
+/* The cohort sources: the error rule is the one-summary rule of ECDNA_ACCEPT_FINAL; the records lie [P][n] (rep stride 1,
+ * timepoint stride n, error stride 0); timepoint_mask = 1 << p gives patient p's acceptance or quantiles, 0 all P
+ * jointly, as for every source. A context without the cohort block returns ECDNA_E_STATE for both, and so does
+ * ECDNA_ACCEPT_COHORT_SAMPLES without sample_cells. */
 
 /* One threshold row: the largest accepted value of each of the four distances of ecdna_rep_stats_t. Each must be
  * >= 0 (not NaN); +inf switches that statistic off. */
