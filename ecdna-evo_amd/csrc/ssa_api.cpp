@@ -1,7 +1,8 @@
 // ssa_api.cpp — the C ABI of include/ecdna_ssa.h: parameter validation,
 // device-resident run contexts, chunking by HBM capacity, and launches of the
 // stepper and end-of-run kernels (ssa_kernels.hip, ssa_hist.hip, ssa_subsample.hip, ssa_snapstats.hip,
-// ssa_passage.hip, ssa_cohort.hip) and of the post-launch acceptance pass (ssa_accept.hip).
+// ssa_passage.hip, ssa_cohort.hip), of the post-launch acceptance pass (ssa_accept.hip) and of the passes over the kept
+// samples (ssa_rescore.hip).
 //
 // This file replaces, for one GPU, the per-replicate driver loop of the
 // reference: run_simulations(idx) mapped by rayon over seed*10 .. seed*10+runs
@@ -21,6 +22,7 @@
 
 #include "../../include/ecdna_ssa.h"
 #include "ssa_cohort.hpp"
+#include "ssa_keep.hpp"
 #include "ssa_launch.h"
 #include "ssa_plan.hpp"
 #include "ssa_select.hpp"
@@ -354,6 +356,19 @@ struct ecdna_ssa_ctx {
     bool sel_keys_valid = false;
     uint32_t sel_source = 0;
     uint64_t sel_tmask = 0;
+    // the kept samples (ecdna_ssa_keep_t; keep_m = 0: no block): headers [n] and cells [n][keep_m], sized by the run and
+    // written by the keep pass of every chunk. The passes over them keep buffers that belong to the context as the
+    // acceptance pass's do: the rescored records [P][n] with the targets' CDFs [P][bins] and scalars [P][3] (and their
+    // host copies, which an asynchronous upload reads), the pooled histogram, and the gather's index and staging.
+    uint32_t keep_m = 0;
+    uint2* d_kept_headers = nullptr;
+    uint16_t* d_kept_cells = nullptr;
+    AcceptBuf rs_stats, rs_cdf, rs_scalars, pool_hist, gat_index, gat_headers, gat_cells;
+    std::vector<double> rs_cdf_host, rs_scalars_host;
+    bool rescore_valid = false;   // (a launch invalidates the records)
+    bool rescore_pending = false; // a rescore was enqueued since the stream was last drained
+    uint32_t rescore_targets = 0; // the P of the last rescore
+    hipStream_t rescore_stream = nullptr;
 };
 
 namespace {
@@ -384,7 +399,8 @@ void free_ctx(ecdna_ssa_ctx* c) {
             if (e) (void)hipEventDestroy(e);
     for (void* d : c->owned) (void)hipFree(d);
     for (AcceptBuf* b : {&c->acc_mask, &c->acc_counts, &c->acc_blocks, &c->acc_ids, &c->acc_list, &c->sel_keys,
-                         &c->sel_hist})
+                         &c->sel_hist, &c->rs_stats, &c->rs_cdf, &c->rs_scalars, &c->pool_hist, &c->gat_index,
+                         &c->gat_headers, &c->gat_cells})
         if (b->ptr) (void)hipFree(b->ptr);
     delete c;
 }
@@ -570,6 +586,22 @@ int adopt_cohort(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_
     return ECDNA_OK;
 }
 
+// The keep block: the kept samples' headers and cells, sized by the run.
+int adopt_keep(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_keep_t* keep) {
+    c->keep_m = keep->keep_cells;
+    const uint64_t n1 = std::max<uint64_t>(p->n_replicates, 1);
+    const uint64_t bytes = ecdna::keep::cells_bytes(n1, c->keep_m) + ecdna::keep::headers_bytes(n1);
+    hipError_t e = ctx_alloc(c, &c->d_kept_headers, n1);
+    if (e == hipSuccess) e = ctx_alloc(c, &c->d_kept_cells, n1 * c->keep_m);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? ECDNA_E_NOMEM : ECDNA_E_HIP,
+                    "ecdna_ssa_ctx_create_keep: the kept samples (" + std::to_string(bytes) +
+                        " bytes) do not fit: " + hipGetErrorString(e));
+    }
+    return ECDNA_OK;
+}
+
 // Outputs sized by the run (not by the chunk).
 int alloc_outputs(ecdna_ssa_ctx* c) {
     const ecdna_ssa_params_t& p = c->p;
@@ -714,12 +746,13 @@ int alloc_plan(ecdna_ssa_ctx* c, const ecdna::plan::LaunchPlan& pl, const float*
 // Gather, plan, allocate: what the run's shape and the device say, the plan they give (ssa_plan.hpp: every launch
 // decision of create), and the buffers the plan asks for.
 int build_ctx(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
-              const ecdna_ssa_passages_t* pas, const ecdna_ssa_cohort_t* co) {
+              const ecdna_ssa_passages_t* pas, const ecdna_ssa_cohort_t* co, const ecdna_ssa_keep_t* keep) {
     const ecdna::plan::Knobs knobs = ecdna::plan::knobs_from_env();
     const ecdna::plan::RunShape shape = adopt_params(c, p, ext, pas, knobs);
     TRY(upload_inputs(c));
     TRY(upload_targets(c, p, ext, pas));
     if (co) TRY(adopt_cohort(c, p, co));
+    if (keep) TRY(adopt_keep(c, p, keep));
     TRY(alloc_outputs(c));
     ecdna::plan::DeviceFacts facts;
     TRY(gather_facts(c, knobs, &facts));
@@ -914,6 +947,25 @@ int launch_passage_pass(const ecdna_ssa_ctx* c, const Chunk& ch, uint32_t g, con
     return ECDNA_OK;
 }
 
+// the chunk's kept samples, into the run's buffers (ssa_passage's KEEP instance: neither statistics nor a histogram)
+int launch_keep_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::FinalState& fs, ecdna::ChunkIds ids,
+                     hipStream_t st) {
+    ecdna::PassageArgs pa{};
+    pa.state = fs;
+    pa.founder_rows = c->d_kept_cells + ch.first * c->keep_m;
+    pa.founder_counts = c->d_kept_headers + ch.first;
+    pa.founder_stride = c->keep_m;
+    pa.seed = c->p.seed;
+    pa.m = c->keep_m;
+    pa.table_slots = ecdna::subsample_table_slots(pa.m);
+    pa.sort_slots = ecdna::passage_sort_slots(pa.m);
+    ids.reps_per_block = pass_reps_per_block(
+        c, ch.n, ecdna::keep_waves(ids.bins, fs.bag_k, pa.table_slots, pa.sort_slots, nullptr));
+    pa.ids = ids;
+    TRY(ecdna::launch_keep(pa, pass_blocks(ids), st));
+    return ECDNA_OK;
+}
+
 // the statistics of the chunk's snapshots, from the rows the stepper just saved
 int launch_snapstats_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::StepperArgs& a, ecdna::ChunkIds ids,
                           hipStream_t st) {
@@ -966,6 +1018,7 @@ int launch_chunk_phase(ecdna_ssa_ctx* c, size_t k, uint32_t g, hipStream_t st) {
     TRY(ecdna::launch_hist(h, pass_blocks(h.ids), st));
     if (p.subsample_cells) TRY(launch_subsample_pass(c, ch, fs, ids, target, st));
     if (c->n_cohort) TRY(launch_cohort_pass(c, ch, fs, ids, st));
+    if (c->keep_m) TRY(launch_keep_pass(c, ch, fs, ids, st));
     if (c->n_passages) TRY(launch_passage_pass(c, ch, g, fs, ids, target, a.seed, st));
     if (c->snap_stats) TRY(launch_snapstats_pass(c, ch, a, ids, st));
     TRY(hipEventRecord(ev[2], st));
@@ -980,7 +1033,7 @@ int launch_chunk_phase(ecdna_ssa_ctx* c, size_t k, uint32_t g, hipStream_t st) {
 // and 7 are not sources).
 bool is_accept_source(uint32_t source) {
     return source <= (uint32_t)ECDNA_ACCEPT_PASSAGE_SAMPLES || source == (uint32_t)ECDNA_ACCEPT_COHORT ||
-           source == (uint32_t)ECDNA_ACCEPT_COHORT_SAMPLES;
+           source == (uint32_t)ECDNA_ACCEPT_COHORT_SAMPLES || source == (uint32_t)ECDNA_ACCEPT_RESCORED;
 }
 struct AcceptSource {
     const ecdna_rep_stats_t* stats = nullptr;
@@ -1046,6 +1099,17 @@ int accept_source(const ecdna_ssa_ctx* c, uint32_t source, AcceptSource* out) {
             s.has_target = true;
             break;
         }
+        case ECDNA_ACCEPT_RESCORED:
+            if (!c->keep_m)
+                return fail(ECDNA_E_STATE, "accept.source RESCORED: the rescored records need ecdna_ssa_ctx_create_keep");
+            if (!c->launched || !c->rescore_valid)
+                return fail(ECDNA_E_STATE, "accept.source RESCORED: no records before ecdna_ssa_ctx_rescore (a launch "
+                                           "invalidates them)");
+            s.stats = static_cast<const ecdna_rep_stats_t*>(c->rs_stats.ptr);
+            s.T = c->rescore_targets;
+            s.tp_stride = c->p.n_replicates;  // [P][n], as the cohort's
+            s.has_target = true;
+            break;
         default:
             return fail(ECDNA_E_INVALID, "accept.source is not an ecdna_accept_source_t");
     }
@@ -1189,16 +1253,20 @@ int ecdna_dev_bin_schedule(int pair_ok, uint64_t pair_mode, uint64_t sched, uint
 }
 
 // (development / test entry point, not part of include/ecdna_ssa.h: the sampling passes' LDS plan of ssa_launch.h for
-// the CPU tests. pass 0 = ssa_subsample, 1 = ssa_passage, 2 = ssa_snapstats, where m = 0 means no samples)
+// the CPU tests. pass 0 = ssa_subsample, 1 = ssa_passage, 2 = ssa_snapstats, where m = 0 means no samples; the passes
+// of the keep block: 3 = the keep pass, 4 = ssa_rescore, 5 = ssa_pool_accepted, the last two whatever m and bag_k)
 int ecdna_dev_pass_lds(int pass, uint32_t bins, uint32_t bag_k, uint32_t m, uint32_t* waves, uint64_t* lds_bytes,
                        int* sample_hist_lds) {
-    if (pass < 0 || pass > 2 || (!m && pass != 2) || !waves || !lds_bytes || !sample_hist_lds)
+    if (pass < 0 || pass > 5 || (!m && pass != 2 && pass < 4) || !waves || !lds_bytes || !sample_hist_lds)
         return fail(ECDNA_E_INVALID, "ecdna_dev_pass_lds: unknown pass, m = 0 outside pass 2, or a NULL output");
     const uint32_t slots = m ? ecdna::subsample_table_slots(m) : 0u;
     size_t lds = 0;
     bool in_lds = false;
     *waves = pass == 0   ? ecdna::subsample_waves(bins, bag_k, slots, &lds)
              : pass == 1 ? ecdna::passage_waves(bins, bag_k, slots, ecdna::passage_sort_slots(m), &lds)
+             : pass == 3 ? ecdna::keep_waves(bins, bag_k, slots, ecdna::passage_sort_slots(m), &lds)
+             : pass == 4 ? ecdna::rescore_waves(bins, &lds)
+             : pass == 5 ? ecdna::pool_accepted_waves(bins, &lds)
                          : ecdna::snapstats_waves(bins, slots, &lds, &in_lds);
     *lds_bytes = lds;
     *sample_hist_lds = in_lds ? 1 : 0;
@@ -1247,6 +1315,11 @@ int ecdna_ssa_ctx_create_passages(const ecdna_ssa_params_t* p, const ecdna_ssa_e
 
 int ecdna_ssa_ctx_create_cohort(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
                                 const ecdna_ssa_passages_t* pas, const ecdna_ssa_cohort_t* co, ecdna_ssa_ctx** out) {
+    return ecdna_ssa_ctx_create_keep(p, ext, pas, co, nullptr, out);
+}
+
+int ecdna_ssa_ctx_create_keep(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, const ecdna_ssa_passages_t* pas,
+                              const ecdna_ssa_cohort_t* co, const ecdna_ssa_keep_t* keep, ecdna_ssa_ctx** out) {
     if (!out) return fail(ECDNA_E_INVALID, "out is NULL");
     *out = nullptr;
     TRY(validate(p, ext, pas));
@@ -1254,9 +1327,13 @@ int ecdna_ssa_ctx_create_cohort(const ecdna_ssa_params_t* p, const ecdna_ssa_ext
         const std::string why = ecdna::cohort::invalid(*p, ext, pas, *co);
         if (!why.empty()) return fail(ECDNA_E_INVALID, why);
     }
+    if (keep) {  // the keep block
+        const std::string why = ecdna::keep::invalid(*p, pas, *keep);
+        if (!why.empty()) return fail(ECDNA_E_INVALID, why);
+    }
     TRY(pick_device(p->device));
     ecdna_ssa_ctx* c = new ecdna_ssa_ctx();
-    if (int rc = build_ctx(c, p, ext, pas, co)) {
+    if (int rc = build_ctx(c, p, ext, pas, co, keep)) {
         free_ctx(c);
         return rc;
     }
@@ -1314,6 +1391,7 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
     c->launched = true;
     c->accept_valid = false;  // (the acceptance pass's results were the previous launch's)
     c->sel_keys_valid = false;  // (and the select passes' keys were made from its records)
+    c->rescore_valid = false;   // (and the rescored records from its kept samples)
     return ECDNA_OK;
 }
 
@@ -1647,6 +1725,153 @@ int ecdna_ssa_ctx_download_accept(ecdna_ssa_ctx* c, uint64_t* out_counts, uint32
     if (out_list_stats && listed)
         TRY(to_host(out_list_stats, static_cast<const ecdna_rep_stats_t*>(c->acc_list.ptr),
                     listed * c->acc_timepoints));
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_rescore(ecdna_ssa_ctx* c, uint32_t n_targets, const uint64_t* target_hists) {
+    const char* who = "ecdna_ssa_ctx_rescore";
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (n_targets < 1u || n_targets > ecdna::kMaxCohortTargets)
+        return fail(ECDNA_E_INVALID, "rescore.n_targets must be in [1, 64]");
+    if (!target_hists) return fail(ECDNA_E_INVALID, "rescore.target_hists is NULL");
+    const ecdna_ssa_params_t& p = c->p;
+    const uint32_t bins = p.hist_bins, P = n_targets;
+    const uint32_t empty = first_empty_target(target_hists, P, bins);
+    if (empty < P) return fail(ECDNA_E_INVALID, "rescore.target_hists[" + std::to_string(empty) + "] is empty");
+    if (!c->keep_m) return fail(ECDNA_E_STATE, "rescore: the kept samples need ecdna_ssa_ctx_create_keep");
+    TRY(ctx_launched(c, "rescore before launch"));
+    const uint64_t n = p.n_replicates;
+    TRY(hipSetDevice(c->device));
+    hipStream_t st = c->last_stream;
+    // an earlier rescore may still read the targets this one replaces (and its upload their host copies)
+    if (c->rescore_pending) TRY(hipStreamSynchronize(c->rescore_stream));
+    c->rescore_pending = false;
+    c->rescore_valid = false;
+    c->sel_keys_valid = false;  // (the select passes' keys may have been made from the records this call replaces)
+    TRY(accept_reserve(&c->rs_stats, std::max<uint64_t>(n, 1) * P * sizeof(ecdna_rep_stats_t), "records", who));
+    TRY(accept_reserve(&c->rs_cdf, (uint64_t)P * bins * sizeof(double), "target CDFs", who));
+    TRY(accept_reserve(&c->rs_scalars, (uint64_t)P * 3u * sizeof(double), "target scalars", who));
+    if (n) {
+        c->rs_cdf_host.resize((uint64_t)P * bins);
+        c->rs_scalars_host.resize((uint64_t)P * 3u);
+        summarize_targets(target_hists, P, bins, c->rs_cdf_host.data(), c->rs_scalars_host.data());
+        TRY(hipMemcpyAsync(c->rs_cdf.ptr, c->rs_cdf_host.data(), c->rs_cdf_host.size() * sizeof(double),
+                           hipMemcpyHostToDevice, st));
+        TRY(hipMemcpyAsync(c->rs_scalars.ptr, c->rs_scalars_host.data(), c->rs_scalars_host.size() * sizeof(double),
+                           hipMemcpyHostToDevice, st));
+        c->rescore_pending = true;
+        c->rescore_stream = st;
+        ecdna::RescoreArgs a{};
+        a.headers = c->d_kept_headers;
+        a.cells = c->d_kept_cells;
+        a.out = static_cast<ecdna_rep_stats_t*>(c->rs_stats.ptr);
+        a.target_cdf = static_cast<const double*>(c->rs_cdf.ptr);
+        a.target_scalars = static_cast<const double*>(c->rs_scalars.ptr);
+        a.n = (uint32_t)n;
+        a.m = c->keep_m;
+        a.bins = bins;
+        a.n_targets = P;
+        a.reps_per_block = pass_reps_per_block(c, (uint32_t)n, ecdna::rescore_waves(bins, nullptr));
+        TRY(ecdna::launch_rescore(a, st));
+    }
+    c->rescore_targets = P;
+    c->rescore_valid = true;
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_download_rescored(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!c->keep_m) return fail(ECDNA_E_STATE, "download_rescored: the kept samples need ecdna_ssa_ctx_create_keep");
+    if (!c->launched || !c->rescore_valid)
+        return fail(ECDNA_E_STATE, "download_rescored before rescore (a launch invalidates the rescored records)");
+    TRY(ctx_drain(c));
+    const uint64_t records = (uint64_t)c->rescore_targets * c->p.n_replicates;
+    if (out && records) TRY(to_host(out, static_cast<const ecdna_rep_stats_t*>(c->rs_stats.ptr), records));
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_pool_accepted(ecdna_ssa_ctx* c, uint32_t threshold, uint64_t* out_hist) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!out_hist) return fail(ECDNA_E_INVALID, "pool_accepted.out_hist is NULL");
+    if (!c->keep_m) return fail(ECDNA_E_STATE, "pool_accepted: the kept samples need ecdna_ssa_ctx_create_keep");
+    if (!c->launched || !c->accept_valid)
+        return fail(ECDNA_E_STATE, "pool_accepted before accept (a launch invalidates the acceptance results)");
+    if (threshold >= c->acc_rows)
+        return fail(ECDNA_E_INVALID, "pool_accepted.threshold must be < n_thresholds of the last accept");
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t n = p.n_replicates, nb = (uint64_t)p.n_param_sets * p.hist_bins;
+    std::fill(out_hist, out_hist + nb, 0ull);
+    if (!n) return ECDNA_OK;
+    TRY(hipSetDevice(c->device));
+    hipStream_t st = c->last_stream;
+    TRY(accept_reserve(&c->pool_hist, nb * sizeof(uint64_t), "histogram", "ecdna_ssa_ctx_pool_accepted"));
+    TRY(hipMemsetAsync(c->pool_hist.ptr, 0, nb * sizeof(uint64_t), st));
+    ecdna::PoolAcceptedArgs a{};
+    a.headers = c->d_kept_headers;
+    a.cells = c->d_kept_cells;
+    a.mask = static_cast<const uint32_t*>(c->acc_mask.ptr);
+    a.hist = static_cast<unsigned long long*>(c->pool_hist.ptr);
+    a.rid0 = p.first_replicate;
+    a.rid_stride = p.replicate_stride ? p.replicate_stride : 1u;
+    a.reps_per_set = p.reps_per_set;
+    a.n = (uint32_t)n;
+    a.m = c->keep_m;
+    a.bins = p.hist_bins;
+    a.q = threshold;
+    // (the histogram pass's share: about one parameter set per workgroup in a sweep of small sets)
+    const uint64_t set_local = std::max<uint64_t>(1, p.reps_per_set / a.rid_stride);
+    a.reps_per_block = pass_reps_per_block(
+        c, (uint32_t)n, (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(ecdna::kPoolBlock, set_local)));
+    TRY(ecdna::launch_pool_accepted(a, st));
+    TRY(hipStreamSynchronize(st));
+    TRY(to_host(out_hist, static_cast<const uint64_t*>(c->pool_hist.ptr), nb));
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_download_kept(ecdna_ssa_ctx* c, uint64_t n_ids, const uint64_t* ids, ecdna_kept_t* out_headers,
+                                uint16_t* out_cells) {
+    static_assert(sizeof(ecdna_kept_t) == sizeof(uint2), "a kept header is two u32 words");
+    const char* who = "ecdna_ssa_ctx_download_kept";
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t n = p.n_replicates, stride = p.replicate_stride ? p.replicate_stride : 1u;
+    if (!ids && n_ids > n) return fail(ECDNA_E_INVALID, "download_kept.n_ids must be <= n_replicates when ids is NULL");
+    std::vector<uint32_t> index(ids ? n_ids : 0);
+    for (uint64_t j = 0; ids && j < n_ids; ++j) {
+        uint64_t i = 0;
+        if (!ecdna::keep::index_of(ids[j], p.first_replicate, stride, n, &i))
+            return fail(ECDNA_E_INVALID, "download_kept.ids[" + std::to_string(j) + "] = " + std::to_string(ids[j]) +
+                                             " is not a replicate of this call");
+        index[j] = (uint32_t)i;
+    }
+    if (!c->keep_m) return fail(ECDNA_E_STATE, "download_kept: the kept samples need ecdna_ssa_ctx_create_keep");
+    TRY(ctx_launched(c));
+    if (!n_ids || (!out_headers && !out_cells)) return ECDNA_OK;
+    TRY(ctx_drain(c));
+    const uint64_t m = c->keep_m;
+    const uint2* d_headers = c->d_kept_headers;
+    const uint16_t* d_cells = c->d_kept_cells;
+    if (ids) {  // gathered on the device in the order of ids
+        TRY(accept_reserve(&c->gat_index, n_ids * sizeof(uint32_t), "index", who));
+        TRY(accept_reserve(&c->gat_headers, n_ids * sizeof(uint2), "headers", who));
+        TRY(accept_reserve(&c->gat_cells, n_ids * m * sizeof(uint16_t), "cells", who));
+        hipStream_t st = c->last_stream;
+        TRY(hipMemcpy(c->gat_index.ptr, index.data(), n_ids * sizeof(uint32_t), hipMemcpyHostToDevice));
+        ecdna::KeptGatherArgs a{};
+        a.headers = d_headers;
+        a.cells = d_cells;
+        a.index = static_cast<const uint32_t*>(c->gat_index.ptr);
+        a.out_headers = static_cast<uint2*>(c->gat_headers.ptr);
+        a.out_cells = static_cast<uint16_t*>(c->gat_cells.ptr);
+        a.n_ids = (uint32_t)n_ids;
+        a.m = (uint32_t)m;
+        TRY(ecdna::launch_kept_gather(a, st));
+        TRY(hipStreamSynchronize(st));
+        d_headers = a.out_headers;
+        d_cells = a.out_cells;
+    }
+    if (out_headers) TRY(hipMemcpy(out_headers, d_headers, n_ids * sizeof(uint2), hipMemcpyDeviceToHost));
+    if (out_cells) TRY(to_host(out_cells, d_cells, n_ids * m));
     return ECDNA_OK;
 }
 

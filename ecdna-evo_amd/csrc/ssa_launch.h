@@ -1,7 +1,7 @@
 // ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by the device
 // code (steppers: ssa_kernels.hip, ssa_refdraws.hip; end-of-run passes: ssa_hist.hip,
-// ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip, ssa_cohort.hip; the acceptance pass: ssa_accept.hip; the
-// select passes: ssa_select.hip) and ssa_api.cpp (the C ABI).
+// ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip, ssa_cohort.hip; the passes over the kept samples:
+// ssa_rescore.hip; the acceptance pass: ssa_accept.hip; the select passes: ssa_select.hip) and ssa_api.cpp (the C ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -215,6 +215,50 @@ struct CohortArgs {
     uint32_t group_targets[kMaxCohortTargets];
 };
 
+// The kept samples (ecdna_ssa_keep_t, keep mapping v1). The keep pass over one chunk is ssa_passage's KEEP instance on a
+// PassageArgs block: founder_rows / founder_counts are the run's kept cells [n][m] and headers [n] at the chunk's offset,
+// founder_stride = m; stats, sample_hist and target are not read. The passes over the kept samples of the whole run:
+// ssa_rescore scores them against P targets given after the launch, one wave per replicate (records [P][n]);
+struct RescoreArgs {
+    const uint2* headers;                 // [n] {n-, n+}; {0xffffffff, 0xffffffff}: the guard ended the sample
+    const uint16_t* cells;                // [n][m]: the N+ cells' true copy numbers
+    ecdna_rep_stats_t* out;               // [P][n]
+    const double* target_cdf;             // [P][bins]
+    const double* target_scalars;         // [P][3]: the targets' mean, entropy, N+ frequency
+    uint32_t n;                           // replicates of the run
+    uint32_t m;                           // keep_cells
+    uint32_t bins;
+    uint32_t n_targets;                   // P, 1 .. kMaxCohortTargets
+    uint32_t reps_per_block;
+};
+// ssa_pool_accepted sums, per global parameter set, the histograms of the kept samples whose mask bit q is set (hist
+// zeroed on the stream before it);
+struct PoolAcceptedArgs {
+    const uint2* headers;
+    const uint16_t* cells;
+    const uint32_t* mask;                 // [n]: the acceptance pass's
+    unsigned long long* hist;             // [n_sets][bins]
+    uint64_t rid0, rid_stride, reps_per_set;
+    uint32_t n;
+    uint32_t m;
+    uint32_t bins;
+    uint32_t q;                           // the threshold row, < kMaxAcceptRows
+    uint32_t reps_per_block;
+};
+// ssa_kept_gather copies the kept samples of the listed replicates, one wave each, in the list's order.
+struct KeptGatherArgs {
+    const uint2* headers;
+    const uint16_t* cells;
+    const uint32_t* index;                // [n_ids]: replicate indices of the call, each < n (checked on the host)
+    uint2* out_headers;                   // [n_ids]
+    uint16_t* out_cells;                  // [n_ids][m]
+    uint32_t n_ids;
+    uint32_t m;
+};
+constexpr uint32_t kKeptGuard = 0xffffffffu;  // both words of the header of a sample the guard ended
+constexpr int kPoolBlock = 256;
+constexpr int kGatherBlock = 256;
+
 // The acceptance pass over the whole run (ssa_accept.hip; ecdna_ssa_ctx_accept, acceptance mapping v1): ABC rejection
 // over statistics the context already holds. Replicate i's record of timepoint t is stats[i * rep_stride + t * tp_stride]
 // (one record: strides 1, 0; snapshots [n][S]: S, 1; passages [G][n]: 1, n) and the error word of its phase t is
@@ -361,6 +405,26 @@ inline uint32_t cohort_scratch_words(uint32_t bins, uint32_t table_slots) {
 inline uint32_t cohort_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, size_t* lds_bytes) {
     return pass_waves(0, (2u * (size_t)bins + bag_k + cohort_scratch_words(bins, table_slots)) * 4u, lds_bytes);
 }
+// the keep pass (ssa_passage's KEEP instance): the passage pass's plan — per wave histogram, prefix sums, table (u32)
+// and the kept cells (u16) while they are sorted; no workgroup histogram
+inline uint32_t keep_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, uint32_t sort_slots,
+                           size_t* lds_bytes) {
+    return passage_waves(bins, bag_k, table_slots, sort_slots, lds_bytes);
+}
+// ssa_rescore: per wave the kept sample's histogram (u32 per bin) and its CDF (f64 per bin): 24 KiB at 2,048 bins
+inline uint32_t rescore_waves(uint32_t bins, size_t* lds_bytes) {
+    return pass_waves(0, (size_t)bins * 4u + (size_t)bins * 8u, lds_bytes);
+}
+// ssa_pool_accepted: the workgroup's u64 sum of the accepted samples' histograms (one parameter set at a time), 16 KiB
+// at 2,048 bins; its waves keep nothing of their own
+inline uint32_t pool_accepted_waves(uint32_t bins, size_t* lds_bytes) {
+    if (lds_bytes) *lds_bytes = (size_t)bins * 8u;
+    return (uint32_t)kPoolBlock / 64u;
+}
+hipError_t launch_keep(const PassageArgs& a, uint32_t blocks, hipStream_t stream);
+hipError_t launch_rescore(const RescoreArgs& a, hipStream_t stream);
+hipError_t launch_pool_accepted(const PoolAcceptedArgs& a, hipStream_t stream);
+hipError_t launch_kept_gather(const KeptGatherArgs& a, hipStream_t stream);
 hipError_t launch_subsample(const SubsampleArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_cohort(const CohortArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_snapstats(const SnapStatsArgs& a, uint32_t blocks, hipStream_t stream);

@@ -18,6 +18,12 @@
 // ended (all-zero statistics) founds the empty population, as does an empty one.
 // The samples' non-zero bins go to global memory directly: a workgroup histogram beside 2,048 bins and m = 4096 would
 // not fit 64 KiB of LDS.
+//
+// The keep pass (ecdna_ssa_keep_t, keep mapping v1) is the same kernel's KEEP instance: the sample of the end-of-run
+// population is materialised in the founder format — the same picks, complement walk, whole population, sort and
+// {n-, n+} header — into the run's kept buffers, and nothing else: no statistics, no pooled histogram (the sample's
+// records are made later, from the kept cells, by ssa_rescore). A sample the guard ended keeps the header
+// {0xffffffff, 0xffffffff} instead of the empty population.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -57,7 +63,9 @@ __device__ __forceinline__ void wave_bitonic_sort_u16(uint16_t* fs, uint32_t P, 
 
 // BAG as in ssa_hist: 0 = rows only; 1 / 2 = u16 / u32 bin counters bags[q][bag_k] for copy numbers 1..bag_k plus
 // the large-k cells at the head of the row.
-template <int BAG>
+// KEEP: the keep pass (founder_rows / founder_counts are the kept cells and headers; stats, sample_hist and target are
+// not read).
+template <int BAG, bool KEEP>
 __global__ void __launch_bounds__(kPasBlock) ssa_passage(const PassageArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const ChunkIds& ids = a.ids;
@@ -122,9 +130,10 @@ __global__ void __launch_bounds__(kPasBlock) ssa_passage(const PassageArgs a) {
 
         // 5. statistics of the sample histogram, its bins added to the set's sample histogram in global memory
         const uint32_t nminus_s = wh[0];  // the sample's N- cells (whole: all of them; complement: those left)
-        wave_sample_stats(plan, bad, a.m, nm + (uint64_t)np, np, ksum, psum, wh,
-                          reinterpret_cast<unsigned long long*>(a.sample_hist + set * ids.bins), ids.bins, a.target, lane,
-                          a.stats + q);
+        if (!KEEP)
+            wave_sample_stats(plan, bad, a.m, nm + (uint64_t)np, np, ksum, psum, wh,
+                              reinterpret_cast<unsigned long long*>(a.sample_hist + set * ids.bins), ids.bins, a.target,
+                              lane, a.stats + q);
 
         // 6. the founders, ascending
         if (want) {
@@ -136,7 +145,9 @@ __global__ void __launch_bounds__(kPasBlock) ssa_passage(const PassageArgs a) {
             }
             uint16_t* out = a.founder_rows + (uint64_t)q * a.founder_stride;
             for (uint32_t j = lane; j < gn; j += 64u) out[j] = fs[j];
-            if (lane == 0) a.founder_counts[q] = make_uint2(fbad ? 0u : nminus_s, gn);
+            if (lane == 0)
+                a.founder_counts[q] =
+                    KEEP && fbad ? make_uint2(kKeptGuard, kKeptGuard) : make_uint2(fbad ? 0u : nminus_s, gn);
         }
         wave_sync_lds();  // wh and fs are reset for the wave's next replicate
     }
@@ -151,8 +162,22 @@ hipError_t launch_passage(const PassageArgs& a, uint32_t blocks, hipStream_t str
     const uint32_t nw = passage_waves(a.ids.bins, a.state.bag_k, a.table_slots, a.sort_slots, &lds);
     if (lds > kPassLdsMax || a.m > a.founder_stride || a.sort_slots < 64u || (a.sort_slots & (a.sort_slots - 1u)))
         return hipErrorInvalidValue;
-    static const void* const table[3] = {(const void*)ssa_passage<0>, (const void*)ssa_passage<1>,
-                                         (const void*)ssa_passage<2>};
+    static const void* const table[3] = {(const void*)ssa_passage<0, false>, (const void*)ssa_passage<1, false>,
+                                         (const void*)ssa_passage<2, false>};
+    return hipLaunchKernel(table[bag_index(a.state)], dim3(blocks), dim3(nw * 64u), args, lds, stream);
+}
+
+hipError_t launch_keep(const PassageArgs& a, uint32_t blocks, hipStream_t stream) {
+    PassageArgs copy = a;
+    void* args[] = {&copy};
+    size_t lds = 0;
+    const uint32_t nw = keep_waves(a.ids.bins, a.state.bag_k, a.table_slots, a.sort_slots, &lds);
+    // (a kept row is m cells: the kernel never writes a row past min(m, sort_slots))
+    if (lds > kPassLdsMax || !a.founder_rows || !a.founder_counts || a.m > a.founder_stride || a.sort_slots < 64u ||
+        (a.sort_slots & (a.sort_slots - 1u)))
+        return hipErrorInvalidValue;
+    static const void* const table[3] = {(const void*)ssa_passage<0, true>, (const void*)ssa_passage<1, true>,
+                                         (const void*)ssa_passage<2, true>};
     return hipLaunchKernel(table[bag_index(a.state)], dim3(blocks), dim3(nw * 64u), args, lds, stream);
 }
 

@@ -2,7 +2,9 @@
 // ssa_snapstats.hip, the last three through ssa_sampledraw.hpp too; wave_sum also the development counters of
 // ssa_refdraws.hip): wave reductions and the inclusive scan, the wave's LDS ordering
 // point, a chunk's parameter-set segments, the bin-counter read, and the one routine for
-// the per-replicate ABC statistics. Plain functions over one 64-lane wave; every lane of the wave calls them.
+// the per-replicate ABC statistics, with its sibling for a list of targets (wave_cohort_stats: ssa_cohort.hip and
+// ssa_rescore.hip perform the same operations in the same order through it, which is what makes a rescored record the
+// launch-time record byte for byte). Plain functions over one 64-lane wave; every lane of the wave calls them.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -102,6 +104,55 @@ __device__ __forceinline__ void wave_rep_stats(const uint32_t* wh, unsigned long
         st.entropy_rel = has_target ? (target_entropy > 0.0 ? de / target_entropy : de) : 0.0;
         st.frequency_diff = has_target ? fabs(st.frequency - target_freq) : 0.0;
         *out = st;
+    }
+}
+
+// The sibling of wave_rep_stats for a list of targets: the statistics of the population whose histogram wh[bins] holds
+// against targets list[0 .. count) (list == nullptr: targets 0 .. count - 1), count <= 64, written to
+// out[target * out_stride]. Nothing is added to a workgroup histogram. cells, ksum and nplus are wave totals; wh must be
+// complete (wave_sync_lds). F[bins] is the wave's scratch for the population's CDF; every lane reads back only the bins
+// it wrote (b = lane mod 64). Per target the operations and their order are wave_rep_stats': the lane's
+// ks = fmax(ks, |F(b) - F_t(b)|) over its bins ascending, then the wave maximum (max is exact in any order).
+__device__ __forceinline__ void wave_cohort_stats(const uint32_t* wh, double* F, uint32_t bins, uint64_t cells,
+                                                  uint64_t ksum, uint64_t nplus, const double* target_cdf,
+                                                  const double* target_scalars, const uint32_t* list, uint32_t count,
+                                                  uint32_t lane, ecdna_rep_stats_t* out, uint64_t out_stride) {
+    const double inv = cells ? 1.0 / (double)cells : 0.0;
+    double carry = 0.0, ent = 0.0;
+    for (uint32_t base = 0; base < bins; base += 64u) {
+        const uint32_t b = base + lane;
+        const uint32_t cnt = b < bins ? wh[b] : 0u;
+        const double p = (double)cnt * inv;
+        if (cnt) ent -= p * log(p);
+        const double scan = wave_inclusive_scan(p, lane);
+        if (b < bins) F[b] = carry + scan;
+        carry += __shfl(scan, 63, 64);
+    }
+    ent = wave_sum(ent);
+    double my_ks = 0.0;  // lane j: the KS distance to the j-th target of the list
+    for (uint32_t j = 0; j < count; ++j) {
+        const uint32_t t = list ? list[j] : j;
+        const double* tc = target_cdf + (uint64_t)t * bins;
+        double ks = 0.0;
+        for (uint32_t b = lane; b < bins; b += 64u) ks = fmax(ks, fabs(F[b] - tc[b]));
+        ks = wave_max(ks);
+        if (lane == j) my_ks = ks;
+    }
+    if (lane < count) {
+        const uint32_t t = list ? list[lane] : lane;
+        const double target_mean = target_scalars[3u * t], target_entropy = target_scalars[3u * t + 1u],
+                     target_freq = target_scalars[3u * t + 2u];
+        ecdna_rep_stats_t st;
+        st.cells = cells;
+        st.mean = cells ? (double)ksum * inv : 0.0;
+        st.entropy = ent;
+        st.frequency = cells ? (double)nplus * inv : 0.0;
+        st.ks = cells ? my_ks : 1.0;
+        const double dm = fabs(st.mean - target_mean), de = fabs(st.entropy - target_entropy);
+        st.mean_rel = target_mean > 0.0 ? dm / target_mean : dm;
+        st.entropy_rel = target_entropy > 0.0 ? de / target_entropy : de;
+        st.frequency_diff = fabs(st.frequency - target_freq);
+        out[(uint64_t)t * out_stride] = st;
     }
 }
 

@@ -126,8 +126,31 @@ class Passages(C.Structure):
 ACCEPT_FINAL, ACCEPT_SAMPLE, ACCEPT_SNAPSHOTS, ACCEPT_SNAPSHOT_SAMPLES, ACCEPT_PASSAGES, ACCEPT_PASSAGE_SAMPLES = range(6)
 # (6 and 7 are not sources.) The cohort's records, T = n_targets: timepoint p is target p (ecdna_ssa_cohort_t)
 ACCEPT_COHORT, ACCEPT_COHORT_SAMPLES = 8, 9
+# (10 and 11 are not sources.) The records of the last ecdna_ssa_ctx_rescore, T = its P (ecdna_ssa_keep_t)
+ACCEPT_RESCORED = 12
 ACCEPT_MAX_THRESHOLDS = 32
 COHORT_MAX_TARGETS = 64
+KEPT_GUARD = 0xFFFFFFFF  # both words of the header of a kept sample the guard ended (keep mapping v1)
+
+
+class Keep(C.Structure):
+    """ecdna_ssa_keep_t: the keep block of ecdna_ssa_ctx_create_keep (added within ABI v13)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("keep_cells", C.c_uint32),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class Kept(C.Structure):
+    """ecdna_kept_t: one kept sample's header, its N- and N+ cell counts."""
+
+    _fields_ = [("nminus", C.c_uint32), ("nplus", C.c_uint32)]
+
+
+KEPT_DTYPE = np.dtype([("nminus", "<u4"), ("nplus", "<u4")])
+assert KEPT_DTYPE.itemsize == C.sizeof(Kept) == 8
 
 
 class Cohort(C.Structure):
@@ -346,6 +369,10 @@ class RunSpec:
     # replicate's records against every target. Needs FLAG_REP_STATS; no passages, no snapshot_stats
     cohort_targets: Optional[Sequence[Sequence[int]]] = None
     cohort_sample_cells: Optional[Sequence[int]] = None
+    # every replicate's sample of keep_cells cells kept on the GPU (ecdna_ssa_keep_t, within ABI v13; keep mapping v1),
+    # for Context.rescore, .pool_accepted and .download_kept after the sweep. None = no block. Needs FLAG_REP_STATS;
+    # 1 .. 4096; no passages. n_replicates * keep_cells * 2 bytes of device memory
+    keep_cells: Optional[int] = None
     _keep: list = field(default_factory=list, repr=False)
     _keep_cohort: list = field(default_factory=list, repr=False)
     _keep_ext: list = field(default_factory=list, repr=False)
@@ -532,6 +559,18 @@ class RunSpec:
                 raise ValueError("cohort_sample_cells needs one sample size per target")
             self._keep_cohort.append(cells)
             b.sample_cells = _ptr(cells, C.c_uint32)
+        return b
+
+    def keep(self) -> Optional[Keep]:
+        """The keep block this spec asks for, or None (keep_cells is None): the context is then made without
+        ecdna_ssa_ctx_create_keep."""
+        if self.keep_cells is None:
+            return None
+        if not (0 <= int(self.keep_cells) < (1 << 32)):
+            raise ValueError(f"keep_cells = {self.keep_cells} does not fit the ABI's u32 field")
+        b = Keep()
+        b.struct_size = C.sizeof(Keep)
+        b.keep_cells = int(self.keep_cells)
         return b
 
 

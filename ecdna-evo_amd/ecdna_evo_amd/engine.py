@@ -31,6 +31,7 @@ EXPORTS = [
     "ecdna_ssa_ctx_create_ext",
     "ecdna_ssa_ctx_create_passages",
     "ecdna_ssa_ctx_create_cohort",
+    "ecdna_ssa_ctx_create_keep",
     "ecdna_ssa_ctx_set_outputs",
     "ecdna_ssa_ctx_launch",
     "ecdna_ssa_ctx_sync",
@@ -42,6 +43,10 @@ EXPORTS = [
     "ecdna_ssa_ctx_download_snapshot_stats",
     "ecdna_ssa_ctx_download_passages",
     "ecdna_ssa_ctx_download_cohort",
+    "ecdna_ssa_ctx_rescore",
+    "ecdna_ssa_ctx_download_rescored",
+    "ecdna_ssa_ctx_pool_accepted",
+    "ecdna_ssa_ctx_download_kept",
     "ecdna_ssa_ctx_accept",
     "ecdna_ssa_ctx_download_accept",
     "ecdna_ssa_ctx_select",
@@ -168,6 +173,19 @@ def lib():
         L.ecdna_ssa_ctx_create_cohort.restype = C.c_int
         L.ecdna_ssa_ctx_download_cohort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ecdna_ssa_ctx_download_cohort.restype = C.c_int
+    # (likewise added within v13: the kept samples; Context raises when a spec asks an earlier library for them)
+    if hasattr(L, "ecdna_ssa_ctx_create_keep"):
+        L.ecdna_ssa_ctx_create_keep.argtypes = [P(abi.Params), P(abi.Ext), P(abi.Passages), P(abi.Cohort), P(abi.Keep),
+                                                P(C.c_void_p)]
+        L.ecdna_ssa_ctx_create_keep.restype = C.c_int
+        L.ecdna_ssa_ctx_rescore.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.ecdna_ssa_ctx_rescore.restype = C.c_int
+        L.ecdna_ssa_ctx_download_rescored.argtypes = [C.c_void_p, C.c_void_p]
+        L.ecdna_ssa_ctx_download_rescored.restype = C.c_int
+        L.ecdna_ssa_ctx_pool_accepted.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.ecdna_ssa_ctx_pool_accepted.restype = C.c_int
+        L.ecdna_ssa_ctx_download_kept.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ecdna_ssa_ctx_download_kept.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -346,17 +364,30 @@ class Context:
     """A device-resident run (ecdna_ssa_ctx): create once, launch many times."""
 
     def __init__(self, spec: "abi.RunSpec", ext: Optional["abi.Ext"] = None,
-                 passages: Optional["abi.Passages"] = None, cohort: Optional["abi.Cohort"] = None):
+                 passages: Optional["abi.Passages"] = None, cohort: Optional["abi.Cohort"] = None,
+                 keep: Optional["abi.Keep"] = None):
         """`ext`: an explicit extension block (ecdna_ssa_ctx_create_ext); default: the one `spec` asks for, if any.
         `passages`: likewise the passage block (ecdna_ssa_ctx_create_passages), `cohort`: the cohort block
-        (ecdna_ssa_ctx_create_cohort)."""
+        (ecdna_ssa_ctx_create_cohort), `keep`: the keep block (ecdna_ssa_ctx_create_keep)."""
         self.spec = spec
         self.params = spec.params()
         self.ext = ext if ext is not None else spec.ext()
         self.passages = passages if passages is not None else spec.passages()
         self.cohort = cohort if cohort is not None else spec.cohort()
+        self.keep = keep if keep is not None else spec.keep()
+        self._rescore_targets = 0
         h = C.c_void_p()
-        if self.cohort is not None:  # (only a spec that asks for a cohort goes through _cohort)
+
+        def ref(block):
+            return C.byref(block) if block is not None else None
+
+        if self.keep is not None:  # (only a spec that asks for kept samples goes through _keep)
+            if not hasattr(lib(), "ecdna_ssa_ctx_create_keep"):
+                raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_keep (kept samples)")
+            _check(lib().ecdna_ssa_ctx_create_keep(C.byref(self.params), ref(self.ext), ref(self.passages),
+                                                   ref(self.cohort), C.byref(self.keep), C.byref(h)),
+                   "ecdna_ssa_ctx_create_keep")
+        elif self.cohort is not None:  # (only a spec that asks for a cohort goes through _cohort)
             if not hasattr(lib(), "ecdna_ssa_ctx_create_cohort"):
                 raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_cohort (a cohort of targets)")
             _check(lib().ecdna_ssa_ctx_create_cohort(C.byref(self.params),
@@ -424,7 +455,10 @@ class Context:
         return int(lib().ecdna_ssa_ctx_row_stride(self.h))
 
     def accept_timepoints(self, source: int) -> int:
-        """T of an acceptance source: 1, the spec's snapshots, its passages, or its cohort's targets."""
+        """T of an acceptance source: 1, the spec's snapshots, its passages, its cohort's targets, or the targets of
+        the last rescore."""
+        if source == abi.ACCEPT_RESCORED:
+            return self._rescore_targets
         if source in (abi.ACCEPT_COHORT, abi.ACCEPT_COHORT_SAMPLES):
             return int(self.cohort.n_targets) if self.cohort is not None else 0
         if source in (abi.ACCEPT_SNAPSHOTS, abi.ACCEPT_SNAPSHOT_SAMPLES):
@@ -540,6 +574,74 @@ class Context:
         _check(lib().ecdna_ssa_ctx_download_cohort(self.h, st.ctypes.data, sst.ctypes.data if sst is not None else None),
                "ecdna_ssa_ctx_download_cohort")
         return CohortResult(st, sst)
+
+    def _keep_lib(self):
+        if not hasattr(lib(), "ecdna_ssa_ctx_create_keep"):
+            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_keep (kept samples)")
+        return lib()
+
+    def rescore_enqueue(self, targets):
+        """Enqueue the late scoring of the kept samples against `targets` [P][hist_bins] on the stream of the last
+        launch (ecdna_ssa_ctx_rescore); download_rescored returns the records."""
+        tgt = np.ascontiguousarray(targets, dtype=np.uint64)
+        if tgt.ndim != 2 or tgt.shape[1] != self.params.hist_bins:
+            raise ValueError("targets must be [P][hist_bins]: one histogram of hist_bins entries per target")
+        if not (0 <= tgt.shape[0] < (1 << 32)):
+            raise ValueError(f"{tgt.shape[0]} targets do not fit the ABI's u32 field")
+        self._rescore_targets = 0
+        _check(self._keep_lib().ecdna_ssa_ctx_rescore(self.h, tgt.shape[0], tgt.ctypes.data), "ecdna_ssa_ctx_rescore")
+        self._rescore_targets = tgt.shape[0]
+
+    def download_rescored(self) -> np.ndarray:
+        """The records of the last rescore, [P][n] abi.STATS_DTYPE (ecdna_ssa_ctx_download_rescored; synchronises)."""
+        out = np.zeros((self._rescore_targets, int(self.params.n_replicates)), dtype=abi.STATS_DTYPE)
+        _check(self._keep_lib().ecdna_ssa_ctx_download_rescored(self.h, out.ctypes.data if out.size else None),
+               "ecdna_ssa_ctx_download_rescored")
+        return out
+
+    def rescore(self, targets) -> np.ndarray:
+        """Score every replicate's kept sample (RunSpec.keep_cells) against targets that need not have been known at
+        create: records [P][n] abi.STATS_DTYPE, byte for byte those of a run with stats_target = targets[p] and
+        subsample_cells = keep_cells. They are the acceptance source abi.ACCEPT_RESCORED until the next rescore or
+        launch."""
+        self.rescore_enqueue(targets)
+        return self.download_rescored()
+
+    def pool_accepted(self, threshold: int) -> np.ndarray:
+        """The posterior predictive histogram (ecdna_ssa_ctx_pool_accepted): per global parameter set, the sum of the
+        kept samples' histograms of the replicates the last accept() accepted under row `threshold`,
+        [n_param_sets][hist_bins] u64. Shards' arrays sum to the whole run's."""
+        if not (0 <= int(threshold) < (1 << 32)):
+            raise ValueError(f"threshold = {threshold} does not fit the ABI's u32 field")
+        p = self.params
+        out = np.zeros((p.n_param_sets, p.hist_bins), dtype=np.uint64)
+        _check(self._keep_lib().ecdna_ssa_ctx_pool_accepted(self.h, int(threshold), out.ctypes.data),
+               "ecdna_ssa_ctx_pool_accepted")
+        return out
+
+    def download_kept(self, ids=None, count: Optional[int] = None):
+        """Kept samples of the last launch (ecdna_ssa_ctx_download_kept): (headers [k] abi.KEPT_DTYPE, cells
+        [k][keep_cells] u16) of the replicates with the global `ids`, in their order (an AcceptResult's ids as they
+        come), or of the call's first `count` replicates (default: all). cells[j][:headers[j]["nplus"]] are the N+
+        cells' true copy numbers, ascending; the rest of a row is unspecified."""
+        m = int(self.keep.keep_cells) if self.keep is not None else 0
+        if ids is not None:
+            if count is not None:
+                raise ValueError("give ids or count, not both")
+            idv = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+            k = len(idv)
+        else:
+            idv = None
+            k = int(self.params.n_replicates) if count is None else int(count)
+            if not (0 <= k < (1 << 64)):
+                raise ValueError(f"count = {count} does not fit the ABI's u64 field")
+        headers = np.zeros(k, dtype=abi.KEPT_DTYPE)
+        cells = np.zeros((k, m), dtype=np.uint16)
+        _check(self._keep_lib().ecdna_ssa_ctx_download_kept(self.h, k, idv.ctypes.data if idv is not None and k else None,
+                                                            headers.ctypes.data if k else None,
+                                                            cells.ctypes.data if cells.size else None),
+               "ecdna_ssa_ctx_download_kept")
+        return headers, cells
 
     def download(self, want_rows: bool = False) -> Result:
         p = self.params

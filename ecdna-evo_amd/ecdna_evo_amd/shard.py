@@ -239,3 +239,19 @@ def select(ctx, source: int, ranks=None, fractions=None, timepoints=None, group=
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
         walk.feed(t.cpu().numpy().view(np.uint64))
     return walk.result()
+
+
+def pool_accepted(ctx, threshold: int, group=None, device=None):
+    """Context.pool_accepted over every rank's shard: the whole run's posterior predictive histogram
+    [n_param_sets][hist_bins] u64, the same on every rank. Each rank pools its own accepted replicates' kept samples
+    and one all-reduce (int64, sum) joins the arrays: integer sums, exact in any order. `device` as for select()."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    hist = ctx.pool_accepted(threshold)
+    t = torch.from_numpy(hist.view(np.int64))  # (counts stay far below 2^63)
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.cpu().numpy().view(np.uint64)

@@ -43,7 +43,14 @@
 extern "C" {
 #endif
 
-/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): one sweep scored
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): every replicate's
+ * sample kept on the GPU, scored and pooled after the sweep — the keep block ecdna_ssa_keep_t and
+ * ecdna_ssa_ctx_create_keep, late scoring against targets that were not known at create (ecdna_ssa_ctx_rescore,
+ * ecdna_ssa_ctx_download_rescored and the acceptance source ECDNA_ACCEPT_RESCORED), the posterior predictive histogram
+ * ecdna_ssa_ctx_pool_accepted and the kept cells themselves, ecdna_ssa_ctx_download_kept (below; keep mapping v1).
+ * ecdna_ssa_ctx_create_cohort(p, ext, passages, cohort, out) is ecdna_ssa_ctx_create_keep(p, ext, passages, cohort, NULL,
+ * out): a context without the block allocates and launches nothing new.
+ * Added within v13 (additive: no layout and no existing function changes, the version stays 13): one sweep scored
  * against a cohort of targets on the GPU — several patients, or several biopsies of one tumour, each with its own
  * copy-number histogram and its own number of measured cells: the cohort block ecdna_ssa_cohort_t,
  * ecdna_ssa_ctx_create_cohort and ecdna_ssa_ctx_download_cohort, and the acceptance sources ECDNA_ACCEPT_COHORT and
@@ -474,6 +481,77 @@ int ecdna_ssa_ctx_create_cohort(const ecdna_ssa_params_t* p, const ecdna_ssa_ext
  * before a launch, on a context without the block, and when out_sample_stats is asked for with sample_cells == NULL. */
 int ecdna_ssa_ctx_download_cohort(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out_stats /* [P][n] */,
                                   ecdna_rep_stats_t* out_sample_stats /* [P][n] */);
+
+/* Every replicate's sample kept on the GPU (added within ABI v13). The cohort block scores targets that are known at
+ * create; with the keep block the sample itself stays on the device after the sweep, so that a target that arrives later
+ * (another patient or biopsy, a re-binned or corrected histogram) is scored without a new sweep (ecdna_ssa_ctx_rescore),
+ * the copy-number distribution of the accepted simulations — the posterior predictive check — is pooled where the
+ * samples lie (ecdna_ssa_ctx_pool_accepted), and the accepted simulations' cells can be fetched
+ * (ecdna_ssa_ctx_download_kept). After each chunk's histogram pass, and after its subsample and cohort passes, one more
+ * pass writes the chunk's kept samples into run-sized buffers: [n][keep_cells] u16 plus [n] headers, n × m × 2 bytes.
+ *
+ * Keep mapping v1. With m = keep_cells:
+ *  - Replicate i's kept sample is the sample that subsample mapping v1 (ecdna_ssa_params_t.subsample_cells above) defines
+ *    for m on its end-of-run population, unchanged: stream field 0, counter (i, 0xC0000000 | t, r lo, r hi), the run's
+ *    key, r the GLOBAL id. It is therefore the same sample that subsample_cells = m, and a cohort target with
+ *    sample_cells[p] = m, see.
+ *  - The header ecdna_kept_t holds the sample's N- and N+ cell counts: nminus + nplus = min(m, N).
+ *  - cells[i][0 .. nplus) holds the N+ cells' TRUE copy numbers (not the clipped bins), ascending: the founder format of
+ *    passage mapping v1. Entries past nplus are unspecified.
+ *  - An extinct or never-started replicate keeps the empty sample {0, 0}.
+ *  - A sample the guard ended keeps {0xffffffff, 0xffffffff}: it is rescored as the all-zero record, which is what the
+ *    sampling passes write for it, and adds nothing to a pooled histogram.
+ *  - A kept sample does not depend on chunk, shard, grid or device. Chunked runs are covered.
+ *  - ext, cohort, params.subsample_cells and params.stats_target_hist keep their meaning and stay independent of the
+ *    block, as does every other output.
+ * Rejected at create (ECDNA_E_INVALID, before a device is touched, the message names the field): a wrong struct_size,
+ * keep_cells outside 1 .. 4096, reserved != 0, ECDNA_FLAG_REP_STATS missing, and a non-NULL passages (kept samples of
+ * every phase are a different feature). ECDNA_E_NOMEM at create if the [n][m] u16 cells plus the [n] headers do not fit
+ * (the message says how many bytes were asked for). */
+typedef struct {
+    uint32_t struct_size;   /* sizeof(ecdna_ssa_keep_t); anything else: ECDNA_E_INVALID */
+    uint32_t keep_cells;    /* m, 1 .. 4096 */
+    uint64_t reserved;      /* must be 0 */
+} ecdna_ssa_keep_t;
+typedef struct { uint32_t nminus, nplus; } ecdna_kept_t;   /* one kept sample's header */
+/* ecdna_ssa_ctx_create_cohort with a keep block. keep == NULL: exactly ecdna_ssa_ctx_create_cohort — nothing more is
+ * allocated or launched. The four older create calls forward to this one. */
+int ecdna_ssa_ctx_create_keep(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                              const ecdna_ssa_passages_t* passages, const ecdna_ssa_cohort_t* cohort,
+                              const ecdna_ssa_keep_t* keep, ecdna_ssa_ctx** out);
+/* Late scoring: the kept samples of the last launch against n_targets = P targets given now, binned as
+ * stats_target_hist. Enqueued on the stream of the last launch, asynchronous, like ecdna_ssa_ctx_accept. Record [p][i] is
+ * byte for byte the record ecdna_ssa_ctx_download_sample returns for the same run with stats_target_hist =
+ * target_hists[p] and subsample_cells = keep_cells. A later rescore replaces the records (P may differ between calls) and
+ * drops the keys ecdna_ssa_ctx_select cached, as a relaunch does; a relaunch invalidates the records. The buffer belongs
+ * to the context: allocated at the first call, grown by later ones, freed at destroy.
+ * The records are the acceptance source ECDNA_ACCEPT_RESCORED: T = the P of the last rescore, timepoint p is target p,
+ * the error rule is the one-summary rule of ECDNA_ACCEPT_FINAL, the records lie [P][n] (rep stride 1, timepoint stride n,
+ * error stride 0). ecdna_ssa_ctx_accept, _select and _select_digits take it; before a rescore (and on a context without
+ * the block) they return ECDNA_E_STATE.
+ * ECDNA_E_INVALID: NULL c, n_targets outside 1 .. 64, NULL target_hists, an all-zero target row. ECDNA_E_STATE: before a
+ * launch; a context without the keep block. ECDNA_E_NOMEM leaves the context usable. */
+int ecdna_ssa_ctx_rescore(ecdna_ssa_ctx* c, uint32_t n_targets, const uint64_t* target_hists /* host [P][hist_bins] */);
+/* The records of the last ecdna_ssa_ctx_rescore, [P][n] (ECDNA_E_STATE before one, and after a relaunch until the next).
+ * Synchronises, as the other downloads do. */
+int ecdna_ssa_ctx_download_rescored(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out /* [P][n] */);
+/* The posterior predictive histogram. Synchronous. For row `threshold` of the last ecdna_ssa_ctx_accept, whatever its
+ * source, out_hist[s] is the sum, over the replicates of global parameter set s whose mask bit is set, of their kept
+ * samples' histograms, binned as out_hist of ecdna_ssa_ctx_download: bin 0 holds the N- cells, true copy numbers are
+ * clipped at hist_bins - 1. The sums are integers: shards' arrays sum to the whole run's.
+ * ECDNA_E_STATE: a context without the keep block; no valid accept results (before an accept, after a relaunch).
+ * ECDNA_E_INVALID: NULL c, threshold >= Q of that accept, NULL out_hist. */
+int ecdna_ssa_ctx_pool_accepted(ecdna_ssa_ctx* c, uint32_t threshold,
+                                uint64_t* out_hist /* host [n_param_sets][hist_bins] */);
+/* The kept samples of the replicates with the global ids ids[0 .. n_ids) (ids == NULL: the call's first n_ids
+ * replicates), gathered on the device in the order of ids, then copied once: it takes ecdna_ssa_ctx_download_accept's
+ * out_ids as they come. Either output may be NULL.
+ * ECDNA_E_INVALID: NULL c; an id that is not a replicate of this call ((id - first_replicate) is not a multiple of the
+ * stride, or its index is >= n_replicates); n_ids above n_replicates when ids is NULL. ECDNA_E_STATE: before a launch; a
+ * context without the keep block. */
+int ecdna_ssa_ctx_download_kept(ecdna_ssa_ctx* c, uint64_t n_ids,
+                                const uint64_t* ids /* host, global ids; NULL: the call's first n_ids replicates */,
+                                ecdna_kept_t* out_headers /* [n_ids] */, uint16_t* out_cells /* [n_ids][keep_cells] */);
 /* Use caller-owned DEVICE buffers for the histogram [n_param_sets*hist_bins] u64 and totals
  * [n_param_sets] (e.g. tensors later all-reduced over RCCL). NULL keeps the internal buffer. */
 int ecdna_ssa_ctx_set_outputs(ecdna_ssa_ctx* c, uint64_t* d_hist, ecdna_totals_t* d_totals);
@@ -535,7 +613,9 @@ typedef enum {
     ECDNA_ACCEPT_PASSAGE_SAMPLES = 5,  /* ... out_sample_stats, T = n_passages */
     /* (6 and 7 are not sources: ECDNA_E_INVALID) */
     ECDNA_ACCEPT_COHORT = 8,           /* download_cohort's out_stats, T = n_targets: timepoint p is target p */
-    ECDNA_ACCEPT_COHORT_SAMPLES = 9    /* ... out_sample_stats, T = n_targets (needs sample_cells) */
+    ECDNA_ACCEPT_COHORT_SAMPLES = 9,   /* ... out_sample_stats, T = n_targets (needs sample_cells) */
+    /* (10 and 11 are not sources: ECDNA_E_INVALID) */
+    ECDNA_ACCEPT_RESCORED = 12         /* download_rescored's records, T = the P of the last ecdna_ssa_ctx_rescore */
 } ecdna_accept_source_t;
 /* The cohort sources: the error rule is the one-summary rule of ECDNA_ACCEPT_FINAL; the records lie [P][n] (rep stride 1,
  * timepoint stride n, error stride 0); timepoint_mask = 1 << p gives patient p's acceptance or quantiles, 0 all P
