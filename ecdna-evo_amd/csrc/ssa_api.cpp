@@ -23,6 +23,7 @@
 #include "../../include/ecdna_ssa.h"
 #include "ssa_cohort.hpp"
 #include "ssa_keep.hpp"
+#include "ssa_keep_timepoints.hpp"
 #include "ssa_launch.h"
 #include "ssa_plan.hpp"
 #include "ssa_select.hpp"
@@ -369,6 +370,20 @@ struct ecdna_ssa_ctx {
     bool rescore_pending = false; // a rescore was enqueued since the stream was last drained
     uint32_t rescore_targets = 0; // the P of the last rescore
     hipStream_t rescore_stream = nullptr;
+    // the kept samples of every timepoint (ecdna_ssa_keep_timepoints_t; tk_m = 0: no block): headers [T][n] and cells
+    // [T][n][tk_m], sized by the run; T = tk_T is the run's snapshots or growth phases. The records of
+    // ecdna_ssa_ctx_rescore_timepoints [T][n], their targets and their validity are apart from ecdna_ssa_ctx_rescore's;
+    // the pooled histogram [T][sets][bins] and the gather's staging [T][n_ids] share the keep block's buffers (both
+    // calls are synchronous).
+    uint32_t tk_m = 0;
+    uint32_t tk_T = 0;
+    uint2* d_tk_headers = nullptr;
+    uint16_t* d_tk_cells = nullptr;
+    AcceptBuf tk_stats, tk_cdf, tk_scalars;
+    std::vector<double> tk_cdf_host, tk_scalars_host;
+    bool tk_rescore_valid = false;
+    bool tk_rescore_pending = false;
+    hipStream_t tk_rescore_stream = nullptr;
 };
 
 namespace {
@@ -400,7 +415,7 @@ void free_ctx(ecdna_ssa_ctx* c) {
     for (void* d : c->owned) (void)hipFree(d);
     for (AcceptBuf* b : {&c->acc_mask, &c->acc_counts, &c->acc_blocks, &c->acc_ids, &c->acc_list, &c->sel_keys,
                          &c->sel_hist, &c->rs_stats, &c->rs_cdf, &c->rs_scalars, &c->pool_hist, &c->gat_index,
-                         &c->gat_headers, &c->gat_cells})
+                         &c->gat_headers, &c->gat_cells, &c->tk_stats, &c->tk_cdf, &c->tk_scalars})
         if (b->ptr) (void)hipFree(b->ptr);
     delete c;
 }
@@ -602,6 +617,24 @@ int adopt_keep(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ke
     return ECDNA_OK;
 }
 
+// The timepoint keep block: the kept samples' headers [T][n] and cells [T][n][m], sized by the run.
+int adopt_keep_timepoints(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                          const ecdna_ssa_passages_t* pas, const ecdna_ssa_keep_timepoints_t* kt) {
+    c->tk_m = kt->keep_cells;
+    c->tk_T = ecdna::keep_timepoints::timepoints(*p, ext, pas);
+    const uint64_t n1 = std::max<uint64_t>(p->n_replicates, 1);
+    const uint64_t bytes = ecdna::keep_timepoints::bytes(c->tk_T, n1, c->tk_m);
+    hipError_t e = ctx_alloc(c, &c->d_tk_headers, c->tk_T * n1);
+    if (e == hipSuccess) e = ctx_alloc(c, &c->d_tk_cells, c->tk_T * n1 * c->tk_m);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(e == hipErrorOutOfMemory ? ECDNA_E_NOMEM : ECDNA_E_HIP,
+                    "ecdna_ssa_ctx_create_keep_timepoints: the kept samples (" + std::to_string(bytes) +
+                        " bytes) do not fit: " + hipGetErrorString(e));
+    }
+    return ECDNA_OK;
+}
+
 // Outputs sized by the run (not by the chunk).
 int alloc_outputs(ecdna_ssa_ctx* c) {
     const ecdna_ssa_params_t& p = c->p;
@@ -746,13 +779,15 @@ int alloc_plan(ecdna_ssa_ctx* c, const ecdna::plan::LaunchPlan& pl, const float*
 // Gather, plan, allocate: what the run's shape and the device say, the plan they give (ssa_plan.hpp: every launch
 // decision of create), and the buffers the plan asks for.
 int build_ctx(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
-              const ecdna_ssa_passages_t* pas, const ecdna_ssa_cohort_t* co, const ecdna_ssa_keep_t* keep) {
+              const ecdna_ssa_passages_t* pas, const ecdna_ssa_cohort_t* co, const ecdna_ssa_keep_t* keep,
+              const ecdna_ssa_keep_timepoints_t* kt) {
     const ecdna::plan::Knobs knobs = ecdna::plan::knobs_from_env();
     const ecdna::plan::RunShape shape = adopt_params(c, p, ext, pas, knobs);
     TRY(upload_inputs(c));
     TRY(upload_targets(c, p, ext, pas));
     if (co) TRY(adopt_cohort(c, p, co));
     if (keep) TRY(adopt_keep(c, p, keep));
+    if (kt) TRY(adopt_keep_timepoints(c, p, ext, pas, kt));
     TRY(alloc_outputs(c));
     ecdna::plan::DeviceFacts facts;
     TRY(gather_facts(c, knobs, &facts));
@@ -966,6 +1001,50 @@ int launch_keep_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::Final
     return ECDNA_OK;
 }
 
+// phase g's kept sample of every replicate of the chunk, into slice g of the run's buffers (the KEEP instance under the
+// phase's key: the sample the passage pass measures and, but for the last phase, founds the next phase with)
+int launch_keep_phase_pass(const ecdna_ssa_ctx* c, const Chunk& ch, uint32_t g, const ecdna::FinalState& fs,
+                           ecdna::ChunkIds ids, uint64_t seed_g, hipStream_t st) {
+    const uint64_t n_run = std::max<uint64_t>(c->p.n_replicates, 1);
+    ecdna::PassageArgs pa{};
+    pa.state = fs;
+    pa.founder_rows = c->d_tk_cells + (g * n_run + ch.first) * c->tk_m;
+    pa.founder_counts = c->d_tk_headers + g * n_run + ch.first;
+    pa.founder_stride = c->tk_m;
+    pa.seed = seed_g;
+    pa.m = c->tk_m;
+    pa.table_slots = ecdna::subsample_table_slots(pa.m);
+    pa.sort_slots = ecdna::passage_sort_slots(pa.m);
+    ids.reps_per_block = pass_reps_per_block(
+        c, ch.n, ecdna::keep_waves(ids.bins, fs.bag_k, pa.table_slots, pa.sort_slots, nullptr));
+    pa.ids = ids;
+    TRY(ecdna::launch_keep(pa, pass_blocks(ids), st));
+    return ECDNA_OK;
+}
+
+// the kept samples of the chunk's snapshots, from the rows the stepper just saved, into the run's buffers (ssa_passage's
+// KEEP = 2 instance: one wave per (replicate, snapshot) pair)
+int launch_keep_snapshots_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::StepperArgs& a, ecdna::ChunkIds ids,
+                               hipStream_t st) {
+    ecdna::PassageArgs pa{};
+    pa.state = ecdna::FinalState{a.snap_rows, nullptr, a.snap_stride, nullptr, 0u, 0u};
+    pa.founder_rows = c->d_tk_cells + ch.first * c->tk_m;
+    pa.founder_counts = c->d_tk_headers + ch.first;
+    pa.founder_stride = c->tk_m;
+    pa.seed = c->p.seed;
+    pa.m = c->tk_m;
+    pa.table_slots = ecdna::subsample_table_slots(pa.m);
+    pa.sort_slots = ecdna::passage_sort_slots(pa.m);
+    pa.snap_meta = a.snap_meta;
+    pa.slice_stride = std::max<uint64_t>(c->p.n_replicates, 1);
+    pa.n_snap = c->p.n_snapshots;
+    ids.reps_per_block = pass_reps_per_block(
+        c, ch.n, ecdna::keep_snapshots_waves(ids.bins, pa.table_slots, pa.sort_slots, nullptr));
+    pa.ids = ids;
+    TRY(ecdna::launch_keep_snapshots(pa, pass_blocks(ids), st));
+    return ECDNA_OK;
+}
+
 // the statistics of the chunk's snapshots, from the rows the stepper just saved
 int launch_snapstats_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::StepperArgs& a, ecdna::ChunkIds ids,
                           hipStream_t st) {
@@ -1021,6 +1100,9 @@ int launch_chunk_phase(ecdna_ssa_ctx* c, size_t k, uint32_t g, hipStream_t st) {
     if (c->keep_m) TRY(launch_keep_pass(c, ch, fs, ids, st));
     if (c->n_passages) TRY(launch_passage_pass(c, ch, g, fs, ids, target, a.seed, st));
     if (c->snap_stats) TRY(launch_snapstats_pass(c, ch, a, ids, st));
+    // the timepoint keep block: phase g's sample, or the samples at the chunk's snapshots while their rows exist
+    if (c->tk_m && c->n_passages) TRY(launch_keep_phase_pass(c, ch, g, fs, ids, a.seed, st));
+    if (c->tk_m && c->snap_stats) TRY(launch_keep_snapshots_pass(c, ch, a, ids, st));
     TRY(hipEventRecord(ev[2], st));
     return ECDNA_OK;
 }
@@ -1033,7 +1115,8 @@ int launch_chunk_phase(ecdna_ssa_ctx* c, size_t k, uint32_t g, hipStream_t st) {
 // and 7 are not sources).
 bool is_accept_source(uint32_t source) {
     return source <= (uint32_t)ECDNA_ACCEPT_PASSAGE_SAMPLES || source == (uint32_t)ECDNA_ACCEPT_COHORT ||
-           source == (uint32_t)ECDNA_ACCEPT_COHORT_SAMPLES || source == (uint32_t)ECDNA_ACCEPT_RESCORED;
+           source == (uint32_t)ECDNA_ACCEPT_COHORT_SAMPLES || source == (uint32_t)ECDNA_ACCEPT_RESCORED ||
+           source == (uint32_t)ECDNA_ACCEPT_RESCORED_TIMEPOINTS;
 }
 struct AcceptSource {
     const ecdna_rep_stats_t* stats = nullptr;
@@ -1108,6 +1191,22 @@ int accept_source(const ecdna_ssa_ctx* c, uint32_t source, AcceptSource* out) {
             s.stats = static_cast<const ecdna_rep_stats_t*>(c->rs_stats.ptr);
             s.T = c->rescore_targets;
             s.tp_stride = c->p.n_replicates;  // [P][n], as the cohort's
+            s.has_target = true;
+            break;
+        case ECDNA_ACCEPT_RESCORED_TIMEPOINTS:
+            if (!c->tk_m)
+                return fail(ECDNA_E_STATE, "accept.source RESCORED_TIMEPOINTS: the rescored records need "
+                                           "ecdna_ssa_ctx_create_keep_timepoints");
+            if (!c->launched || !c->tk_rescore_valid)
+                return fail(ECDNA_E_STATE, "accept.source RESCORED_TIMEPOINTS: no records before "
+                                           "ecdna_ssa_ctx_rescore_timepoints (a launch invalidates them)");
+            s.stats = static_cast<const ecdna_rep_stats_t*>(c->tk_stats.ptr);
+            s.T = c->tk_T;
+            s.tp_stride = n_run;  // [T][n]
+            if (c->n_passages) {  // the passage sources' error rule: every participating phase's own summary
+                s.summaries = c->d_pas_summ;
+                s.err_stride = n_run;
+            }
             s.has_target = true;
             break;
         default:
@@ -1254,10 +1353,11 @@ int ecdna_dev_bin_schedule(int pair_ok, uint64_t pair_mode, uint64_t sched, uint
 
 // (development / test entry point, not part of include/ecdna_ssa.h: the sampling passes' LDS plan of ssa_launch.h for
 // the CPU tests. pass 0 = ssa_subsample, 1 = ssa_passage, 2 = ssa_snapstats, where m = 0 means no samples; the passes
-// of the keep block: 3 = the keep pass, 4 = ssa_rescore, 5 = ssa_pool_accepted, the last two whatever m and bag_k)
+// of the keep block: 3 = the keep pass, 4 = ssa_rescore, 5 = ssa_pool_accepted, the last two whatever m and bag_k; of the
+// timepoint keep block: 6 = the snapshot keep pass, whatever bag_k — its populations are rows)
 int ecdna_dev_pass_lds(int pass, uint32_t bins, uint32_t bag_k, uint32_t m, uint32_t* waves, uint64_t* lds_bytes,
                        int* sample_hist_lds) {
-    if (pass < 0 || pass > 5 || (!m && pass != 2 && pass < 4) || !waves || !lds_bytes || !sample_hist_lds)
+    if (pass < 0 || pass > 6 || (!m && pass != 2 && pass != 4 && pass != 5) || !waves || !lds_bytes || !sample_hist_lds)
         return fail(ECDNA_E_INVALID, "ecdna_dev_pass_lds: unknown pass, m = 0 outside pass 2, or a NULL output");
     const uint32_t slots = m ? ecdna::subsample_table_slots(m) : 0u;
     size_t lds = 0;
@@ -1267,6 +1367,7 @@ int ecdna_dev_pass_lds(int pass, uint32_t bins, uint32_t bag_k, uint32_t m, uint
              : pass == 3 ? ecdna::keep_waves(bins, bag_k, slots, ecdna::passage_sort_slots(m), &lds)
              : pass == 4 ? ecdna::rescore_waves(bins, &lds)
              : pass == 5 ? ecdna::pool_accepted_waves(bins, &lds)
+             : pass == 6 ? ecdna::keep_snapshots_waves(bins, slots, ecdna::passage_sort_slots(m), &lds)
                          : ecdna::snapstats_waves(bins, slots, &lds, &in_lds);
     *lds_bytes = lds;
     *sample_hist_lds = in_lds ? 1 : 0;
@@ -1320,6 +1421,13 @@ int ecdna_ssa_ctx_create_cohort(const ecdna_ssa_params_t* p, const ecdna_ssa_ext
 
 int ecdna_ssa_ctx_create_keep(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, const ecdna_ssa_passages_t* pas,
                               const ecdna_ssa_cohort_t* co, const ecdna_ssa_keep_t* keep, ecdna_ssa_ctx** out) {
+    return ecdna_ssa_ctx_create_keep_timepoints(p, ext, pas, co, keep, nullptr, out);
+}
+
+int ecdna_ssa_ctx_create_keep_timepoints(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                                         const ecdna_ssa_passages_t* pas, const ecdna_ssa_cohort_t* co,
+                                         const ecdna_ssa_keep_t* keep, const ecdna_ssa_keep_timepoints_t* kt,
+                                         ecdna_ssa_ctx** out) {
     if (!out) return fail(ECDNA_E_INVALID, "out is NULL");
     *out = nullptr;
     TRY(validate(p, ext, pas));
@@ -1331,9 +1439,13 @@ int ecdna_ssa_ctx_create_keep(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t
         const std::string why = ecdna::keep::invalid(*p, pas, *keep);
         if (!why.empty()) return fail(ECDNA_E_INVALID, why);
     }
+    if (kt) {  // the timepoint keep block
+        const std::string why = ecdna::keep_timepoints::invalid(*p, ext, pas, *kt);
+        if (!why.empty()) return fail(ECDNA_E_INVALID, why);
+    }
     TRY(pick_device(p->device));
     ecdna_ssa_ctx* c = new ecdna_ssa_ctx();
-    if (int rc = build_ctx(c, p, ext, pas, co, keep)) {
+    if (int rc = build_ctx(c, p, ext, pas, co, keep, kt)) {
         free_ctx(c);
         return rc;
     }
@@ -1392,6 +1504,7 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
     c->accept_valid = false;  // (the acceptance pass's results were the previous launch's)
     c->sel_keys_valid = false;  // (and the select passes' keys were made from its records)
     c->rescore_valid = false;   // (and the rescored records from its kept samples)
+    c->tk_rescore_valid = false;
     return ECDNA_OK;
 }
 
@@ -1872,6 +1985,169 @@ int ecdna_ssa_ctx_download_kept(ecdna_ssa_ctx* c, uint64_t n_ids, const uint64_t
     }
     if (out_headers) TRY(hipMemcpy(out_headers, d_headers, n_ids * sizeof(uint2), hipMemcpyDeviceToHost));
     if (out_cells) TRY(to_host(out_cells, d_cells, n_ids * m));
+    return ECDNA_OK;
+}
+
+// ---- the calls over the kept samples of every timepoint (ecdna_ssa_keep_timepoints_t): slice t of the buffers is a run
+// of kept samples as the keep block's, so each call is the keep block's pass once per timepoint, on offset pointers ----
+
+namespace {
+const char* const kNeedsTimepoints = ": the kept timepoint samples need ecdna_ssa_ctx_create_keep_timepoints";
+}
+
+int ecdna_ssa_ctx_rescore_timepoints(ecdna_ssa_ctx* c, const uint64_t* target_hists) {
+    const char* who = "ecdna_ssa_ctx_rescore_timepoints";
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!target_hists) return fail(ECDNA_E_INVALID, "rescore_timepoints.target_hists is NULL");
+    if (!c->tk_m) return fail(ECDNA_E_STATE, std::string("rescore_timepoints") + kNeedsTimepoints);
+    const ecdna_ssa_params_t& p = c->p;
+    const uint32_t bins = p.hist_bins, T = c->tk_T;
+    const uint32_t empty = first_empty_target(target_hists, T, bins);
+    if (empty < T)
+        return fail(ECDNA_E_INVALID, "rescore_timepoints.target_hists[" + std::to_string(empty) + "] is empty");
+    TRY(ctx_launched(c, "rescore_timepoints before launch"));
+    const uint64_t n = p.n_replicates;
+    TRY(hipSetDevice(c->device));
+    hipStream_t st = c->last_stream;
+    // an earlier call may still read the targets this one replaces (and its upload their host copies)
+    if (c->tk_rescore_pending) TRY(hipStreamSynchronize(c->tk_rescore_stream));
+    c->tk_rescore_pending = false;
+    c->tk_rescore_valid = false;
+    c->sel_keys_valid = false;  // (the select passes' keys may have been made from the records this call replaces)
+    TRY(accept_reserve(&c->tk_stats, std::max<uint64_t>(n, 1) * T * sizeof(ecdna_rep_stats_t), "records", who));
+    TRY(accept_reserve(&c->tk_cdf, (uint64_t)T * bins * sizeof(double), "target CDFs", who));
+    TRY(accept_reserve(&c->tk_scalars, (uint64_t)T * 3u * sizeof(double), "target scalars", who));
+    if (n) {
+        c->tk_cdf_host.resize((uint64_t)T * bins);
+        c->tk_scalars_host.resize((uint64_t)T * 3u);
+        summarize_targets(target_hists, T, bins, c->tk_cdf_host.data(), c->tk_scalars_host.data());
+        TRY(hipMemcpyAsync(c->tk_cdf.ptr, c->tk_cdf_host.data(), c->tk_cdf_host.size() * sizeof(double),
+                           hipMemcpyHostToDevice, st));
+        TRY(hipMemcpyAsync(c->tk_scalars.ptr, c->tk_scalars_host.data(), c->tk_scalars_host.size() * sizeof(double),
+                           hipMemcpyHostToDevice, st));
+        c->tk_rescore_pending = true;
+        c->tk_rescore_stream = st;
+        for (uint64_t t = 0; t < T; ++t) {  // timepoint t's samples against target t: ssa_rescore with one target
+            ecdna::RescoreArgs a{};
+            a.headers = c->d_tk_headers + t * n;
+            a.cells = c->d_tk_cells + t * n * c->tk_m;
+            a.out = static_cast<ecdna_rep_stats_t*>(c->tk_stats.ptr) + t * n;
+            a.target_cdf = static_cast<const double*>(c->tk_cdf.ptr) + t * bins;
+            a.target_scalars = static_cast<const double*>(c->tk_scalars.ptr) + t * 3u;
+            a.n = (uint32_t)n;
+            a.m = c->tk_m;
+            a.bins = bins;
+            a.n_targets = 1u;
+            a.reps_per_block = pass_reps_per_block(c, (uint32_t)n, ecdna::rescore_waves(bins, nullptr));
+            TRY(ecdna::launch_rescore(a, st));
+        }
+    }
+    c->tk_rescore_valid = true;
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_download_rescored_timepoints(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!c->tk_m) return fail(ECDNA_E_STATE, std::string("download_rescored_timepoints") + kNeedsTimepoints);
+    if (!c->launched || !c->tk_rescore_valid)
+        return fail(ECDNA_E_STATE, "download_rescored_timepoints before rescore_timepoints (a launch invalidates the "
+                                   "rescored records; ecdna_ssa_ctx_create_keep_timepoints)");
+    TRY(ctx_drain(c));
+    const uint64_t records = (uint64_t)c->tk_T * c->p.n_replicates;
+    if (out && records) TRY(to_host(out, static_cast<const ecdna_rep_stats_t*>(c->tk_stats.ptr), records));
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_pool_accepted_timepoints(ecdna_ssa_ctx* c, uint32_t threshold, uint64_t* out_hist) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!out_hist) return fail(ECDNA_E_INVALID, "pool_accepted_timepoints.out_hist is NULL");
+    if (!c->tk_m) return fail(ECDNA_E_STATE, std::string("pool_accepted_timepoints") + kNeedsTimepoints);
+    if (!c->launched || !c->accept_valid)
+        return fail(ECDNA_E_STATE, "pool_accepted_timepoints before accept (a launch invalidates the acceptance results; "
+                                   "ecdna_ssa_ctx_create_keep_timepoints)");
+    if (threshold >= c->acc_rows)
+        return fail(ECDNA_E_INVALID, "pool_accepted_timepoints.threshold must be < n_thresholds of the last accept");
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t n = p.n_replicates, nb = (uint64_t)p.n_param_sets * p.hist_bins, T = c->tk_T;
+    std::fill(out_hist, out_hist + T * nb, 0ull);
+    if (!n) return ECDNA_OK;
+    TRY(hipSetDevice(c->device));
+    hipStream_t st = c->last_stream;
+    TRY(accept_reserve(&c->pool_hist, T * nb * sizeof(uint64_t), "histogram", "ecdna_ssa_ctx_pool_accepted_timepoints"));
+    TRY(hipMemsetAsync(c->pool_hist.ptr, 0, T * nb * sizeof(uint64_t), st));
+    for (uint64_t t = 0; t < T; ++t) {
+        ecdna::PoolAcceptedArgs a{};
+        a.headers = c->d_tk_headers + t * n;
+        a.cells = c->d_tk_cells + t * n * c->tk_m;
+        a.mask = static_cast<const uint32_t*>(c->acc_mask.ptr);
+        a.hist = static_cast<unsigned long long*>(c->pool_hist.ptr) + t * nb;
+        a.rid0 = p.first_replicate;
+        a.rid_stride = p.replicate_stride ? p.replicate_stride : 1u;
+        a.reps_per_set = p.reps_per_set;
+        a.n = (uint32_t)n;
+        a.m = c->tk_m;
+        a.bins = p.hist_bins;
+        a.q = threshold;
+        // (ecdna_ssa_ctx_pool_accepted's share)
+        const uint64_t set_local = std::max<uint64_t>(1, p.reps_per_set / a.rid_stride);
+        a.reps_per_block = pass_reps_per_block(
+            c, (uint32_t)n, (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(ecdna::kPoolBlock, set_local)));
+        TRY(ecdna::launch_pool_accepted(a, st));
+    }
+    TRY(hipStreamSynchronize(st));
+    TRY(to_host(out_hist, static_cast<const uint64_t*>(c->pool_hist.ptr), T * nb));
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_download_kept_timepoints(ecdna_ssa_ctx* c, uint64_t n_ids, const uint64_t* ids,
+                                           ecdna_kept_t* out_headers, uint16_t* out_cells) {
+    const char* who = "ecdna_ssa_ctx_download_kept_timepoints";
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t n = p.n_replicates, stride = p.replicate_stride ? p.replicate_stride : 1u;
+    if (!ids && n_ids > n)
+        return fail(ECDNA_E_INVALID, "download_kept_timepoints.n_ids must be <= n_replicates when ids is NULL");
+    std::vector<uint32_t> index(ids ? n_ids : 0);
+    for (uint64_t j = 0; ids && j < n_ids; ++j) {
+        uint64_t i = 0;
+        if (!ecdna::keep::index_of(ids[j], p.first_replicate, stride, n, &i))
+            return fail(ECDNA_E_INVALID, "download_kept_timepoints.ids[" + std::to_string(j) + "] = " +
+                                             std::to_string(ids[j]) + " is not a replicate of this call");
+        index[j] = (uint32_t)i;
+    }
+    if (!c->tk_m) return fail(ECDNA_E_STATE, std::string("download_kept_timepoints") + kNeedsTimepoints);
+    TRY(ctx_launched(c, "download_kept_timepoints before launch (ecdna_ssa_ctx_create_keep_timepoints)"));
+    if (!n_ids || (!out_headers && !out_cells)) return ECDNA_OK;
+    TRY(ctx_drain(c));
+    const uint64_t m = c->tk_m, T = c->tk_T;
+    if (ids) {  // gathered on the device in the order of ids, timepoint by timepoint, then copied once
+        TRY(accept_reserve(&c->gat_index, n_ids * sizeof(uint32_t), "index", who));
+        TRY(accept_reserve(&c->gat_headers, T * n_ids * sizeof(uint2), "headers", who));
+        TRY(accept_reserve(&c->gat_cells, T * n_ids * m * sizeof(uint16_t), "cells", who));
+        hipStream_t st = c->last_stream;
+        TRY(hipMemcpy(c->gat_index.ptr, index.data(), n_ids * sizeof(uint32_t), hipMemcpyHostToDevice));
+        for (uint64_t t = 0; t < T; ++t) {
+            ecdna::KeptGatherArgs a{};
+            a.headers = c->d_tk_headers + t * n;
+            a.cells = c->d_tk_cells + t * n * m;
+            a.index = static_cast<const uint32_t*>(c->gat_index.ptr);
+            a.out_headers = static_cast<uint2*>(c->gat_headers.ptr) + t * n_ids;
+            a.out_cells = static_cast<uint16_t*>(c->gat_cells.ptr) + t * n_ids * m;
+            a.n_ids = (uint32_t)n_ids;
+            a.m = (uint32_t)m;
+            TRY(ecdna::launch_kept_gather(a, st));
+        }
+        TRY(hipStreamSynchronize(st));
+        if (out_headers)
+            TRY(hipMemcpy(out_headers, c->gat_headers.ptr, T * n_ids * sizeof(uint2), hipMemcpyDeviceToHost));
+        if (out_cells) TRY(to_host(out_cells, static_cast<const uint16_t*>(c->gat_cells.ptr), T * n_ids * m));
+        return ECDNA_OK;
+    }
+    for (uint64_t t = 0; t < T; ++t) {  // the first n_ids samples of every slice
+        if (out_headers)
+            TRY(hipMemcpy(out_headers + t * n_ids, c->d_tk_headers + t * n, n_ids * sizeof(uint2), hipMemcpyDeviceToHost));
+        if (out_cells) TRY(to_host(out_cells + t * n_ids * m, c->d_tk_cells + t * n * m, n_ids * m));
+    }
     return ECDNA_OK;
 }
 

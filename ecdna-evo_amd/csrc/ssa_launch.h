@@ -188,6 +188,13 @@ struct PassageArgs {
     uint32_t m;                           // sample size (cells), 1 .. kMaxSubsampleCells
     uint32_t table_slots;                 // per-wave table of drawn positions: subsample_table_slots(m)
     uint32_t sort_slots;                  // per-wave founder array (u16): passage_sort_slots(m)
+    // the snapshot keep pass only (launch_keep_snapshots; ecdna_ssa_keep_timepoints_t): one population per (replicate,
+    // snapshot) pair of the chunk. state.rows / .row_stride are the chunk's snapshot rows [n][n_snap][row_stride] (no
+    // summaries, no counters); founder_rows / founder_counts are slice 0 of the run's kept cells [T][n_run][m] and
+    // headers [T][n_run] at the chunk's offset, and snapshot s goes to slice s, slice_stride samples further on.
+    const ecdna_snapshot_t* snap_meta;    // [n][n_snap], chunk-offset
+    uint64_t slice_stride;                // samples per timepoint slice: the run's replicates
+    uint32_t n_snap;
 };
 
 // The cohort pass over one chunk (ssa_cohort.hip; ecdna_ssa_cohort_t, cohort mapping v1): per replicate, the statistics
@@ -421,7 +428,14 @@ inline uint32_t pool_accepted_waves(uint32_t bins, size_t* lds_bytes) {
     if (lds_bytes) *lds_bytes = (size_t)bins * 8u;
     return (uint32_t)kPoolBlock / 64u;
 }
+// the snapshot keep pass (ssa_passage's KEEP = 2 instance): the keep pass's plan over a population that is a row only
+// (bag_k = 0) — per wave histogram, table (u32) and the kept cells (u16) while they are sorted: 8 + 32 + 8 KiB at 2,048
+// bins and m = 4096, one wave per workgroup
+inline uint32_t keep_snapshots_waves(uint32_t bins, uint32_t table_slots, uint32_t sort_slots, size_t* lds_bytes) {
+    return passage_waves(bins, 0u, table_slots, sort_slots, lds_bytes);
+}
 hipError_t launch_keep(const PassageArgs& a, uint32_t blocks, hipStream_t stream);
+hipError_t launch_keep_snapshots(const PassageArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_rescore(const RescoreArgs& a, hipStream_t stream);
 hipError_t launch_pool_accepted(const PoolAcceptedArgs& a, hipStream_t stream);
 hipError_t launch_kept_gather(const KeptGatherArgs& a, hipStream_t stream);

@@ -24,6 +24,12 @@
 // {n-, n+} header — into the run's kept buffers, and nothing else: no statistics, no pooled histogram (the sample's
 // records are made later, from the kept cells, by ssa_rescore). A sample the guard ended keeps the header
 // {0xffffffff, 0xffffffff} instead of the empty population.
+//
+// The timepoint keep block (ecdna_ssa_keep_timepoints_t, timepoint keep mapping v1) keeps the sample of every timepoint
+// of a longitudinal run with the same body. A passage context launches the KEEP instance above once per phase, under
+// the phase's key, into slice g of the run's buffers. A snapshot context launches the KEEP = 2 instance after
+// ssa_snapstats, while the chunk's snapshot rows exist: one wave per (replicate, snapshot) pair, the population a row
+// only, the draws on snapshot s's stream, slice s of the buffers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -63,9 +69,12 @@ __device__ __forceinline__ void wave_bitonic_sort_u16(uint16_t* fs, uint32_t P, 
 
 // BAG as in ssa_hist: 0 = rows only; 1 / 2 = u16 / u32 bin counters bags[q][bag_k] for copy numbers 1..bag_k plus
 // the large-k cells at the head of the row.
-// KEEP: the keep pass (founder_rows / founder_counts are the kept cells and headers; stats, sample_hist and target are
-// not read).
-template <int BAG, bool KEEP>
+// KEEP: 1 = the keep pass (founder_rows / founder_counts are the kept cells and headers; stats, sample_hist and target
+// are not read). 2 = the snapshot keep pass (ecdna_ssa_keep_timepoints_t, timepoint keep mapping v1; BAG = 0): the same
+// body over the chunk's (replicate, snapshot) pairs, one wave per pair. Pair w = q * n_snap + s is the population
+// "nminus N- cells, then snapshot row w" of ssa_snapstats, sampled on the stream of snapshot s as ssa_snapstats samples
+// it, and kept in slice s of the run's buffers. A snapshot that was not taken is the empty population.
+template <int BAG, int KEEP>
 __global__ void __launch_bounds__(kPasBlock) ssa_passage(const PassageArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const ChunkIds& ids = a.ids;
@@ -84,10 +93,24 @@ __global__ void __launch_bounds__(kPasBlock) ssa_passage(const PassageArgs a) {
     const bool want = a.founder_rows != nullptr;
     const uint32_t fcap = min(a.m, a.sort_slots);  // a founder row is never written past m
 
-    for (uint32_t q = r_begin + wave; q < r_end; q += nw) {
-        const ecdna_rep_summary_t* s = a.state.summaries + q;
-        const uint64_t nm = s->nminus;
-        const uint32_t np = (uint32_t)s->nplus;
+    // populations per replicate: its snapshots in the snapshot keep pass, else its final state. (w below n * n_snap
+    // fits u32: the chunk holds a row of at least 128 bytes per pair; launch_keep_snapshots checks it.)
+    const uint32_t S = KEEP == 2 ? a.n_snap : 1u;
+    for (uint32_t w = r_begin * S + wave; w < r_end * S; w += nw) {
+        const uint32_t q = KEEP == 2 ? w / S : w;       // the replicate
+        const uint32_t t = KEEP == 2 ? w - q * S : 0u;  // its snapshot
+        uint64_t nm;
+        uint32_t np;
+        if (KEEP == 2) {  // as ssa_snapstats reads a pair: the row is never read past its memory
+            const ecdna_snapshot_t* meta = a.snap_meta + w;
+            const bool taken = meta->taken != 0u;
+            nm = taken ? meta->nminus : 0ull;
+            np = taken ? (uint32_t)min(meta->nplus, a.state.row_stride) : 0u;
+        } else {
+            const ecdna_rep_summary_t* s = a.state.summaries + q;
+            nm = s->nminus;
+            np = (uint32_t)s->nplus;
+        }
         const uint64_t rid = ids.rid0 + (uint64_t)q * ids.rid_stride;
         const uint64_t set = rid / ids.reps_per_set;
         SamplePlan plan = sample_plan(a.m, nm + (uint64_t)np);
@@ -96,7 +119,8 @@ __global__ void __launch_bounds__(kPasBlock) ssa_passage(const PassageArgs a) {
 
         // 1. counters: prefix sums for the position -> k lookup, and (whole / complement) the full histogram
         uint64_t ksum = 0;  // sum of k over the full population (need_full)
-        const SamplePop pop = wave_load_final_state<BAG>(a.state, q, nm, np, ids.bins, plan, wh, pre, ksum, lane);
+        // (row w of a.state: the replicate's row, or the pair's snapshot row — a row-only population, bag_k = 0)
+        const SamplePop pop = wave_load_final_state<BAG>(a.state, w, nm, np, ids.bins, plan, wh, pre, ksum, lane);
 
         // 2.-4. draws until m' distinct positions have appeared; every new one is looked up and counted (and, when the
         // picks are the sample, gathered as a founder)
@@ -105,7 +129,8 @@ __global__ void __launch_bounds__(kPasBlock) ssa_passage(const PassageArgs a) {
         bool bad = plan.bad;
         if (!plan.whole && !bad)
             bad = wave_sample_picks<BAG>(wh, tab, a.table_slots, pop, plan.N, plan.mp, plan.comp, last,
-                                         sample_stream_tag(0u), rid, k0, k1, lane, psum, want ? fs : nullptr, fcap, &gn);
+                                         sample_stream_tag(KEEP == 2 ? t + 1u : 0u), rid, k0, k1, lane, psum,
+                                         want ? fs : nullptr, fcap, &gn);
         wave_sync_lds();
 
         // founders of a whole population or of a complement: one walk over the positions (N <= 2m), from the 64-block
@@ -143,10 +168,12 @@ __global__ void __launch_bounds__(kPasBlock) ssa_passage(const PassageArgs a) {
                 while (P < gn) P <<= 1;
                 wave_bitonic_sort_u16(fs, P, lane);
             }
-            uint16_t* out = a.founder_rows + (uint64_t)q * a.founder_stride;
+            // (the snapshot keep pass: slice t of the run's buffers)
+            const uint64_t at = KEEP == 2 ? (uint64_t)t * a.slice_stride + q : (uint64_t)q;
+            uint16_t* out = a.founder_rows + at * a.founder_stride;
             for (uint32_t j = lane; j < gn; j += 64u) out[j] = fs[j];
             if (lane == 0)
-                a.founder_counts[q] =
+                a.founder_counts[at] =
                     KEEP && fbad ? make_uint2(kKeptGuard, kKeptGuard) : make_uint2(fbad ? 0u : nminus_s, gn);
         }
         wave_sync_lds();  // wh and fs are reset for the wave's next replicate
@@ -162,8 +189,8 @@ hipError_t launch_passage(const PassageArgs& a, uint32_t blocks, hipStream_t str
     const uint32_t nw = passage_waves(a.ids.bins, a.state.bag_k, a.table_slots, a.sort_slots, &lds);
     if (lds > kPassLdsMax || a.m > a.founder_stride || a.sort_slots < 64u || (a.sort_slots & (a.sort_slots - 1u)))
         return hipErrorInvalidValue;
-    static const void* const table[3] = {(const void*)ssa_passage<0, false>, (const void*)ssa_passage<1, false>,
-                                         (const void*)ssa_passage<2, false>};
+    static const void* const table[3] = {(const void*)ssa_passage<0, 0>, (const void*)ssa_passage<1, 0>,
+                                         (const void*)ssa_passage<2, 0>};
     return hipLaunchKernel(table[bag_index(a.state)], dim3(blocks), dim3(nw * 64u), args, lds, stream);
 }
 
@@ -176,9 +203,24 @@ hipError_t launch_keep(const PassageArgs& a, uint32_t blocks, hipStream_t stream
     if (lds > kPassLdsMax || !a.founder_rows || !a.founder_counts || a.m > a.founder_stride || a.sort_slots < 64u ||
         (a.sort_slots & (a.sort_slots - 1u)))
         return hipErrorInvalidValue;
-    static const void* const table[3] = {(const void*)ssa_passage<0, true>, (const void*)ssa_passage<1, true>,
-                                         (const void*)ssa_passage<2, true>};
+    static const void* const table[3] = {(const void*)ssa_passage<0, 1>, (const void*)ssa_passage<1, 1>,
+                                         (const void*)ssa_passage<2, 1>};
     return hipLaunchKernel(table[bag_index(a.state)], dim3(blocks), dim3(nw * 64u), args, lds, stream);
+}
+
+hipError_t launch_keep_snapshots(const PassageArgs& a, uint32_t blocks, hipStream_t stream) {
+    PassageArgs copy = a;
+    void* args[] = {&copy};
+    size_t lds = 0;
+    const uint32_t nw = keep_snapshots_waves(a.ids.bins, a.table_slots, a.sort_slots, &lds);
+    // (a row-only population: no counters and no summaries; the pair index and its step stay below 2^32; a slice holds
+    // the chunk's replicates)
+    if (lds > kPassLdsMax || !a.founder_rows || !a.founder_counts || a.m > a.founder_stride || a.sort_slots < 64u ||
+        (a.sort_slots & (a.sort_slots - 1u)) || a.state.bags || a.state.bag_k || !a.state.rows || !a.snap_meta ||
+        a.n_snap < 1u || a.n_snap > kMaxSnapshots || (uint64_t)a.ids.n * a.n_snap + 4u > 0xffffffffull ||
+        a.slice_stride < a.ids.n)
+        return hipErrorInvalidValue;
+    return hipLaunchKernel((const void*)ssa_passage<0, 2>, dim3(blocks), dim3(nw * 64u), args, lds, stream);
 }
 
 }  // namespace ecdna

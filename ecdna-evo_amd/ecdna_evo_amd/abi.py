@@ -128,6 +128,9 @@ ACCEPT_FINAL, ACCEPT_SAMPLE, ACCEPT_SNAPSHOTS, ACCEPT_SNAPSHOT_SAMPLES, ACCEPT_P
 ACCEPT_COHORT, ACCEPT_COHORT_SAMPLES = 8, 9
 # (10 and 11 are not sources.) The records of the last ecdna_ssa_ctx_rescore, T = its P (ecdna_ssa_keep_t)
 ACCEPT_RESCORED = 12
+# The records of the last ecdna_ssa_ctx_rescore_timepoints, T = the context's snapshots or growth phases
+# (ecdna_ssa_keep_timepoints_t)
+ACCEPT_RESCORED_TIMEPOINTS = 13
 ACCEPT_MAX_THRESHOLDS = 32
 COHORT_MAX_TARGETS = 64
 KEPT_GUARD = 0xFFFFFFFF  # both words of the header of a kept sample the guard ended (keep mapping v1)
@@ -135,6 +138,17 @@ KEPT_GUARD = 0xFFFFFFFF  # both words of the header of a kept sample the guard e
 
 class Keep(C.Structure):
     """ecdna_ssa_keep_t: the keep block of ecdna_ssa_ctx_create_keep (added within ABI v13)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("keep_cells", C.c_uint32),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class KeepTimepoints(C.Structure):
+    """ecdna_ssa_keep_timepoints_t: the timepoint keep block of ecdna_ssa_ctx_create_keep_timepoints (added within ABI
+    v13)."""
 
     _fields_ = [
         ("struct_size", C.c_uint32),
@@ -373,6 +387,12 @@ class RunSpec:
     # for Context.rescore, .pool_accepted and .download_kept after the sweep. None = no block. Needs FLAG_REP_STATS;
     # 1 .. 4096; no passages. n_replicates * keep_cells * 2 bytes of device memory
     keep_cells: Optional[int] = None
+    # the sample of keep_timepoint_cells cells of every timepoint kept on the GPU (ecdna_ssa_keep_timepoints_t, within
+    # ABI v13; timepoint keep mapping v1): every snapshot of a run with snapshot_stats, or every growth phase of a
+    # passage run (then it must equal passage_cells), for Context.rescore_timepoints, .pool_accepted_timepoints and
+    # .download_kept_timepoints after the sweep. None = no block. Needs FLAG_REP_STATS; 1 .. 4096.
+    # T * n_replicates * (2 * keep_timepoint_cells + 8) bytes of device memory
+    keep_timepoint_cells: Optional[int] = None
     _keep: list = field(default_factory=list, repr=False)
     _keep_cohort: list = field(default_factory=list, repr=False)
     _keep_ext: list = field(default_factory=list, repr=False)
@@ -571,6 +591,25 @@ class RunSpec:
         b = Keep()
         b.struct_size = C.sizeof(Keep)
         b.keep_cells = int(self.keep_cells)
+        return b
+
+    def timepoints(self) -> int:
+        """T of the timepoint keep block: the growth phases of a passage run, else the snapshots of a run with
+        snapshot_stats, else 0."""
+        if self.n_passages:
+            return int(self.n_passages)
+        return len(self.snapshots or ()) if self.snapshot_stats else 0
+
+    def keep_timepoints(self) -> Optional[KeepTimepoints]:
+        """The timepoint keep block this spec asks for, or None (keep_timepoint_cells is None): the context is then
+        made without ecdna_ssa_ctx_create_keep_timepoints."""
+        if self.keep_timepoint_cells is None:
+            return None
+        if not (0 <= int(self.keep_timepoint_cells) < (1 << 32)):
+            raise ValueError(f"keep_timepoint_cells = {self.keep_timepoint_cells} does not fit the ABI's u32 field")
+        b = KeepTimepoints()
+        b.struct_size = C.sizeof(KeepTimepoints)
+        b.keep_cells = int(self.keep_timepoint_cells)
         return b
 
 

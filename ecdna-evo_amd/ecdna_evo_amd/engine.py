@@ -32,6 +32,7 @@ EXPORTS = [
     "ecdna_ssa_ctx_create_passages",
     "ecdna_ssa_ctx_create_cohort",
     "ecdna_ssa_ctx_create_keep",
+    "ecdna_ssa_ctx_create_keep_timepoints",
     "ecdna_ssa_ctx_set_outputs",
     "ecdna_ssa_ctx_launch",
     "ecdna_ssa_ctx_sync",
@@ -47,6 +48,10 @@ EXPORTS = [
     "ecdna_ssa_ctx_download_rescored",
     "ecdna_ssa_ctx_pool_accepted",
     "ecdna_ssa_ctx_download_kept",
+    "ecdna_ssa_ctx_rescore_timepoints",
+    "ecdna_ssa_ctx_download_rescored_timepoints",
+    "ecdna_ssa_ctx_pool_accepted_timepoints",
+    "ecdna_ssa_ctx_download_kept_timepoints",
     "ecdna_ssa_ctx_accept",
     "ecdna_ssa_ctx_download_accept",
     "ecdna_ssa_ctx_select",
@@ -186,6 +191,19 @@ def lib():
         L.ecdna_ssa_ctx_pool_accepted.restype = C.c_int
         L.ecdna_ssa_ctx_download_kept.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ecdna_ssa_ctx_download_kept.restype = C.c_int
+    # (likewise added within v13: the kept samples of every timepoint)
+    if hasattr(L, "ecdna_ssa_ctx_create_keep_timepoints"):
+        L.ecdna_ssa_ctx_create_keep_timepoints.argtypes = [P(abi.Params), P(abi.Ext), P(abi.Passages), P(abi.Cohort),
+                                                           P(abi.Keep), P(abi.KeepTimepoints), P(C.c_void_p)]
+        L.ecdna_ssa_ctx_create_keep_timepoints.restype = C.c_int
+        L.ecdna_ssa_ctx_rescore_timepoints.argtypes = [C.c_void_p, C.c_void_p]
+        L.ecdna_ssa_ctx_rescore_timepoints.restype = C.c_int
+        L.ecdna_ssa_ctx_download_rescored_timepoints.argtypes = [C.c_void_p, C.c_void_p]
+        L.ecdna_ssa_ctx_download_rescored_timepoints.restype = C.c_int
+        L.ecdna_ssa_ctx_pool_accepted_timepoints.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.ecdna_ssa_ctx_pool_accepted_timepoints.restype = C.c_int
+        L.ecdna_ssa_ctx_download_kept_timepoints.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ecdna_ssa_ctx_download_kept_timepoints.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -365,23 +383,29 @@ class Context:
 
     def __init__(self, spec: "abi.RunSpec", ext: Optional["abi.Ext"] = None,
                  passages: Optional["abi.Passages"] = None, cohort: Optional["abi.Cohort"] = None,
-                 keep: Optional["abi.Keep"] = None):
+                 keep: Optional["abi.Keep"] = None, keep_timepoints: Optional["abi.KeepTimepoints"] = None):
         """`ext`: an explicit extension block (ecdna_ssa_ctx_create_ext); default: the one `spec` asks for, if any.
         `passages`: likewise the passage block (ecdna_ssa_ctx_create_passages), `cohort`: the cohort block
-        (ecdna_ssa_ctx_create_cohort), `keep`: the keep block (ecdna_ssa_ctx_create_keep)."""
+        (ecdna_ssa_ctx_create_cohort), `keep`: the keep block (ecdna_ssa_ctx_create_keep), `keep_timepoints`: the
+        timepoint keep block (ecdna_ssa_ctx_create_keep_timepoints)."""
         self.spec = spec
         self.params = spec.params()
         self.ext = ext if ext is not None else spec.ext()
         self.passages = passages if passages is not None else spec.passages()
         self.cohort = cohort if cohort is not None else spec.cohort()
         self.keep = keep if keep is not None else spec.keep()
+        self.keep_timepoints = keep_timepoints if keep_timepoints is not None else spec.keep_timepoints()
         self._rescore_targets = 0
         h = C.c_void_p()
 
         def ref(block):
             return C.byref(block) if block is not None else None
 
-        if self.keep is not None:  # (only a spec that asks for kept samples goes through _keep)
+        if self.keep_timepoints is not None:  # (only a spec that asks for them goes through _keep_timepoints)
+            _check(self._keep_timepoints_lib().ecdna_ssa_ctx_create_keep_timepoints(
+                C.byref(self.params), ref(self.ext), ref(self.passages), ref(self.cohort), ref(self.keep),
+                C.byref(self.keep_timepoints), C.byref(h)), "ecdna_ssa_ctx_create_keep_timepoints")
+        elif self.keep is not None:  # (only a spec that asks for kept samples goes through _keep)
             if not hasattr(lib(), "ecdna_ssa_ctx_create_keep"):
                 raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_keep (kept samples)")
             _check(lib().ecdna_ssa_ctx_create_keep(C.byref(self.params), ref(self.ext), ref(self.passages),
@@ -456,9 +480,11 @@ class Context:
 
     def accept_timepoints(self, source: int) -> int:
         """T of an acceptance source: 1, the spec's snapshots, its passages, its cohort's targets, or the targets of
-        the last rescore."""
+        the last rescore; for the rescored timepoints, the context's snapshots or passages."""
         if source == abi.ACCEPT_RESCORED:
             return self._rescore_targets
+        if source == abi.ACCEPT_RESCORED_TIMEPOINTS:
+            return self.timepoints()
         if source in (abi.ACCEPT_COHORT, abi.ACCEPT_COHORT_SAMPLES):
             return int(self.cohort.n_targets) if self.cohort is not None else 0
         if source in (abi.ACCEPT_SNAPSHOTS, abi.ACCEPT_SNAPSHOT_SAMPLES):
@@ -641,6 +667,86 @@ class Context:
                                                             headers.ctypes.data if k else None,
                                                             cells.ctypes.data if cells.size else None),
                "ecdna_ssa_ctx_download_kept")
+        return headers, cells
+
+    def _keep_timepoints_lib(self):
+        if not hasattr(lib(), "ecdna_ssa_ctx_create_keep_timepoints"):
+            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_keep_timepoints (kept timepoint samples)")
+        return lib()
+
+    def timepoints(self) -> int:
+        """T of the timepoint keep block: the context's growth phases, else its snapshots with snapshot statistics."""
+        if self.passages is not None:
+            return int(self.passages.n_passages)
+        if self.ext is not None and self.ext.snapshot_stats:
+            return int(self.params.n_snapshots)
+        return 0
+
+    def rescore_timepoints_enqueue(self, targets):
+        """Enqueue the late scoring of the kept timepoint samples against one longitudinal target, `targets`
+        [T][hist_bins], on the stream of the last launch (ecdna_ssa_ctx_rescore_timepoints);
+        download_rescored_timepoints returns the records."""
+        tgt = np.ascontiguousarray(targets, dtype=np.uint64)
+        if self.keep_timepoints is not None and (tgt.ndim != 2 or tgt.shape != (self.timepoints(), self.params.hist_bins)):
+            raise ValueError("targets must be [T][hist_bins]: one histogram of hist_bins entries per timepoint")
+        _check(self._keep_timepoints_lib().ecdna_ssa_ctx_rescore_timepoints(self.h, tgt.ctypes.data if tgt.size else None),
+               "ecdna_ssa_ctx_rescore_timepoints")
+
+    def download_rescored_timepoints(self) -> np.ndarray:
+        """The records of the last rescore_timepoints, [T][n] abi.STATS_DTYPE
+        (ecdna_ssa_ctx_download_rescored_timepoints; synchronises)."""
+        T = self.timepoints() if self.keep_timepoints is not None else 0
+        out = np.zeros((T, int(self.params.n_replicates)), dtype=abi.STATS_DTYPE)
+        _check(self._keep_timepoints_lib().ecdna_ssa_ctx_download_rescored_timepoints(
+            self.h, out.ctypes.data if out.size else None), "ecdna_ssa_ctx_download_rescored_timepoints")
+        return out
+
+    def rescore_timepoints(self, targets) -> np.ndarray:
+        """Score every replicate's kept sample of every timepoint (RunSpec.keep_timepoint_cells) against a longitudinal
+        target that need not have been known at create: records [T][n] abi.STATS_DTYPE, byte for byte the sample
+        records of a run created with these targets as passage_targets (or as snapshot_targets with
+        snapshot_subsample_cells = keep_timepoint_cells). They are the acceptance source
+        abi.ACCEPT_RESCORED_TIMEPOINTS until the next rescore_timepoints or launch."""
+        self.rescore_timepoints_enqueue(targets)
+        return self.download_rescored_timepoints()
+
+    def pool_accepted_timepoints(self, threshold: int) -> np.ndarray:
+        """The posterior predictive histogram per timepoint (ecdna_ssa_ctx_pool_accepted_timepoints): per timepoint and
+        global parameter set, the sum of the kept samples' histograms of the replicates the last accept() accepted
+        under row `threshold`, [T][n_param_sets][hist_bins] u64. Shards' arrays sum to the whole run's."""
+        if not (0 <= int(threshold) < (1 << 32)):
+            raise ValueError(f"threshold = {threshold} does not fit the ABI's u32 field")
+        p = self.params
+        T = self.timepoints() if self.keep_timepoints is not None else 0
+        out = np.zeros((max(T, 1), p.n_param_sets, p.hist_bins), dtype=np.uint64)
+        _check(self._keep_timepoints_lib().ecdna_ssa_ctx_pool_accepted_timepoints(self.h, int(threshold),
+                                                                                  out.ctypes.data),
+               "ecdna_ssa_ctx_pool_accepted_timepoints")
+        return out[:T]
+
+    def download_kept_timepoints(self, ids=None, count: Optional[int] = None):
+        """Kept timepoint samples of the last launch (ecdna_ssa_ctx_download_kept_timepoints): (headers [T][k]
+        abi.KEPT_DTYPE, cells [T][k][keep_timepoint_cells] u16) of the replicates with the global `ids`, in their order,
+        or of the call's first `count` replicates (default: all). cells[t][j][:headers[t][j]["nplus"]] are the N+
+        cells' true copy numbers, ascending; the rest of a row is unspecified."""
+        m = int(self.keep_timepoints.keep_cells) if self.keep_timepoints is not None else 0
+        T = self.timepoints() if self.keep_timepoints is not None else 0
+        if ids is not None:
+            if count is not None:
+                raise ValueError("give ids or count, not both")
+            idv = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+            k = len(idv)
+        else:
+            idv = None
+            k = int(self.params.n_replicates) if count is None else int(count)
+            if not (0 <= k < (1 << 64)):
+                raise ValueError(f"count = {count} does not fit the ABI's u64 field")
+        headers = np.zeros((T, k), dtype=abi.KEPT_DTYPE)
+        cells = np.zeros((T, k, m), dtype=np.uint16)
+        _check(self._keep_timepoints_lib().ecdna_ssa_ctx_download_kept_timepoints(
+            self.h, k, idv.ctypes.data if idv is not None and k else None,
+            headers.ctypes.data if headers.size else None, cells.ctypes.data if cells.size else None),
+            "ecdna_ssa_ctx_download_kept_timepoints")
         return headers, cells
 
     def download(self, want_rows: bool = False) -> Result:

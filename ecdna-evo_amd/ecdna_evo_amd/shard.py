@@ -255,3 +255,20 @@ def pool_accepted(ctx, threshold: int, group=None, device=None):
         t = t.to(device)
     dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
     return t.cpu().numpy().view(np.uint64)
+
+
+def pool_accepted_timepoints(ctx, threshold: int, group=None, device=None):
+    """Context.pool_accepted_timepoints over every rank's shard: the whole run's posterior predictive histogram per
+    timepoint, [T][n_param_sets][hist_bins] u64, the same on every rank. Each rank pools its own accepted replicates'
+    kept timepoint samples and one all-reduce (int64, sum) joins the arrays: integer sums, exact in any order. `device`
+    as for select()."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    hist = np.ascontiguousarray(ctx.pool_accepted_timepoints(threshold))
+    t = torch.from_numpy(hist.view(np.int64))  # (counts stay far below 2^63)
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.cpu().numpy().view(np.uint64)

@@ -43,7 +43,15 @@
 extern "C" {
 #endif
 
-/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): every replicate's
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): the sample of every
+ * timepoint of a longitudinal run kept on the GPU — the timepoint keep block ecdna_ssa_keep_timepoints_t and
+ * ecdna_ssa_ctx_create_keep_timepoints, late scoring of a longitudinal target (ecdna_ssa_ctx_rescore_timepoints,
+ * ecdna_ssa_ctx_download_rescored_timepoints and the acceptance source ECDNA_ACCEPT_RESCORED_TIMEPOINTS), the posterior
+ * predictive histogram per timepoint ecdna_ssa_ctx_pool_accepted_timepoints and the kept cells themselves,
+ * ecdna_ssa_ctx_download_kept_timepoints (below; timepoint keep mapping v1). ecdna_ssa_ctx_create_keep(p, ext, passages,
+ * cohort, keep, out) is ecdna_ssa_ctx_create_keep_timepoints(p, ext, passages, cohort, keep, NULL, out): a context
+ * without the block allocates and launches nothing new.
+ * Added within v13 (additive: no layout and no existing function changes, the version stays 13): every replicate's
  * sample kept on the GPU, scored and pooled after the sweep — the keep block ecdna_ssa_keep_t and
  * ecdna_ssa_ctx_create_keep, late scoring against targets that were not known at create (ecdna_ssa_ctx_rescore,
  * ecdna_ssa_ctx_download_rescored and the acceptance source ECDNA_ACCEPT_RESCORED), the posterior predictive histogram
@@ -552,6 +560,83 @@ int ecdna_ssa_ctx_pool_accepted(ecdna_ssa_ctx* c, uint32_t threshold,
 int ecdna_ssa_ctx_download_kept(ecdna_ssa_ctx* c, uint64_t n_ids,
                                 const uint64_t* ids /* host, global ids; NULL: the call's first n_ids replicates */,
                                 ecdna_kept_t* out_headers /* [n_ids] */, uint16_t* out_cells /* [n_ids][keep_cells] */);
+
+/* Every timepoint's sample kept on the GPU (added within ABI v13). The keep block above stops at the end of the run. The
+ * two longitudinal modes — the snapshots of the patient strategy (ecdna_ssa_ext_t.snapshot_stats) and the growth phases
+ * of the cell-line strategy (ecdna_ssa_passages_t) — are where a sweep costs most, and their samples were discarded: a
+ * second patient, a re-binned target, the posterior predictive per timepoint or the accepted simulations' cells at each
+ * timepoint needed a new sweep. With the timepoint keep block the sample of every (replicate, timepoint) pair stays on
+ * the device, in run-sized buffers headers[T][n] and cells[T][n][m] allocated at create: T × n × (2m + 8) bytes. (By
+ * arithmetic, not a measurement: 6.7 GB of cells and 0.13 GB of headers for 2^22 replicates at T = 4 and m = 200.)
+ * ECDNA_E_NOMEM at create, with the
+ * byte count in the message, if they do not fit.
+ *
+ * Timepoint keep mapping v1. T is the number of timepoints of the context, m = keep_cells. Replicate ids are global.
+ *  - A snapshot context (params.n_snapshots = S > 0 and ext->snapshot_stats = 1; T = S): the kept sample of (replicate
+ *    r, snapshot s) is the sample that snapshot_subsample_cells = m defines for that pair, unchanged: its population is
+ *    "nminus N- cells, then the snapshot row", drawn by subsample mapping v1 on stream field (s + 1) << 16 under the
+ *    run's key. ext->snapshot_subsample_cells keeps its meaning and stays independent of the block. A snapshot that was
+ *    not taken keeps {0, 0}. The row is never read past min(nplus, the row's stride). The pass runs per chunk after the
+ *    snapshot statistics, while the chunk's snapshot rows exist: with or without ECDNA_FLAG_SNAPSHOT_ROWS.
+ *  - A passage context (T = G = n_passages): keep_cells must equal passage_cells — the kept sample of phase g is the
+ *    sample that founds phase g + 1, and another size on the same stream would be a different sample. The kept sample of
+ *    (r, g) is phase g's sample under seed_g, stream field 0 (passage mapping v1). For g < G - 1 its header and cells
+ *    are the founders of phase g + 1. The last phase is kept too. A phase that never started (an ECDNA_REP_ERR_EMPTY
+ *    phase is one) keeps {0, 0}.
+ *  - Both: the format is keep mapping v1's — the header ecdna_kept_t {nminus, nplus} with nminus + nplus = min(m, N),
+ *    then the nplus TRUE copy numbers, ascending; {0xffffffff, 0xffffffff} for a sample the guard ended. Nothing depends
+ *    on chunk, shard, grid or device. Chunked runs are covered. Every other output of the run is unchanged.
+ * Rejected at create (ECDNA_E_INVALID, before a device is touched, the message names the field): a wrong struct_size,
+ * reserved != 0, keep_cells outside 1 .. 4096, ECDNA_FLAG_REP_STATS missing, a context with neither a passage block nor
+ * ext->snapshot_stats, and a passage block with keep_cells != passage_cells. The end-of-run keep block beside a
+ * snapshot context stays legal and independent. */
+typedef struct {
+    uint32_t struct_size;   /* sizeof(ecdna_ssa_keep_timepoints_t); anything else: ECDNA_E_INVALID */
+    uint32_t keep_cells;    /* m, 1 .. 4096 */
+    uint64_t reserved;      /* must be 0 */
+} ecdna_ssa_keep_timepoints_t;
+/* ecdna_ssa_ctx_create_keep with a timepoint keep block. keep_timepoints == NULL: exactly ecdna_ssa_ctx_create_keep —
+ * nothing more is allocated or launched, and ecdna_ssa_ctx_instance is unchanged. The five older create calls forward
+ * to this one. */
+int ecdna_ssa_ctx_create_keep_timepoints(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
+                                         const ecdna_ssa_passages_t* passages, const ecdna_ssa_cohort_t* cohort,
+                                         const ecdna_ssa_keep_t* keep,
+                                         const ecdna_ssa_keep_timepoints_t* keep_timepoints, ecdna_ssa_ctx** out);
+/* The four calls over the kept timepoint samples return ECDNA_E_STATE before a launch and on a context without the
+ * block (the message names ecdna_ssa_ctx_create_keep_timepoints).
+ *
+ * Late scoring of one longitudinal target: timepoint t's kept samples against target_hists[t], binned as
+ * stats_target_hist. Called again for the next patient. Enqueued on the stream of the last launch, asynchronous. The
+ * records lie [T][n]. Record [t][i] is byte for byte: on a passage context, ecdna_ssa_ctx_download_passages'
+ * out_sample_stats[t][i] of the same run created with passage_target_hists = target_hists; on a snapshot context,
+ * ecdna_ssa_ctx_download_snapshot_stats' out_sample_stats[i][t] of the same run created with snapshot_target_hists =
+ * target_hists and snapshot_subsample_cells = m. The records and their validity are the call's own, apart from
+ * ecdna_ssa_ctx_rescore's. A later call replaces them and drops the keys ecdna_ssa_ctx_select cached, as
+ * ecdna_ssa_ctx_rescore does; a relaunch invalidates them.
+ * The records are the acceptance source ECDNA_ACCEPT_RESCORED_TIMEPOINTS = 13: T as above, rep stride 1, timepoint
+ * stride n. On a passage context the error rule and strides are ECDNA_ACCEPT_PASSAGE_SAMPLES' (per-phase summaries,
+ * every participating phase error-free); on a snapshot context the one-summary rule of ECDNA_ACCEPT_FINAL.
+ * ecdna_ssa_ctx_accept, _select and _select_digits take it; before a rescore_timepoints they return ECDNA_E_STATE.
+ * ECDNA_E_INVALID: NULL c, NULL target_hists, an all-zero target row (target_hists[t] is named). ECDNA_E_NOMEM leaves the
+ * context usable. */
+int ecdna_ssa_ctx_rescore_timepoints(ecdna_ssa_ctx* c, const uint64_t* target_hists /* host [T][hist_bins] */);
+/* The records of the last ecdna_ssa_ctx_rescore_timepoints, [T][n] (ECDNA_E_STATE before one, and after a relaunch until
+ * the next). Synchronises. */
+int ecdna_ssa_ctx_download_rescored_timepoints(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out /* [T][n] */);
+/* The posterior predictive histogram per timepoint. Synchronous. For row `threshold` of the last ecdna_ssa_ctx_accept,
+ * whatever its source and timepoint mask, out_hist[t][s] is the sum, over the accepted replicates of global parameter
+ * set s, of their timepoint-t kept samples' histograms. Binning and guard handling are ecdna_ssa_ctx_pool_accepted's. The
+ * sums are integers: shards' arrays sum to the whole run's.
+ * ECDNA_E_STATE also without valid accept results. ECDNA_E_INVALID: NULL c, threshold >= Q of that accept, NULL out_hist. */
+int ecdna_ssa_ctx_pool_accepted_timepoints(ecdna_ssa_ctx* c, uint32_t threshold,
+                                           uint64_t* out_hist /* host [T][n_param_sets][hist_bins] */);
+/* The kept timepoint samples of the replicates with the global ids ids[0 .. n_ids) (ids == NULL: the call's first n_ids
+ * replicates), in the order of ids, every timepoint. The id rules and errors are ecdna_ssa_ctx_download_kept's. Either
+ * output may be NULL. */
+int ecdna_ssa_ctx_download_kept_timepoints(ecdna_ssa_ctx* c, uint64_t n_ids,
+                                           const uint64_t* ids /* host, global ids; NULL: the first n_ids replicates */,
+                                           ecdna_kept_t* out_headers /* [T][n_ids] */,
+                                           uint16_t* out_cells /* [T][n_ids][keep_cells] */);
 /* Use caller-owned DEVICE buffers for the histogram [n_param_sets*hist_bins] u64 and totals
  * [n_param_sets] (e.g. tensors later all-reduced over RCCL). NULL keeps the internal buffer. */
 int ecdna_ssa_ctx_set_outputs(ecdna_ssa_ctx* c, uint64_t* d_hist, ecdna_totals_t* d_totals);
@@ -561,7 +646,8 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream);
 /* Block until the last launch finished; returns its device time in ms (HIP events on the launch
  * stream): ssa_ms = SSA stepper kernels only, hist_ms = histogram/summary kernels (and the
  * subsampling pass when params.subsample_cells > 0, and the snapshot statistics pass under
- * ecdna_ssa_ext_t.snapshot_stats, and the cohort pass under ecdna_ssa_cohort_t). Either may be NULL. */
+ * ecdna_ssa_ext_t.snapshot_stats, and the cohort pass under ecdna_ssa_cohort_t, and the keep passes of
+ * ecdna_ssa_keep_t and ecdna_ssa_keep_timepoints_t). Either may be NULL. */
 int ecdna_ssa_ctx_sync(ecdna_ssa_ctx* c, float* ssa_ms, float* hist_ms);
 /* Device pointers of the current outputs. */
 int ecdna_ssa_ctx_device_outputs(ecdna_ssa_ctx* c, uint64_t** d_hist, ecdna_totals_t** d_totals);
@@ -615,8 +701,14 @@ typedef enum {
     ECDNA_ACCEPT_COHORT = 8,           /* download_cohort's out_stats, T = n_targets: timepoint p is target p */
     ECDNA_ACCEPT_COHORT_SAMPLES = 9,   /* ... out_sample_stats, T = n_targets (needs sample_cells) */
     /* (10 and 11 are not sources: ECDNA_E_INVALID) */
-    ECDNA_ACCEPT_RESCORED = 12         /* download_rescored's records, T = the P of the last ecdna_ssa_ctx_rescore */
+    ECDNA_ACCEPT_RESCORED = 12,        /* download_rescored's records, T = the P of the last ecdna_ssa_ctx_rescore */
+    ECDNA_ACCEPT_RESCORED_TIMEPOINTS   /* 13, the next value: download_rescored_timepoints' records, T = the context's
+                                          timepoints (n_snapshots or n_passages) */
 } ecdna_accept_source_t;
+/* The rescored timepoints (source 13): the records lie [T][n] (rep stride 1, timepoint stride n). On a passage context
+ * the error rule is the passage sources' (error stride n: error == 0 in the summary of every participating phase); on a
+ * snapshot context the one-summary rule (error stride 0). ECDNA_E_STATE on a context without the timepoint keep block,
+ * and before an ecdna_ssa_ctx_rescore_timepoints. */
 /* The cohort sources: the error rule is the one-summary rule of ECDNA_ACCEPT_FINAL; the records lie [P][n] (rep stride 1,
  * timepoint stride n, error stride 0); timepoint_mask = 1 << p gives patient p's acceptance or quantiles, 0 all P
  * jointly, as for every source. A context without the cohort block returns ECDNA_E_STATE for both, and so does
