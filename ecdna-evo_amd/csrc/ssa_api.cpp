@@ -2,7 +2,8 @@
 // device-resident run contexts, chunking by HBM capacity, and launches of the
 // stepper and end-of-run kernels (ssa_kernels.hip, ssa_hist.hip, ssa_subsample.hip, ssa_snapstats.hip,
 // ssa_passage.hip, ssa_cohort.hip), of the post-launch acceptance pass (ssa_accept.hip) and of the passes over the kept
-// samples (ssa_rescore.hip).
+// samples (ssa_rescore.hip). The kept samples of the keep block and of the timepoint keep block lie in one kind of store
+// (KeptStore), and every pass over them has one implementation, which the two blocks' entry points call.
 //
 // This file replaces, for one GPU, the per-replicate driver loop of the
 // reference: run_simulations(idx) mapped by rayon over seed*10 .. seed*10+runs
@@ -23,7 +24,6 @@
 #include "../../include/ecdna_ssa.h"
 #include "ssa_cohort.hpp"
 #include "ssa_keep.hpp"
-#include "ssa_keep_timepoints.hpp"
 #include "ssa_launch.h"
 #include "ssa_plan.hpp"
 #include "ssa_select.hpp"
@@ -79,6 +79,9 @@ uint32_t first_empty_target(const uint64_t* hists, uint32_t count, uint32_t bins
     return count;
 }
 
+// The step between the global ids of a call's replicates (replicate_stride = 0 stands for 1).
+uint64_t rid_stride(const ecdna_ssa_params_t& p) { return p.replicate_stride ? p.replicate_stride : 1u; }
+
 int validate(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, const ecdna_ssa_passages_t* pas) {
     if (!p) return fail(ECDNA_E_INVALID, "params is NULL");
     if (!p->rates || p->n_param_sets == 0) return fail(ECDNA_E_INVALID, "rates/n_param_sets");
@@ -107,7 +110,7 @@ int validate(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, const ecdn
     if (p->segregation < 0 || p->segregation > 3) return fail(ECDNA_E_INVALID, "unknown segregation");
     if (p->max_iter > 0xffffffffull) return fail(ECDNA_E_INVALID, "max_iter must be < 2^32");
     if (p->n_replicates > 0xffffffffull) return fail(ECDNA_E_INVALID, "n_replicates must be < 2^32 per call");
-    const uint64_t stride = p->replicate_stride ? p->replicate_stride : 1u;
+    const uint64_t stride = rid_stride(*p);
     if (p->n_replicates && (p->n_replicates - 1) > (~0ull - p->first_replicate) / stride)
         return fail(ECDNA_E_INVALID, "replicate ids overflow u64");
     if (p->n_replicates && (p->first_replicate + (p->n_replicates - 1) * stride) / p->reps_per_set >= p->n_param_sets)
@@ -243,6 +246,24 @@ struct AcceptBuf {
     uint64_t bytes = 0;
 };
 
+// A store of kept samples (m = 0: the context has no such block): the keep block's (ecdna_ssa_keep_t), one slice, or the
+// timepoint keep block's (ecdna_ssa_keep_timepoints_t), a slice per timepoint — the run's snapshots or growth phases.
+// Headers [T][n] and cells [T][n][m] are sized by the run and written by the keep pass of every chunk. The store's last
+// rescore left its records [T][P][n] with the targets' CDFs [T][P][bins] and scalars [T][P][3] (and their host copies,
+// which an asynchronous upload reads) in buffers that belong to the context as the acceptance pass's do. The pooled
+// histogram and the gather's index and staging are the context's, shared by its stores (both calls are synchronous).
+struct KeptStore {
+    uint32_t m = 0, T = 0;
+    uint2* d_headers = nullptr;
+    uint16_t* d_cells = nullptr;
+    AcceptBuf stats, cdf, scalars;
+    std::vector<double> host_cdf, host_scalars;
+    bool valid = false;    // (a launch invalidates the records)
+    bool pending = false;  // a rescore was enqueued since the stream was last drained
+    uint32_t targets = 0;  // the P of the last rescore: targets per slice (the timepoint keep block: 1)
+    hipStream_t stream = nullptr;
+};
+
 }  // namespace
 
 struct ecdna_ssa_ctx {
@@ -357,33 +378,11 @@ struct ecdna_ssa_ctx {
     bool sel_keys_valid = false;
     uint32_t sel_source = 0;
     uint64_t sel_tmask = 0;
-    // the kept samples (ecdna_ssa_keep_t; keep_m = 0: no block): headers [n] and cells [n][keep_m], sized by the run and
-    // written by the keep pass of every chunk. The passes over them keep buffers that belong to the context as the
-    // acceptance pass's do: the rescored records [P][n] with the targets' CDFs [P][bins] and scalars [P][3] (and their
-    // host copies, which an asynchronous upload reads), the pooled histogram, and the gather's index and staging.
-    uint32_t keep_m = 0;
-    uint2* d_kept_headers = nullptr;
-    uint16_t* d_kept_cells = nullptr;
-    AcceptBuf rs_stats, rs_cdf, rs_scalars, pool_hist, gat_index, gat_headers, gat_cells;
-    std::vector<double> rs_cdf_host, rs_scalars_host;
-    bool rescore_valid = false;   // (a launch invalidates the records)
-    bool rescore_pending = false; // a rescore was enqueued since the stream was last drained
-    uint32_t rescore_targets = 0; // the P of the last rescore
-    hipStream_t rescore_stream = nullptr;
-    // the kept samples of every timepoint (ecdna_ssa_keep_timepoints_t; tk_m = 0: no block): headers [T][n] and cells
-    // [T][n][tk_m], sized by the run; T = tk_T is the run's snapshots or growth phases. The records of
-    // ecdna_ssa_ctx_rescore_timepoints [T][n], their targets and their validity are apart from ecdna_ssa_ctx_rescore's;
-    // the pooled histogram [T][sets][bins] and the gather's staging [T][n_ids] share the keep block's buffers (both
-    // calls are synchronous).
-    uint32_t tk_m = 0;
-    uint32_t tk_T = 0;
-    uint2* d_tk_headers = nullptr;
-    uint16_t* d_tk_cells = nullptr;
-    AcceptBuf tk_stats, tk_cdf, tk_scalars;
-    std::vector<double> tk_cdf_host, tk_scalars_host;
-    bool tk_rescore_valid = false;
-    bool tk_rescore_pending = false;
-    hipStream_t tk_rescore_stream = nullptr;
+    // the kept samples: the keep block's store (ecdna_ssa_ctx_rescore's records [P][n]) and the timepoint keep block's
+    // (ecdna_ssa_ctx_rescore_timepoints's [T][n]), each with its own records, targets and validity; and what the passes
+    // over either share: the pooled histogram [T][sets][bins], the gather's index [n_ids] and staging [T][n_ids]
+    KeptStore kept, kept_tp;
+    AcceptBuf pool_hist, gat_index, gat_headers, gat_cells;
 };
 
 namespace {
@@ -414,8 +413,8 @@ void free_ctx(ecdna_ssa_ctx* c) {
             if (e) (void)hipEventDestroy(e);
     for (void* d : c->owned) (void)hipFree(d);
     for (AcceptBuf* b : {&c->acc_mask, &c->acc_counts, &c->acc_blocks, &c->acc_ids, &c->acc_list, &c->sel_keys,
-                         &c->sel_hist, &c->rs_stats, &c->rs_cdf, &c->rs_scalars, &c->pool_hist, &c->gat_index,
-                         &c->gat_headers, &c->gat_cells, &c->tk_stats, &c->tk_cdf, &c->tk_scalars})
+                         &c->sel_hist, &c->pool_hist, &c->gat_index, &c->gat_headers, &c->gat_cells, &c->kept.stats,
+                         &c->kept.cdf, &c->kept.scalars, &c->kept_tp.stats, &c->kept_tp.cdf, &c->kept_tp.scalars})
         if (b->ptr) (void)hipFree(b->ptr);
     delete c;
 }
@@ -468,7 +467,7 @@ double target_total(const uint64_t* hist, uint32_t bins) {
     for (uint32_t b = 0; b < bins; ++b) tot += (double)hist[b];
     return tot;
 }
-void summarize_targets(const uint64_t* hists, uint64_t count, uint32_t bins, double* cdf_out, double* scalars_out) {
+void summarize_targets(const uint64_t* hists, uint64_t count, uint32_t bins, double* out_cdf, double* out_scalars) {
     for (uint64_t i = 0; i < count; ++i) {
         const uint64_t* hist = hists + i * bins;
         const double tot = target_total(hist, bins);
@@ -476,13 +475,13 @@ void summarize_targets(const uint64_t* hists, uint64_t count, uint32_t bins, dou
         for (uint32_t b = 0; b < bins; ++b) {
             const double pb = (double)hist[b] / tot;
             acc += pb;
-            cdf_out[i * bins + b] = acc;
+            out_cdf[i * bins + b] = acc;
             ksum += (double)b * (double)hist[b];
             if (pb > 0.0) ent -= pb * std::log(pb);
         }
-        scalars_out[3 * i] = ksum / tot;
-        scalars_out[3 * i + 1] = ent;
-        scalars_out[3 * i + 2] = 1.0 - (double)hist[0] / tot;
+        out_scalars[3 * i] = ksum / tot;
+        out_scalars[3 * i + 1] = ent;
+        out_scalars[3 * i + 2] = 1.0 - (double)hist[0] / tot;
     }
 }
 
@@ -601,35 +600,18 @@ int adopt_cohort(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_
     return ECDNA_OK;
 }
 
-// The keep block: the kept samples' headers and cells, sized by the run.
-int adopt_keep(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_keep_t* keep) {
-    c->keep_m = keep->keep_cells;
-    const uint64_t n1 = std::max<uint64_t>(p->n_replicates, 1);
-    const uint64_t bytes = ecdna::keep::cells_bytes(n1, c->keep_m) + ecdna::keep::headers_bytes(n1);
-    hipError_t e = ctx_alloc(c, &c->d_kept_headers, n1);
-    if (e == hipSuccess) e = ctx_alloc(c, &c->d_kept_cells, n1 * c->keep_m);
+// A keep block's store of T slices of samples of m cells: the headers [T][n] and cells [T][n][m], sized by the run.
+// `who`: the create call of the block, for the message.
+int adopt_kept_store(ecdna_ssa_ctx* c, KeptStore* s, uint32_t T, uint32_t m, const char* who) {
+    s->T = T;
+    s->m = m;
+    const uint64_t n1 = std::max<uint64_t>(c->p.n_replicates, 1);
+    hipError_t e = ctx_alloc(c, &s->d_headers, T * n1);
+    if (e == hipSuccess) e = ctx_alloc(c, &s->d_cells, T * n1 * m);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         return fail(e == hipErrorOutOfMemory ? ECDNA_E_NOMEM : ECDNA_E_HIP,
-                    "ecdna_ssa_ctx_create_keep: the kept samples (" + std::to_string(bytes) +
-                        " bytes) do not fit: " + hipGetErrorString(e));
-    }
-    return ECDNA_OK;
-}
-
-// The timepoint keep block: the kept samples' headers [T][n] and cells [T][n][m], sized by the run.
-int adopt_keep_timepoints(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext,
-                          const ecdna_ssa_passages_t* pas, const ecdna_ssa_keep_timepoints_t* kt) {
-    c->tk_m = kt->keep_cells;
-    c->tk_T = ecdna::keep_timepoints::timepoints(*p, ext, pas);
-    const uint64_t n1 = std::max<uint64_t>(p->n_replicates, 1);
-    const uint64_t bytes = ecdna::keep_timepoints::bytes(c->tk_T, n1, c->tk_m);
-    hipError_t e = ctx_alloc(c, &c->d_tk_headers, c->tk_T * n1);
-    if (e == hipSuccess) e = ctx_alloc(c, &c->d_tk_cells, c->tk_T * n1 * c->tk_m);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? ECDNA_E_NOMEM : ECDNA_E_HIP,
-                    "ecdna_ssa_ctx_create_keep_timepoints: the kept samples (" + std::to_string(bytes) +
+                    std::string(who) + ": the kept samples (" + std::to_string(ecdna::keep::bytes(T, n1, m)) +
                         " bytes) do not fit: " + hipGetErrorString(e));
     }
     return ECDNA_OK;
@@ -745,7 +727,7 @@ int alloc_plan(ecdna_ssa_ctx* c, const ecdna::plan::LaunchPlan& pl, const float*
 
     // start order (set_cost_hint): within each chunk, replicates of costlier sets first, then by id
     if (set_cost_hint && n) {
-        const uint64_t stride = p.replicate_stride ? p.replicate_stride : 1u;
+        const uint64_t stride = rid_stride(p);
         std::vector<uint32_t> order(n);
         for (const Chunk& ch : c->chunks) {
             uint32_t* o = order.data() + ch.first;
@@ -786,8 +768,10 @@ int build_ctx(ecdna_ssa_ctx* c, const ecdna_ssa_params_t* p, const ecdna_ssa_ext
     TRY(upload_inputs(c));
     TRY(upload_targets(c, p, ext, pas));
     if (co) TRY(adopt_cohort(c, p, co));
-    if (keep) TRY(adopt_keep(c, p, keep));
-    if (kt) TRY(adopt_keep_timepoints(c, p, ext, pas, kt));
+    if (keep) TRY(adopt_kept_store(c, &c->kept, 1u, keep->keep_cells, "ecdna_ssa_ctx_create_keep"));
+    if (kt)
+        TRY(adopt_kept_store(c, &c->kept_tp, ecdna::keep_timepoints::timepoints(*p, ext, pas), kt->keep_cells,
+                             "ecdna_ssa_ctx_create_keep_timepoints"));
     TRY(alloc_outputs(c));
     ecdna::plan::DeviceFacts facts;
     TRY(gather_facts(c, knobs, &facts));
@@ -817,9 +801,8 @@ ecdna::StepperArgs stepper_args(const ecdna_ssa_ctx* c, const Chunk& ch, size_t 
         a.founder_counts = c->d_founder_counts;
         a.founder_stride = c->founder_stride;
     }
-    const uint64_t stride = p.replicate_stride ? p.replicate_stride : 1u;
-    a.rid0 = p.first_replicate + ch.first * stride;
-    a.rid_stride = stride;
+    a.rid_stride = rid_stride(p);
+    a.rid0 = p.first_replicate + ch.first * a.rid_stride;
     a.reps_per_set = p.reps_per_set;
     a.max_cells = p.max_cells;
     a.init_nminus = p.init_nminus;
@@ -886,6 +869,15 @@ uint32_t pass_reps_per_block(const ecdna_ssa_ctx* c, uint32_t n, uint32_t floor)
     return std::max<uint32_t>(floor, (n + hist_blocks_max - 1) / hist_blocks_max);
 }
 uint32_t pass_blocks(const ecdna::ChunkIds& ids) { return (ids.n + ids.reps_per_block - 1) / ids.reps_per_block; }
+// The share of a pass that sums histograms per parameter set, in workgroups of `block` lanes (the histogram pass, and
+// the pooling of the kept samples): at least one replicate per lane of a workgroup, or the chunk's replicates of one
+// parameter set if fewer: small runs otherwise spread over 2,048 workgroups of mostly idle waves, each adding its own
+// nonzero bins to the same global words (C2: 0.061 -> 0.023 ms per launch at 256, 0.038 at 64, 0.052 at 1,024;
+// profiles/r06ak_hist_rpb.txt); sweeps of small sets keep about one set per workgroup
+uint32_t hist_reps_per_block(const ecdna_ssa_ctx* c, uint32_t n, uint32_t block) {
+    const uint64_t set_local = c->p.reps_per_set / rid_stride(c->p);
+    return pass_reps_per_block(c, n, (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(block, set_local)));
+}
 
 ecdna::HistArgs hist_args(const ecdna_ssa_ctx* c, const Chunk& ch, uint32_t g, const ecdna::FinalState& fs,
                           ecdna::ChunkIds ids, const ecdna::StatsTarget& target) {
@@ -901,13 +893,7 @@ ecdna::HistArgs hist_args(const ecdna_ssa_ctx* c, const Chunk& ch, uint32_t g, c
     h.bag_c32 = fs.bag_c32;
     h.hist = pas ? c->d_pas_hist + g * nb : c->d_hist;
     h.totals = reinterpret_cast<unsigned long long*>(pas ? c->d_pas_tot + (uint64_t)g * p.n_param_sets : c->d_tot);
-    // at least one replicate per lane of a workgroup, or the chunk's replicates of one parameter set if fewer: small
-    // runs otherwise spread over 2,048 workgroups of mostly idle waves, each adding its own nonzero bins to the
-    // same global words (C2: 0.061 -> 0.023 ms per launch at 256, 0.038 at 64, 0.052 at 1,024;
-    // profiles/r06ak_hist_rpb.txt); sweeps of small sets keep about one set per workgroup
-    const uint64_t set_local = std::max<uint64_t>(1, p.reps_per_set / ids.rid_stride);
-    ids.reps_per_block = pass_reps_per_block(
-        c, ch.n, (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(ecdna::kHistBlock, set_local)));
+    ids.reps_per_block = hist_reps_per_block(c, ch.n, ecdna::kHistBlock);
     h.ids = ids;
     h.stats = pas ? c->d_pas_stats + g * n_run + ch.first : (c->d_stats ? c->d_stats + ch.first : nullptr);
     h.target = target;
@@ -958,90 +944,72 @@ int launch_cohort_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::Fin
     return ECDNA_OK;
 }
 
-// phase g's measurement, and (but for the last phase) the founders of the next
-int launch_passage_pass(const ecdna_ssa_ctx* c, const Chunk& ch, uint32_t g, const ecdna::FinalState& fs,
-                        ecdna::ChunkIds ids, const ecdna::StatsTarget& target, uint64_t seed_g, hipStream_t st) {
-    const ecdna_ssa_params_t& p = c->p;
-    const uint64_t nb = (uint64_t)p.n_param_sets * p.hist_bins, n_run = std::max<uint64_t>(p.n_replicates, 1);
+// What the passes of ssa_passage.hip share: the populations, and a sample of m cells of each under `seed` with the
+// per-wave table and sort slots that its size asks for. keep_args: such samples into slice `slice` of a store, at the
+// chunk's offset. set_share: the chunk's ids under the pass's share, `waves` populations per workgroup at least.
+ecdna::PassageArgs sample_args(const ecdna::FinalState& fs, uint32_t m, uint64_t seed) {
     ecdna::PassageArgs pa{};
     pa.state = fs;
+    pa.seed = seed;
+    pa.m = m;
+    pa.table_slots = ecdna::subsample_table_slots(m);
+    pa.sort_slots = ecdna::passage_sort_slots(m);
+    return pa;
+}
+ecdna::PassageArgs keep_args(const ecdna_ssa_ctx* c, const KeptStore& s, uint32_t slice, const Chunk& ch,
+                             const ecdna::FinalState& fs, uint64_t seed) {
+    const uint64_t at = slice * std::max<uint64_t>(c->p.n_replicates, 1) + ch.first;
+    ecdna::PassageArgs pa = sample_args(fs, s.m, seed);
+    pa.founder_rows = s.d_cells + at * s.m;
+    pa.founder_counts = s.d_headers + at;
+    pa.founder_stride = s.m;
+    return pa;
+}
+void set_share(const ecdna_ssa_ctx* c, ecdna::PassageArgs* pa, ecdna::ChunkIds ids, uint32_t waves) {
+    ids.reps_per_block = pass_reps_per_block(c, ids.n, waves);
+    pa->ids = ids;
+}
+
+// phase g's measurement, and (but for the last phase) the founders of the next
+int launch_passage_pass(const ecdna_ssa_ctx* c, const Chunk& ch, uint32_t g, const ecdna::FinalState& fs,
+                        const ecdna::ChunkIds& ids, const ecdna::StatsTarget& target, uint64_t seed_g, hipStream_t st) {
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t nb = (uint64_t)p.n_param_sets * p.hist_bins, n_run = std::max<uint64_t>(p.n_replicates, 1);
+    ecdna::PassageArgs pa = sample_args(fs, c->passage_m, seed_g);
     pa.target = target;
     pa.stats = c->d_pas_sample_stats + g * n_run + ch.first;
     pa.sample_hist = c->d_pas_sample_hist + g * nb;
     pa.founder_rows = g + 1u < c->n_passages ? c->d_founder_rows : nullptr;
     pa.founder_counts = c->d_founder_counts;
     pa.founder_stride = c->founder_stride;
-    pa.seed = seed_g;
-    pa.m = c->passage_m;
-    pa.table_slots = ecdna::subsample_table_slots(pa.m);
-    pa.sort_slots = ecdna::passage_sort_slots(pa.m);
-    ids.reps_per_block = pass_reps_per_block(
-        c, ch.n, ecdna::passage_waves(ids.bins, fs.bag_k, pa.table_slots, pa.sort_slots, nullptr));
-    pa.ids = ids;
-    TRY(ecdna::launch_passage(pa, pass_blocks(ids), st));
+    set_share(c, &pa, ids, ecdna::passage_waves(ids.bins, fs.bag_k, pa.table_slots, pa.sort_slots, nullptr));
+    TRY(ecdna::launch_passage(pa, pass_blocks(pa.ids), st));
     return ECDNA_OK;
 }
 
-// the chunk's kept samples, into the run's buffers (ssa_passage's KEEP instance: neither statistics nor a histogram)
-int launch_keep_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::FinalState& fs, ecdna::ChunkIds ids,
-                     hipStream_t st) {
-    ecdna::PassageArgs pa{};
-    pa.state = fs;
-    pa.founder_rows = c->d_kept_cells + ch.first * c->keep_m;
-    pa.founder_counts = c->d_kept_headers + ch.first;
-    pa.founder_stride = c->keep_m;
-    pa.seed = c->p.seed;
-    pa.m = c->keep_m;
-    pa.table_slots = ecdna::subsample_table_slots(pa.m);
-    pa.sort_slots = ecdna::passage_sort_slots(pa.m);
-    ids.reps_per_block = pass_reps_per_block(
-        c, ch.n, ecdna::keep_waves(ids.bins, fs.bag_k, pa.table_slots, pa.sort_slots, nullptr));
-    pa.ids = ids;
-    TRY(ecdna::launch_keep(pa, pass_blocks(ids), st));
+// the chunk's kept samples under `seed`, into slice `slice` of a store (ssa_passage's KEEP instance: neither statistics
+// nor a histogram). The keep block: slice 0 under the run's seed. The timepoint keep block of a passage run: phase g's
+// sample into slice g under the phase's key — the sample the passage pass measures and, but for the last phase, founds
+// the next phase with.
+int launch_keep_pass(const ecdna_ssa_ctx* c, const KeptStore& s, uint32_t slice, const Chunk& ch,
+                     const ecdna::FinalState& fs, const ecdna::ChunkIds& ids, uint64_t seed, hipStream_t st) {
+    ecdna::PassageArgs pa = keep_args(c, s, slice, ch, fs, seed);
+    set_share(c, &pa, ids, ecdna::keep_waves(ids.bins, fs.bag_k, pa.table_slots, pa.sort_slots, nullptr));
+    TRY(ecdna::launch_keep(pa, pass_blocks(pa.ids), st));
     return ECDNA_OK;
 }
 
-// phase g's kept sample of every replicate of the chunk, into slice g of the run's buffers (the KEEP instance under the
-// phase's key: the sample the passage pass measures and, but for the last phase, founds the next phase with)
-int launch_keep_phase_pass(const ecdna_ssa_ctx* c, const Chunk& ch, uint32_t g, const ecdna::FinalState& fs,
-                           ecdna::ChunkIds ids, uint64_t seed_g, hipStream_t st) {
-    const uint64_t n_run = std::max<uint64_t>(c->p.n_replicates, 1);
-    ecdna::PassageArgs pa{};
-    pa.state = fs;
-    pa.founder_rows = c->d_tk_cells + (g * n_run + ch.first) * c->tk_m;
-    pa.founder_counts = c->d_tk_headers + g * n_run + ch.first;
-    pa.founder_stride = c->tk_m;
-    pa.seed = seed_g;
-    pa.m = c->tk_m;
-    pa.table_slots = ecdna::subsample_table_slots(pa.m);
-    pa.sort_slots = ecdna::passage_sort_slots(pa.m);
-    ids.reps_per_block = pass_reps_per_block(
-        c, ch.n, ecdna::keep_waves(ids.bins, fs.bag_k, pa.table_slots, pa.sort_slots, nullptr));
-    pa.ids = ids;
-    TRY(ecdna::launch_keep(pa, pass_blocks(ids), st));
-    return ECDNA_OK;
-}
-
-// the kept samples of the chunk's snapshots, from the rows the stepper just saved, into the run's buffers (ssa_passage's
-// KEEP = 2 instance: one wave per (replicate, snapshot) pair)
-int launch_keep_snapshots_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::StepperArgs& a, ecdna::ChunkIds ids,
-                               hipStream_t st) {
-    ecdna::PassageArgs pa{};
-    pa.state = ecdna::FinalState{a.snap_rows, nullptr, a.snap_stride, nullptr, 0u, 0u};
-    pa.founder_rows = c->d_tk_cells + ch.first * c->tk_m;
-    pa.founder_counts = c->d_tk_headers + ch.first;
-    pa.founder_stride = c->tk_m;
-    pa.seed = c->p.seed;
-    pa.m = c->tk_m;
-    pa.table_slots = ecdna::subsample_table_slots(pa.m);
-    pa.sort_slots = ecdna::passage_sort_slots(pa.m);
+// the kept samples of the chunk's snapshots, from the rows the stepper just saved, into the timepoint keep block's store
+// (ssa_passage's KEEP = 2 instance: one wave per (replicate, snapshot) pair; snapshot s goes to slice s)
+int launch_keep_snapshots_pass(const ecdna_ssa_ctx* c, const Chunk& ch, const ecdna::StepperArgs& a,
+                               const ecdna::ChunkIds& ids, hipStream_t st) {
+    const ecdna::FinalState rows{a.snap_rows, nullptr, a.snap_stride, nullptr, 0u, 0u};
+    ecdna::PassageArgs pa = keep_args(c, c->kept_tp, 0u, ch, rows, c->p.seed);
     pa.snap_meta = a.snap_meta;
     pa.slice_stride = std::max<uint64_t>(c->p.n_replicates, 1);
     pa.n_snap = c->p.n_snapshots;
-    ids.reps_per_block = pass_reps_per_block(
-        c, ch.n, ecdna::keep_snapshots_waves(ids.bins, pa.table_slots, pa.sort_slots, nullptr));
-    pa.ids = ids;
-    TRY(ecdna::launch_keep_snapshots(pa, pass_blocks(ids), st));
+    set_share(c, &pa, ids, ecdna::keep_snapshots_waves(ids.bins, pa.table_slots, pa.sort_slots, nullptr));
+    TRY(ecdna::launch_keep_snapshots(pa, pass_blocks(pa.ids), st));
     return ECDNA_OK;
 }
 
@@ -1097,12 +1065,12 @@ int launch_chunk_phase(ecdna_ssa_ctx* c, size_t k, uint32_t g, hipStream_t st) {
     TRY(ecdna::launch_hist(h, pass_blocks(h.ids), st));
     if (p.subsample_cells) TRY(launch_subsample_pass(c, ch, fs, ids, target, st));
     if (c->n_cohort) TRY(launch_cohort_pass(c, ch, fs, ids, st));
-    if (c->keep_m) TRY(launch_keep_pass(c, ch, fs, ids, st));
+    if (c->kept.m) TRY(launch_keep_pass(c, c->kept, 0u, ch, fs, ids, p.seed, st));
     if (c->n_passages) TRY(launch_passage_pass(c, ch, g, fs, ids, target, a.seed, st));
     if (c->snap_stats) TRY(launch_snapstats_pass(c, ch, a, ids, st));
     // the timepoint keep block: phase g's sample, or the samples at the chunk's snapshots while their rows exist
-    if (c->tk_m && c->n_passages) TRY(launch_keep_phase_pass(c, ch, g, fs, ids, a.seed, st));
-    if (c->tk_m && c->snap_stats) TRY(launch_keep_snapshots_pass(c, ch, a, ids, st));
+    if (c->kept_tp.m && c->n_passages) TRY(launch_keep_pass(c, c->kept_tp, g, ch, fs, ids, a.seed, st));
+    if (c->kept_tp.m && c->snap_stats) TRY(launch_keep_snapshots_pass(c, ch, a, ids, st));
     TRY(hipEventRecord(ev[2], st));
     return ECDNA_OK;
 }
@@ -1183,25 +1151,25 @@ int accept_source(const ecdna_ssa_ctx* c, uint32_t source, AcceptSource* out) {
             break;
         }
         case ECDNA_ACCEPT_RESCORED:
-            if (!c->keep_m)
+            if (!c->kept.m)
                 return fail(ECDNA_E_STATE, "accept.source RESCORED: the rescored records need ecdna_ssa_ctx_create_keep");
-            if (!c->launched || !c->rescore_valid)
+            if (!c->launched || !c->kept.valid)
                 return fail(ECDNA_E_STATE, "accept.source RESCORED: no records before ecdna_ssa_ctx_rescore (a launch "
                                            "invalidates them)");
-            s.stats = static_cast<const ecdna_rep_stats_t*>(c->rs_stats.ptr);
-            s.T = c->rescore_targets;
+            s.stats = static_cast<const ecdna_rep_stats_t*>(c->kept.stats.ptr);
+            s.T = c->kept.targets;
             s.tp_stride = c->p.n_replicates;  // [P][n], as the cohort's
             s.has_target = true;
             break;
         case ECDNA_ACCEPT_RESCORED_TIMEPOINTS:
-            if (!c->tk_m)
+            if (!c->kept_tp.m)
                 return fail(ECDNA_E_STATE, "accept.source RESCORED_TIMEPOINTS: the rescored records need "
                                            "ecdna_ssa_ctx_create_keep_timepoints");
-            if (!c->launched || !c->tk_rescore_valid)
+            if (!c->launched || !c->kept_tp.valid)
                 return fail(ECDNA_E_STATE, "accept.source RESCORED_TIMEPOINTS: no records before "
                                            "ecdna_ssa_ctx_rescore_timepoints (a launch invalidates them)");
-            s.stats = static_cast<const ecdna_rep_stats_t*>(c->tk_stats.ptr);
-            s.T = c->tk_T;
+            s.stats = static_cast<const ecdna_rep_stats_t*>(c->kept_tp.stats.ptr);
+            s.T = c->kept_tp.T;
             s.tp_stride = n_run;  // [T][n]
             if (c->n_passages) {  // the passage sources' error rule: every participating phase's own summary
                 s.summaries = c->d_pas_summ;
@@ -1320,6 +1288,152 @@ int select_pass(ecdna_ssa_ctx* c, uint32_t source, const SelectSource& s, uint32
                         out_hist + ((uint64_t)x * K + j) * sel::kDigits);
     return ECDNA_OK;
 }
+
+// ---- the passes over a store of kept samples: what a call of the keep block (one slice) and its twin of the timepoint
+// keep block do after their own argument checks. Slice t of the buffers is a run of kept samples as the keep block's, so
+// each is the keep block's pass once per slice, on offset pointers. `who`: the calling entry point, for the messages ----
+
+// Slice t's samples against its P targets, target_hists [T][P][bins]: the store's records [T][P][n], enqueued on the
+// stream of the last launch.
+int rescore_store(ecdna_ssa_ctx* c, KeptStore* s, uint32_t P, const uint64_t* target_hists, const char* who) {
+    const uint32_t bins = c->p.hist_bins;
+    const uint64_t n = c->p.n_replicates, targets = (uint64_t)s->T * P;
+    TRY(hipSetDevice(c->device));
+    hipStream_t st = c->last_stream;
+    // an earlier rescore may still read the targets this one replaces (and its upload their host copies)
+    if (s->pending) TRY(hipStreamSynchronize(s->stream));
+    s->pending = false;
+    s->valid = false;
+    c->sel_keys_valid = false;  // (the select passes' keys may have been made from the records this call replaces)
+    TRY(accept_reserve(&s->stats, std::max<uint64_t>(n, 1) * targets * sizeof(ecdna_rep_stats_t), "records", who));
+    TRY(accept_reserve(&s->cdf, targets * bins * sizeof(double), "target CDFs", who));
+    TRY(accept_reserve(&s->scalars, targets * 3u * sizeof(double), "target scalars", who));
+    if (n) {
+        s->host_cdf.resize(targets * bins);
+        s->host_scalars.resize(targets * 3u);
+        summarize_targets(target_hists, targets, bins, s->host_cdf.data(), s->host_scalars.data());
+        TRY(hipMemcpyAsync(s->cdf.ptr, s->host_cdf.data(), s->host_cdf.size() * sizeof(double), hipMemcpyHostToDevice,
+                           st));
+        TRY(hipMemcpyAsync(s->scalars.ptr, s->host_scalars.data(), s->host_scalars.size() * sizeof(double),
+                           hipMemcpyHostToDevice, st));
+        s->pending = true;
+        s->stream = st;
+        for (uint64_t t = 0; t < s->T; ++t) {
+            ecdna::RescoreArgs a{};
+            a.headers = s->d_headers + t * n;
+            a.cells = s->d_cells + t * n * s->m;
+            a.out = static_cast<ecdna_rep_stats_t*>(s->stats.ptr) + t * P * n;
+            a.target_cdf = static_cast<const double*>(s->cdf.ptr) + t * P * bins;
+            a.target_scalars = static_cast<const double*>(s->scalars.ptr) + t * P * 3u;
+            a.n = (uint32_t)n;
+            a.m = s->m;
+            a.bins = bins;
+            a.n_targets = P;
+            a.reps_per_block = pass_reps_per_block(c, (uint32_t)n, ecdna::rescore_waves(bins, nullptr));
+            TRY(ecdna::launch_rescore(a, st));
+        }
+    }
+    s->targets = P;
+    s->valid = true;
+    return ECDNA_OK;
+}
+
+int download_rescored_store(ecdna_ssa_ctx* c, const KeptStore& s, ecdna_rep_stats_t* out) {
+    TRY(ctx_drain(c));
+    const uint64_t records = (uint64_t)s.T * s.targets * c->p.n_replicates;
+    if (out && records) TRY(to_host(out, static_cast<const ecdna_rep_stats_t*>(s.stats.ptr), records));
+    return ECDNA_OK;
+}
+
+// Per slice and global parameter set, the sum of the histograms of the samples accepted under row `threshold` of the
+// last accept: out_hist [T][sets][bins]. Synchronises.
+int pool_store(ecdna_ssa_ctx* c, const KeptStore& s, uint32_t threshold, uint64_t* out_hist, const char* who) {
+    const ecdna_ssa_params_t& p = c->p;
+    const uint64_t n = p.n_replicates, nb = (uint64_t)p.n_param_sets * p.hist_bins, T = s.T;
+    std::fill(out_hist, out_hist + T * nb, 0ull);
+    if (!n) return ECDNA_OK;
+    TRY(hipSetDevice(c->device));
+    hipStream_t st = c->last_stream;
+    TRY(accept_reserve(&c->pool_hist, T * nb * sizeof(uint64_t), "histogram", who));
+    TRY(hipMemsetAsync(c->pool_hist.ptr, 0, T * nb * sizeof(uint64_t), st));
+    for (uint64_t t = 0; t < T; ++t) {
+        ecdna::PoolAcceptedArgs a{};
+        a.headers = s.d_headers + t * n;
+        a.cells = s.d_cells + t * n * s.m;
+        a.mask = static_cast<const uint32_t*>(c->acc_mask.ptr);
+        a.hist = static_cast<unsigned long long*>(c->pool_hist.ptr) + t * nb;
+        a.rid0 = p.first_replicate;
+        a.rid_stride = rid_stride(p);
+        a.reps_per_set = p.reps_per_set;
+        a.n = (uint32_t)n;
+        a.m = s.m;
+        a.bins = p.hist_bins;
+        a.q = threshold;
+        // (the histogram pass's share: about one parameter set per workgroup in a sweep of small sets)
+        a.reps_per_block = hist_reps_per_block(c, (uint32_t)n, ecdna::kPoolBlock);
+        TRY(ecdna::launch_pool_accepted(a, st));
+    }
+    TRY(hipStreamSynchronize(st));
+    TRY(to_host(out_hist, static_cast<const uint64_t*>(c->pool_hist.ptr), T * nb));
+    return ECDNA_OK;
+}
+
+// The indices in the call, index [n_ids], of the replicates with the global `ids` (ids = NULL: none, the call's first
+// n_ids are meant). `name`: the calling entry point without its prefix, as the messages name its arguments.
+int kept_index(const ecdna_ssa_ctx* c, const std::string& name, uint64_t n_ids, const uint64_t* ids, uint32_t* index) {
+    const ecdna_ssa_params_t& p = c->p;
+    if (!ids && n_ids > p.n_replicates)
+        return fail(ECDNA_E_INVALID, name + ".n_ids must be <= n_replicates when ids is NULL");
+    for (uint64_t j = 0; ids && j < n_ids; ++j) {
+        uint64_t i = 0;
+        if (!ecdna::keep::index_of(ids[j], p.first_replicate, rid_stride(p), p.n_replicates, &i))
+            return fail(ECDNA_E_INVALID, name + ".ids[" + std::to_string(j) + "] = " + std::to_string(ids[j]) +
+                                             " is not a replicate of this call");
+        index[j] = (uint32_t)i;
+    }
+    return ECDNA_OK;
+}
+
+// Every slice's samples of the replicates at `index` (kept_index), gathered on the device in that order, slice by slice,
+// then copied once; index = NULL: the first n_ids samples of every slice. out_headers [T][n_ids], out_cells [T][n_ids][m].
+int download_kept_store(ecdna_ssa_ctx* c, const KeptStore& s, uint64_t n_ids, const uint32_t* index,
+                        ecdna_kept_t* out_headers, uint16_t* out_cells, const char* who) {
+    static_assert(sizeof(ecdna_kept_t) == sizeof(uint2), "a kept header is two u32 words");
+    if (!n_ids || (!out_headers && !out_cells)) return ECDNA_OK;
+    TRY(ctx_drain(c));
+    const uint64_t n = c->p.n_replicates, m = s.m, T = s.T;
+    if (index) {
+        TRY(accept_reserve(&c->gat_index, n_ids * sizeof(uint32_t), "index", who));
+        TRY(accept_reserve(&c->gat_headers, T * n_ids * sizeof(uint2), "headers", who));
+        TRY(accept_reserve(&c->gat_cells, T * n_ids * m * sizeof(uint16_t), "cells", who));
+        hipStream_t st = c->last_stream;
+        TRY(hipMemcpy(c->gat_index.ptr, index, n_ids * sizeof(uint32_t), hipMemcpyHostToDevice));
+        for (uint64_t t = 0; t < T; ++t) {
+            ecdna::KeptGatherArgs a{};
+            a.headers = s.d_headers + t * n;
+            a.cells = s.d_cells + t * n * m;
+            a.index = static_cast<const uint32_t*>(c->gat_index.ptr);
+            a.out_headers = static_cast<uint2*>(c->gat_headers.ptr) + t * n_ids;
+            a.out_cells = static_cast<uint16_t*>(c->gat_cells.ptr) + t * n_ids * m;
+            a.n_ids = (uint32_t)n_ids;
+            a.m = (uint32_t)m;
+            TRY(ecdna::launch_kept_gather(a, st));
+        }
+        TRY(hipStreamSynchronize(st));
+        if (out_headers)
+            TRY(hipMemcpy(out_headers, c->gat_headers.ptr, T * n_ids * sizeof(uint2), hipMemcpyDeviceToHost));
+        if (out_cells) TRY(to_host(out_cells, static_cast<const uint16_t*>(c->gat_cells.ptr), T * n_ids * m));
+        return ECDNA_OK;
+    }
+    for (uint64_t t = 0; t < T; ++t) {
+        if (out_headers)
+            TRY(hipMemcpy(out_headers + t * n_ids, s.d_headers + t * n, n_ids * sizeof(uint2), hipMemcpyDeviceToHost));
+        if (out_cells) TRY(to_host(out_cells + t * n_ids * m, s.d_cells + t * n * m, n_ids * m));
+    }
+    return ECDNA_OK;
+}
+
+const char* const kNeedsTimepoints = ": the kept timepoint samples need ecdna_ssa_ctx_create_keep_timepoints";
 }  // namespace
 
 // library-internal entry points for ssa_comm.cpp (the RCCL reduction)
@@ -1503,8 +1617,7 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
     c->launched = true;
     c->accept_valid = false;  // (the acceptance pass's results were the previous launch's)
     c->sel_keys_valid = false;  // (and the select passes' keys were made from its records)
-    c->rescore_valid = false;   // (and the rescored records from its kept samples)
-    c->tk_rescore_valid = false;
+    c->kept.valid = c->kept_tp.valid = false;  // (and the rescored records from its kept samples)
     return ECDNA_OK;
 }
 
@@ -1783,7 +1896,7 @@ int ecdna_ssa_ctx_accept(ecdna_ssa_ctx* c, const ecdna_ssa_accept_t* a) {
         k.err_stride = src.err_stride;
         k.tmask = a->timepoint_mask ? a->timepoint_mask : all;
         k.rid0 = p.first_replicate;
-        k.rid_stride = p.replicate_stride ? p.replicate_stride : 1u;
+        k.rid_stride = rid_stride(p);
         k.reps_per_set = p.reps_per_set;
         k.n = (uint32_t)n;
         k.T = src.T;
@@ -1841,314 +1954,95 @@ int ecdna_ssa_ctx_download_accept(ecdna_ssa_ctx* c, uint64_t* out_counts, uint32
     return ECDNA_OK;
 }
 
+// ---- the calls over the kept samples, of the keep block (ecdna_ssa_keep_t) and of the timepoint keep block
+// (ecdna_ssa_keep_timepoints_t): each checks its own arguments, in its own order and words, and runs the pass over its
+// block's store ----
+
 int ecdna_ssa_ctx_rescore(ecdna_ssa_ctx* c, uint32_t n_targets, const uint64_t* target_hists) {
-    const char* who = "ecdna_ssa_ctx_rescore";
     if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
     if (n_targets < 1u || n_targets > ecdna::kMaxCohortTargets)
         return fail(ECDNA_E_INVALID, "rescore.n_targets must be in [1, 64]");
     if (!target_hists) return fail(ECDNA_E_INVALID, "rescore.target_hists is NULL");
-    const ecdna_ssa_params_t& p = c->p;
-    const uint32_t bins = p.hist_bins, P = n_targets;
-    const uint32_t empty = first_empty_target(target_hists, P, bins);
-    if (empty < P) return fail(ECDNA_E_INVALID, "rescore.target_hists[" + std::to_string(empty) + "] is empty");
-    if (!c->keep_m) return fail(ECDNA_E_STATE, "rescore: the kept samples need ecdna_ssa_ctx_create_keep");
+    const uint32_t empty = first_empty_target(target_hists, n_targets, c->p.hist_bins);
+    if (empty < n_targets)
+        return fail(ECDNA_E_INVALID, "rescore.target_hists[" + std::to_string(empty) + "] is empty");
+    if (!c->kept.m) return fail(ECDNA_E_STATE, "rescore: the kept samples need ecdna_ssa_ctx_create_keep");
     TRY(ctx_launched(c, "rescore before launch"));
-    const uint64_t n = p.n_replicates;
-    TRY(hipSetDevice(c->device));
-    hipStream_t st = c->last_stream;
-    // an earlier rescore may still read the targets this one replaces (and its upload their host copies)
-    if (c->rescore_pending) TRY(hipStreamSynchronize(c->rescore_stream));
-    c->rescore_pending = false;
-    c->rescore_valid = false;
-    c->sel_keys_valid = false;  // (the select passes' keys may have been made from the records this call replaces)
-    TRY(accept_reserve(&c->rs_stats, std::max<uint64_t>(n, 1) * P * sizeof(ecdna_rep_stats_t), "records", who));
-    TRY(accept_reserve(&c->rs_cdf, (uint64_t)P * bins * sizeof(double), "target CDFs", who));
-    TRY(accept_reserve(&c->rs_scalars, (uint64_t)P * 3u * sizeof(double), "target scalars", who));
-    if (n) {
-        c->rs_cdf_host.resize((uint64_t)P * bins);
-        c->rs_scalars_host.resize((uint64_t)P * 3u);
-        summarize_targets(target_hists, P, bins, c->rs_cdf_host.data(), c->rs_scalars_host.data());
-        TRY(hipMemcpyAsync(c->rs_cdf.ptr, c->rs_cdf_host.data(), c->rs_cdf_host.size() * sizeof(double),
-                           hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(c->rs_scalars.ptr, c->rs_scalars_host.data(), c->rs_scalars_host.size() * sizeof(double),
-                           hipMemcpyHostToDevice, st));
-        c->rescore_pending = true;
-        c->rescore_stream = st;
-        ecdna::RescoreArgs a{};
-        a.headers = c->d_kept_headers;
-        a.cells = c->d_kept_cells;
-        a.out = static_cast<ecdna_rep_stats_t*>(c->rs_stats.ptr);
-        a.target_cdf = static_cast<const double*>(c->rs_cdf.ptr);
-        a.target_scalars = static_cast<const double*>(c->rs_scalars.ptr);
-        a.n = (uint32_t)n;
-        a.m = c->keep_m;
-        a.bins = bins;
-        a.n_targets = P;
-        a.reps_per_block = pass_reps_per_block(c, (uint32_t)n, ecdna::rescore_waves(bins, nullptr));
-        TRY(ecdna::launch_rescore(a, st));
-    }
-    c->rescore_targets = P;
-    c->rescore_valid = true;
-    return ECDNA_OK;
+    return rescore_store(c, &c->kept, n_targets, target_hists, "ecdna_ssa_ctx_rescore");
+}
+
+int ecdna_ssa_ctx_rescore_timepoints(ecdna_ssa_ctx* c, const uint64_t* target_hists) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!target_hists) return fail(ECDNA_E_INVALID, "rescore_timepoints.target_hists is NULL");
+    if (!c->kept_tp.m) return fail(ECDNA_E_STATE, std::string("rescore_timepoints") + kNeedsTimepoints);
+    const uint32_t T = c->kept_tp.T, empty = first_empty_target(target_hists, T, c->p.hist_bins);
+    if (empty < T)
+        return fail(ECDNA_E_INVALID, "rescore_timepoints.target_hists[" + std::to_string(empty) + "] is empty");
+    TRY(ctx_launched(c, "rescore_timepoints before launch"));
+    // timepoint t's samples against target t: one target per slice
+    return rescore_store(c, &c->kept_tp, 1u, target_hists, "ecdna_ssa_ctx_rescore_timepoints");
 }
 
 int ecdna_ssa_ctx_download_rescored(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out) {
     if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!c->keep_m) return fail(ECDNA_E_STATE, "download_rescored: the kept samples need ecdna_ssa_ctx_create_keep");
-    if (!c->launched || !c->rescore_valid)
+    if (!c->kept.m) return fail(ECDNA_E_STATE, "download_rescored: the kept samples need ecdna_ssa_ctx_create_keep");
+    if (!c->launched || !c->kept.valid)
         return fail(ECDNA_E_STATE, "download_rescored before rescore (a launch invalidates the rescored records)");
-    TRY(ctx_drain(c));
-    const uint64_t records = (uint64_t)c->rescore_targets * c->p.n_replicates;
-    if (out && records) TRY(to_host(out, static_cast<const ecdna_rep_stats_t*>(c->rs_stats.ptr), records));
-    return ECDNA_OK;
+    return download_rescored_store(c, c->kept, out);
+}
+
+int ecdna_ssa_ctx_download_rescored_timepoints(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!c->kept_tp.m) return fail(ECDNA_E_STATE, std::string("download_rescored_timepoints") + kNeedsTimepoints);
+    if (!c->launched || !c->kept_tp.valid)
+        return fail(ECDNA_E_STATE, "download_rescored_timepoints before rescore_timepoints (a launch invalidates the "
+                                   "rescored records; ecdna_ssa_ctx_create_keep_timepoints)");
+    return download_rescored_store(c, c->kept_tp, out);
 }
 
 int ecdna_ssa_ctx_pool_accepted(ecdna_ssa_ctx* c, uint32_t threshold, uint64_t* out_hist) {
     if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
     if (!out_hist) return fail(ECDNA_E_INVALID, "pool_accepted.out_hist is NULL");
-    if (!c->keep_m) return fail(ECDNA_E_STATE, "pool_accepted: the kept samples need ecdna_ssa_ctx_create_keep");
+    if (!c->kept.m) return fail(ECDNA_E_STATE, "pool_accepted: the kept samples need ecdna_ssa_ctx_create_keep");
     if (!c->launched || !c->accept_valid)
         return fail(ECDNA_E_STATE, "pool_accepted before accept (a launch invalidates the acceptance results)");
     if (threshold >= c->acc_rows)
         return fail(ECDNA_E_INVALID, "pool_accepted.threshold must be < n_thresholds of the last accept");
-    const ecdna_ssa_params_t& p = c->p;
-    const uint64_t n = p.n_replicates, nb = (uint64_t)p.n_param_sets * p.hist_bins;
-    std::fill(out_hist, out_hist + nb, 0ull);
-    if (!n) return ECDNA_OK;
-    TRY(hipSetDevice(c->device));
-    hipStream_t st = c->last_stream;
-    TRY(accept_reserve(&c->pool_hist, nb * sizeof(uint64_t), "histogram", "ecdna_ssa_ctx_pool_accepted"));
-    TRY(hipMemsetAsync(c->pool_hist.ptr, 0, nb * sizeof(uint64_t), st));
-    ecdna::PoolAcceptedArgs a{};
-    a.headers = c->d_kept_headers;
-    a.cells = c->d_kept_cells;
-    a.mask = static_cast<const uint32_t*>(c->acc_mask.ptr);
-    a.hist = static_cast<unsigned long long*>(c->pool_hist.ptr);
-    a.rid0 = p.first_replicate;
-    a.rid_stride = p.replicate_stride ? p.replicate_stride : 1u;
-    a.reps_per_set = p.reps_per_set;
-    a.n = (uint32_t)n;
-    a.m = c->keep_m;
-    a.bins = p.hist_bins;
-    a.q = threshold;
-    // (the histogram pass's share: about one parameter set per workgroup in a sweep of small sets)
-    const uint64_t set_local = std::max<uint64_t>(1, p.reps_per_set / a.rid_stride);
-    a.reps_per_block = pass_reps_per_block(
-        c, (uint32_t)n, (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(ecdna::kPoolBlock, set_local)));
-    TRY(ecdna::launch_pool_accepted(a, st));
-    TRY(hipStreamSynchronize(st));
-    TRY(to_host(out_hist, static_cast<const uint64_t*>(c->pool_hist.ptr), nb));
-    return ECDNA_OK;
-}
-
-int ecdna_ssa_ctx_download_kept(ecdna_ssa_ctx* c, uint64_t n_ids, const uint64_t* ids, ecdna_kept_t* out_headers,
-                                uint16_t* out_cells) {
-    static_assert(sizeof(ecdna_kept_t) == sizeof(uint2), "a kept header is two u32 words");
-    const char* who = "ecdna_ssa_ctx_download_kept";
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    const ecdna_ssa_params_t& p = c->p;
-    const uint64_t n = p.n_replicates, stride = p.replicate_stride ? p.replicate_stride : 1u;
-    if (!ids && n_ids > n) return fail(ECDNA_E_INVALID, "download_kept.n_ids must be <= n_replicates when ids is NULL");
-    std::vector<uint32_t> index(ids ? n_ids : 0);
-    for (uint64_t j = 0; ids && j < n_ids; ++j) {
-        uint64_t i = 0;
-        if (!ecdna::keep::index_of(ids[j], p.first_replicate, stride, n, &i))
-            return fail(ECDNA_E_INVALID, "download_kept.ids[" + std::to_string(j) + "] = " + std::to_string(ids[j]) +
-                                             " is not a replicate of this call");
-        index[j] = (uint32_t)i;
-    }
-    if (!c->keep_m) return fail(ECDNA_E_STATE, "download_kept: the kept samples need ecdna_ssa_ctx_create_keep");
-    TRY(ctx_launched(c));
-    if (!n_ids || (!out_headers && !out_cells)) return ECDNA_OK;
-    TRY(ctx_drain(c));
-    const uint64_t m = c->keep_m;
-    const uint2* d_headers = c->d_kept_headers;
-    const uint16_t* d_cells = c->d_kept_cells;
-    if (ids) {  // gathered on the device in the order of ids
-        TRY(accept_reserve(&c->gat_index, n_ids * sizeof(uint32_t), "index", who));
-        TRY(accept_reserve(&c->gat_headers, n_ids * sizeof(uint2), "headers", who));
-        TRY(accept_reserve(&c->gat_cells, n_ids * m * sizeof(uint16_t), "cells", who));
-        hipStream_t st = c->last_stream;
-        TRY(hipMemcpy(c->gat_index.ptr, index.data(), n_ids * sizeof(uint32_t), hipMemcpyHostToDevice));
-        ecdna::KeptGatherArgs a{};
-        a.headers = d_headers;
-        a.cells = d_cells;
-        a.index = static_cast<const uint32_t*>(c->gat_index.ptr);
-        a.out_headers = static_cast<uint2*>(c->gat_headers.ptr);
-        a.out_cells = static_cast<uint16_t*>(c->gat_cells.ptr);
-        a.n_ids = (uint32_t)n_ids;
-        a.m = (uint32_t)m;
-        TRY(ecdna::launch_kept_gather(a, st));
-        TRY(hipStreamSynchronize(st));
-        d_headers = a.out_headers;
-        d_cells = a.out_cells;
-    }
-    if (out_headers) TRY(hipMemcpy(out_headers, d_headers, n_ids * sizeof(uint2), hipMemcpyDeviceToHost));
-    if (out_cells) TRY(to_host(out_cells, d_cells, n_ids * m));
-    return ECDNA_OK;
-}
-
-// ---- the calls over the kept samples of every timepoint (ecdna_ssa_keep_timepoints_t): slice t of the buffers is a run
-// of kept samples as the keep block's, so each call is the keep block's pass once per timepoint, on offset pointers ----
-
-namespace {
-const char* const kNeedsTimepoints = ": the kept timepoint samples need ecdna_ssa_ctx_create_keep_timepoints";
-}
-
-int ecdna_ssa_ctx_rescore_timepoints(ecdna_ssa_ctx* c, const uint64_t* target_hists) {
-    const char* who = "ecdna_ssa_ctx_rescore_timepoints";
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!target_hists) return fail(ECDNA_E_INVALID, "rescore_timepoints.target_hists is NULL");
-    if (!c->tk_m) return fail(ECDNA_E_STATE, std::string("rescore_timepoints") + kNeedsTimepoints);
-    const ecdna_ssa_params_t& p = c->p;
-    const uint32_t bins = p.hist_bins, T = c->tk_T;
-    const uint32_t empty = first_empty_target(target_hists, T, bins);
-    if (empty < T)
-        return fail(ECDNA_E_INVALID, "rescore_timepoints.target_hists[" + std::to_string(empty) + "] is empty");
-    TRY(ctx_launched(c, "rescore_timepoints before launch"));
-    const uint64_t n = p.n_replicates;
-    TRY(hipSetDevice(c->device));
-    hipStream_t st = c->last_stream;
-    // an earlier call may still read the targets this one replaces (and its upload their host copies)
-    if (c->tk_rescore_pending) TRY(hipStreamSynchronize(c->tk_rescore_stream));
-    c->tk_rescore_pending = false;
-    c->tk_rescore_valid = false;
-    c->sel_keys_valid = false;  // (the select passes' keys may have been made from the records this call replaces)
-    TRY(accept_reserve(&c->tk_stats, std::max<uint64_t>(n, 1) * T * sizeof(ecdna_rep_stats_t), "records", who));
-    TRY(accept_reserve(&c->tk_cdf, (uint64_t)T * bins * sizeof(double), "target CDFs", who));
-    TRY(accept_reserve(&c->tk_scalars, (uint64_t)T * 3u * sizeof(double), "target scalars", who));
-    if (n) {
-        c->tk_cdf_host.resize((uint64_t)T * bins);
-        c->tk_scalars_host.resize((uint64_t)T * 3u);
-        summarize_targets(target_hists, T, bins, c->tk_cdf_host.data(), c->tk_scalars_host.data());
-        TRY(hipMemcpyAsync(c->tk_cdf.ptr, c->tk_cdf_host.data(), c->tk_cdf_host.size() * sizeof(double),
-                           hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(c->tk_scalars.ptr, c->tk_scalars_host.data(), c->tk_scalars_host.size() * sizeof(double),
-                           hipMemcpyHostToDevice, st));
-        c->tk_rescore_pending = true;
-        c->tk_rescore_stream = st;
-        for (uint64_t t = 0; t < T; ++t) {  // timepoint t's samples against target t: ssa_rescore with one target
-            ecdna::RescoreArgs a{};
-            a.headers = c->d_tk_headers + t * n;
-            a.cells = c->d_tk_cells + t * n * c->tk_m;
-            a.out = static_cast<ecdna_rep_stats_t*>(c->tk_stats.ptr) + t * n;
-            a.target_cdf = static_cast<const double*>(c->tk_cdf.ptr) + t * bins;
-            a.target_scalars = static_cast<const double*>(c->tk_scalars.ptr) + t * 3u;
-            a.n = (uint32_t)n;
-            a.m = c->tk_m;
-            a.bins = bins;
-            a.n_targets = 1u;
-            a.reps_per_block = pass_reps_per_block(c, (uint32_t)n, ecdna::rescore_waves(bins, nullptr));
-            TRY(ecdna::launch_rescore(a, st));
-        }
-    }
-    c->tk_rescore_valid = true;
-    return ECDNA_OK;
-}
-
-int ecdna_ssa_ctx_download_rescored_timepoints(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out) {
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!c->tk_m) return fail(ECDNA_E_STATE, std::string("download_rescored_timepoints") + kNeedsTimepoints);
-    if (!c->launched || !c->tk_rescore_valid)
-        return fail(ECDNA_E_STATE, "download_rescored_timepoints before rescore_timepoints (a launch invalidates the "
-                                   "rescored records; ecdna_ssa_ctx_create_keep_timepoints)");
-    TRY(ctx_drain(c));
-    const uint64_t records = (uint64_t)c->tk_T * c->p.n_replicates;
-    if (out && records) TRY(to_host(out, static_cast<const ecdna_rep_stats_t*>(c->tk_stats.ptr), records));
-    return ECDNA_OK;
+    return pool_store(c, c->kept, threshold, out_hist, "ecdna_ssa_ctx_pool_accepted");
 }
 
 int ecdna_ssa_ctx_pool_accepted_timepoints(ecdna_ssa_ctx* c, uint32_t threshold, uint64_t* out_hist) {
     if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
     if (!out_hist) return fail(ECDNA_E_INVALID, "pool_accepted_timepoints.out_hist is NULL");
-    if (!c->tk_m) return fail(ECDNA_E_STATE, std::string("pool_accepted_timepoints") + kNeedsTimepoints);
+    if (!c->kept_tp.m) return fail(ECDNA_E_STATE, std::string("pool_accepted_timepoints") + kNeedsTimepoints);
     if (!c->launched || !c->accept_valid)
         return fail(ECDNA_E_STATE, "pool_accepted_timepoints before accept (a launch invalidates the acceptance results; "
                                    "ecdna_ssa_ctx_create_keep_timepoints)");
     if (threshold >= c->acc_rows)
         return fail(ECDNA_E_INVALID, "pool_accepted_timepoints.threshold must be < n_thresholds of the last accept");
-    const ecdna_ssa_params_t& p = c->p;
-    const uint64_t n = p.n_replicates, nb = (uint64_t)p.n_param_sets * p.hist_bins, T = c->tk_T;
-    std::fill(out_hist, out_hist + T * nb, 0ull);
-    if (!n) return ECDNA_OK;
-    TRY(hipSetDevice(c->device));
-    hipStream_t st = c->last_stream;
-    TRY(accept_reserve(&c->pool_hist, T * nb * sizeof(uint64_t), "histogram", "ecdna_ssa_ctx_pool_accepted_timepoints"));
-    TRY(hipMemsetAsync(c->pool_hist.ptr, 0, T * nb * sizeof(uint64_t), st));
-    for (uint64_t t = 0; t < T; ++t) {
-        ecdna::PoolAcceptedArgs a{};
-        a.headers = c->d_tk_headers + t * n;
-        a.cells = c->d_tk_cells + t * n * c->tk_m;
-        a.mask = static_cast<const uint32_t*>(c->acc_mask.ptr);
-        a.hist = static_cast<unsigned long long*>(c->pool_hist.ptr) + t * nb;
-        a.rid0 = p.first_replicate;
-        a.rid_stride = p.replicate_stride ? p.replicate_stride : 1u;
-        a.reps_per_set = p.reps_per_set;
-        a.n = (uint32_t)n;
-        a.m = c->tk_m;
-        a.bins = p.hist_bins;
-        a.q = threshold;
-        // (ecdna_ssa_ctx_pool_accepted's share)
-        const uint64_t set_local = std::max<uint64_t>(1, p.reps_per_set / a.rid_stride);
-        a.reps_per_block = pass_reps_per_block(
-            c, (uint32_t)n, (uint32_t)std::max<uint64_t>(4, std::min<uint64_t>(ecdna::kPoolBlock, set_local)));
-        TRY(ecdna::launch_pool_accepted(a, st));
-    }
-    TRY(hipStreamSynchronize(st));
-    TRY(to_host(out_hist, static_cast<const uint64_t*>(c->pool_hist.ptr), T * nb));
-    return ECDNA_OK;
+    return pool_store(c, c->kept_tp, threshold, out_hist, "ecdna_ssa_ctx_pool_accepted_timepoints");
+}
+
+int ecdna_ssa_ctx_download_kept(ecdna_ssa_ctx* c, uint64_t n_ids, const uint64_t* ids, ecdna_kept_t* out_headers,
+                                uint16_t* out_cells) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    std::vector<uint32_t> index(ids ? n_ids : 0);
+    TRY(kept_index(c, "download_kept", n_ids, ids, index.data()));
+    if (!c->kept.m) return fail(ECDNA_E_STATE, "download_kept: the kept samples need ecdna_ssa_ctx_create_keep");
+    TRY(ctx_launched(c));
+    return download_kept_store(c, c->kept, n_ids, ids ? index.data() : nullptr, out_headers, out_cells,
+                               "ecdna_ssa_ctx_download_kept");
 }
 
 int ecdna_ssa_ctx_download_kept_timepoints(ecdna_ssa_ctx* c, uint64_t n_ids, const uint64_t* ids,
                                            ecdna_kept_t* out_headers, uint16_t* out_cells) {
-    const char* who = "ecdna_ssa_ctx_download_kept_timepoints";
     if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    const ecdna_ssa_params_t& p = c->p;
-    const uint64_t n = p.n_replicates, stride = p.replicate_stride ? p.replicate_stride : 1u;
-    if (!ids && n_ids > n)
-        return fail(ECDNA_E_INVALID, "download_kept_timepoints.n_ids must be <= n_replicates when ids is NULL");
     std::vector<uint32_t> index(ids ? n_ids : 0);
-    for (uint64_t j = 0; ids && j < n_ids; ++j) {
-        uint64_t i = 0;
-        if (!ecdna::keep::index_of(ids[j], p.first_replicate, stride, n, &i))
-            return fail(ECDNA_E_INVALID, "download_kept_timepoints.ids[" + std::to_string(j) + "] = " +
-                                             std::to_string(ids[j]) + " is not a replicate of this call");
-        index[j] = (uint32_t)i;
-    }
-    if (!c->tk_m) return fail(ECDNA_E_STATE, std::string("download_kept_timepoints") + kNeedsTimepoints);
+    TRY(kept_index(c, "download_kept_timepoints", n_ids, ids, index.data()));
+    if (!c->kept_tp.m) return fail(ECDNA_E_STATE, std::string("download_kept_timepoints") + kNeedsTimepoints);
     TRY(ctx_launched(c, "download_kept_timepoints before launch (ecdna_ssa_ctx_create_keep_timepoints)"));
-    if (!n_ids || (!out_headers && !out_cells)) return ECDNA_OK;
-    TRY(ctx_drain(c));
-    const uint64_t m = c->tk_m, T = c->tk_T;
-    if (ids) {  // gathered on the device in the order of ids, timepoint by timepoint, then copied once
-        TRY(accept_reserve(&c->gat_index, n_ids * sizeof(uint32_t), "index", who));
-        TRY(accept_reserve(&c->gat_headers, T * n_ids * sizeof(uint2), "headers", who));
-        TRY(accept_reserve(&c->gat_cells, T * n_ids * m * sizeof(uint16_t), "cells", who));
-        hipStream_t st = c->last_stream;
-        TRY(hipMemcpy(c->gat_index.ptr, index.data(), n_ids * sizeof(uint32_t), hipMemcpyHostToDevice));
-        for (uint64_t t = 0; t < T; ++t) {
-            ecdna::KeptGatherArgs a{};
-            a.headers = c->d_tk_headers + t * n;
-            a.cells = c->d_tk_cells + t * n * m;
-            a.index = static_cast<const uint32_t*>(c->gat_index.ptr);
-            a.out_headers = static_cast<uint2*>(c->gat_headers.ptr) + t * n_ids;
-            a.out_cells = static_cast<uint16_t*>(c->gat_cells.ptr) + t * n_ids * m;
-            a.n_ids = (uint32_t)n_ids;
-            a.m = (uint32_t)m;
-            TRY(ecdna::launch_kept_gather(a, st));
-        }
-        TRY(hipStreamSynchronize(st));
-        if (out_headers)
-            TRY(hipMemcpy(out_headers, c->gat_headers.ptr, T * n_ids * sizeof(uint2), hipMemcpyDeviceToHost));
-        if (out_cells) TRY(to_host(out_cells, static_cast<const uint16_t*>(c->gat_cells.ptr), T * n_ids * m));
-        return ECDNA_OK;
-    }
-    for (uint64_t t = 0; t < T; ++t) {  // the first n_ids samples of every slice
-        if (out_headers)
-            TRY(hipMemcpy(out_headers + t * n_ids, c->d_tk_headers + t * n, n_ids * sizeof(uint2), hipMemcpyDeviceToHost));
-        if (out_cells) TRY(to_host(out_cells + t * n_ids * m, c->d_tk_cells + t * n * m, n_ids * m));
-    }
-    return ECDNA_OK;
+    return download_kept_store(c, c->kept_tp, n_ids, ids ? index.data() : nullptr, out_headers, out_cells,
+                               "ecdna_ssa_ctx_download_kept_timepoints");
 }
 
 int ecdna_ssa_ctx_select_digits(ecdna_ssa_ctx* c, uint32_t source, uint64_t timepoint_mask, uint32_t pass,

@@ -222,6 +222,18 @@ def _check(rc: int, what: str):
                           f"{L.ecdna_ssa_last_error_message().decode()}")
 
 
+def _lib_with(symbol: str, what: str):
+    """The library, which must export `symbol`: an entry point added within an ABI version, with `what` it brought."""
+    if not hasattr(lib(), symbol):
+        raise EngineError(f"{LIB_PATH} predates {symbol} ({what})")
+    return lib()
+
+
+def _check_u32(name: str, v):
+    if not (0 <= int(v) < (1 << 32)):
+        raise ValueError(f"{name} = {v} does not fit the ABI's u32 field")
+
+
 def device_count() -> int:
     return lib().ecdna_ssa_device_count()
 
@@ -406,31 +418,20 @@ class Context:
                 C.byref(self.params), ref(self.ext), ref(self.passages), ref(self.cohort), ref(self.keep),
                 C.byref(self.keep_timepoints), C.byref(h)), "ecdna_ssa_ctx_create_keep_timepoints")
         elif self.keep is not None:  # (only a spec that asks for kept samples goes through _keep)
-            if not hasattr(lib(), "ecdna_ssa_ctx_create_keep"):
-                raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_keep (kept samples)")
-            _check(lib().ecdna_ssa_ctx_create_keep(C.byref(self.params), ref(self.ext), ref(self.passages),
-                                                   ref(self.cohort), C.byref(self.keep), C.byref(h)),
-                   "ecdna_ssa_ctx_create_keep")
+            _check(self._keep_lib().ecdna_ssa_ctx_create_keep(
+                C.byref(self.params), ref(self.ext), ref(self.passages), ref(self.cohort), C.byref(self.keep),
+                C.byref(h)), "ecdna_ssa_ctx_create_keep")
         elif self.cohort is not None:  # (only a spec that asks for a cohort goes through _cohort)
-            if not hasattr(lib(), "ecdna_ssa_ctx_create_cohort"):
-                raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_cohort (a cohort of targets)")
-            _check(lib().ecdna_ssa_ctx_create_cohort(C.byref(self.params),
-                                                     C.byref(self.ext) if self.ext is not None else None,
-                                                     C.byref(self.passages) if self.passages is not None else None,
-                                                     C.byref(self.cohort), C.byref(h)),
-                   "ecdna_ssa_ctx_create_cohort")
+            _check(_lib_with("ecdna_ssa_ctx_create_cohort", "a cohort of targets").ecdna_ssa_ctx_create_cohort(
+                C.byref(self.params), ref(self.ext), ref(self.passages), C.byref(self.cohort), C.byref(h)),
+                "ecdna_ssa_ctx_create_cohort")
         elif self.passages is not None:  # (only a spec that asks for passages goes through _passages)
-            if not hasattr(lib(), "ecdna_ssa_ctx_create_passages"):
-                raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_passages (serial passaging)")
-            _check(lib().ecdna_ssa_ctx_create_passages(C.byref(self.params),
-                                                       C.byref(self.ext) if self.ext is not None else None,
-                                                       C.byref(self.passages), C.byref(h)),
-                   "ecdna_ssa_ctx_create_passages")
+            _check(_lib_with("ecdna_ssa_ctx_create_passages", "serial passaging").ecdna_ssa_ctx_create_passages(
+                C.byref(self.params), ref(self.ext), C.byref(self.passages), C.byref(h)),
+                "ecdna_ssa_ctx_create_passages")
         elif self.ext is not None:  # (only a spec that asks for the extension goes through _ext)
-            if not hasattr(lib(), "ecdna_ssa_ctx_create_ext"):
-                raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_ext (per-snapshot statistics)")
-            _check(lib().ecdna_ssa_ctx_create_ext(C.byref(self.params), C.byref(self.ext), C.byref(h)),
-                   "ecdna_ssa_ctx_create_ext")
+            _check(_lib_with("ecdna_ssa_ctx_create_ext", "per-snapshot statistics").ecdna_ssa_ctx_create_ext(
+                C.byref(self.params), C.byref(self.ext), C.byref(h)), "ecdna_ssa_ctx_create_ext")
         else:
             _check(lib().ecdna_ssa_ctx_create(C.byref(self.params), C.byref(h)), "ecdna_ssa_ctx_create")
         self.h = h
@@ -497,8 +498,7 @@ class Context:
                        list_capacity: int = 0):
         """Enqueue the acceptance pass on the stream of the last launch (ecdna_ssa_ctx_accept); download_accept
         returns its results. Arguments as accept()."""
-        if not hasattr(lib(), "ecdna_ssa_ctx_accept"):
-            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_accept (ABC rejection on the GPU)")
+        _lib_with("ecdna_ssa_ctx_accept", "ABC rejection on the GPU")
         thr = np.ascontiguousarray(thresholds, dtype=np.float64)
         if thr.ndim != 2 or thr.shape[1] != 4:
             raise ValueError("thresholds must be [Q][4]: ks, mean_rel, entropy_rel, frequency_diff per row")
@@ -548,11 +548,9 @@ class Context:
         (ranks >= 1), or those at `fractions` in (0, 1] of the population, of each of the four distances among the
         error-free replicates of `source` (an abi.ACCEPT_* constant), the maximum over `timepoints` (None: all) standing
         for a replicate. accept() with a finite value as the one threshold accepts exactly its counts_le replicates."""
-        if not hasattr(lib(), "ecdna_ssa_ctx_select"):
-            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_select (ABC thresholds on the GPU)")
+        _lib_with("ecdna_ssa_ctx_select", "ABC thresholds on the GPU")
         rk, fr = select_ranks(ranks, fractions)
-        if not (0 <= int(source) < (1 << 32)):
-            raise ValueError(f"source = {source} does not fit the ABI's u32 field")
+        _check_u32("source", source)
         K = len(rk) if rk is not None else len(fr)
         s = abi.Select(struct_size=C.sizeof(abi.Select), source=int(source), timepoint_mask=timepoint_mask(timepoints),
                        n_ranks=K)
@@ -572,15 +570,13 @@ class Context:
         """One pass of the select on this context's replicates (ecdna_ssa_ctx_select_digits), the shard primitive:
         `prefixes` [4][K] u64 keys (shard.SelectWalk.prefixes), the result [4][K][256] u64: per distance and prefix, the
         population's keys that share the prefix's top 8 * pass_ bits, counted by their next 8 bits. Shards' arrays sum."""
-        if not hasattr(lib(), "ecdna_ssa_ctx_select_digits"):
-            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_select_digits (ABC thresholds on the GPU)")
+        _lib_with("ecdna_ssa_ctx_select_digits", "ABC thresholds on the GPU")
         pre = np.ascontiguousarray(prefixes, dtype=np.uint64)
         if pre.ndim != 2 or pre.shape[0] != 4 or not (1 <= pre.shape[1] <= abi.SELECT_MAX_RANKS):
             raise ValueError(f"prefixes must be [4][K], K in 1 .. {abi.SELECT_MAX_RANKS}")
         if not (0 <= int(pass_) < abi.SELECT_PASSES):
             raise ValueError(f"pass_ = {pass_} must be in 0 .. {abi.SELECT_PASSES - 1}")
-        if not (0 <= int(source) < (1 << 32)):
-            raise ValueError(f"source = {source} does not fit the ABI's u32 field")
+        _check_u32("source", source)
         hist = np.zeros((4, pre.shape[1], 256), dtype=np.uint64)
         _check(lib().ecdna_ssa_ctx_select_digits(self.h, int(source), timepoint_mask(timepoints), int(pass_),
                                                  pre.shape[1], pre.ctypes.data, hist.ctypes.data),
@@ -589,8 +585,7 @@ class Context:
 
     def download_cohort(self) -> CohortResult:
         """The cohort records of the last launch (ecdna_ssa_ctx_download_cohort): stats and sample_stats [P][n]."""
-        if not hasattr(lib(), "ecdna_ssa_ctx_download_cohort"):
-            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_download_cohort (a cohort of targets)")
+        _lib_with("ecdna_ssa_ctx_download_cohort", "a cohort of targets")
         if self.cohort is None:  # (the library refuses: ECDNA_E_STATE)
             _check(lib().ecdna_ssa_ctx_download_cohort(self.h, None, None), "ecdna_ssa_ctx_download_cohort")
             raise EngineError("ecdna_ssa_ctx_download_cohort: the context has no cohort block")
@@ -601,10 +596,41 @@ class Context:
                "ecdna_ssa_ctx_download_cohort")
         return CohortResult(st, sst)
 
-    def _keep_lib(self):
-        if not hasattr(lib(), "ecdna_ssa_ctx_create_keep"):
-            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_keep (kept samples)")
-        return lib()
+    # What the calls of the keep block and their twins of the timepoint keep block share: the library with the block's
+    # entry points, a pooled histogram with a leading axis of T slices, and a download of kept samples with the leading
+    # axes `lead` (none, or T).
+    @staticmethod
+    def _keep_lib():
+        return _lib_with("ecdna_ssa_ctx_create_keep", "kept samples")
+
+    @staticmethod
+    def _keep_timepoints_lib():
+        return _lib_with("ecdna_ssa_ctx_create_keep_timepoints", "kept timepoint samples")
+
+    def _pool_accepted(self, get_lib, name: str, T: int, threshold: int) -> np.ndarray:
+        _check_u32("threshold", threshold)
+        p = self.params
+        out = np.zeros((max(T, 1), p.n_param_sets, p.hist_bins), dtype=np.uint64)
+        _check(getattr(get_lib(), name)(self.h, int(threshold), out.ctypes.data), name)
+        return out[:T]
+
+    def _download_kept(self, get_lib, name: str, lead: tuple, m: int, ids, count):
+        if ids is not None:
+            if count is not None:
+                raise ValueError("give ids or count, not both")
+            idv = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+            k = len(idv)
+        else:
+            idv = None
+            k = int(self.params.n_replicates) if count is None else int(count)
+            if not (0 <= k < (1 << 64)):
+                raise ValueError(f"count = {count} does not fit the ABI's u64 field")
+        headers = np.zeros(lead + (k,), dtype=abi.KEPT_DTYPE)
+        cells = np.zeros(lead + (k, m), dtype=np.uint16)
+        _check(getattr(get_lib(), name)(self.h, k, idv.ctypes.data if idv is not None and k else None,
+                                        headers.ctypes.data if headers.size else None,
+                                        cells.ctypes.data if cells.size else None), name)
+        return headers, cells
 
     def rescore_enqueue(self, targets):
         """Enqueue the late scoring of the kept samples against `targets` [P][hist_bins] on the stream of the last
@@ -637,13 +663,7 @@ class Context:
         """The posterior predictive histogram (ecdna_ssa_ctx_pool_accepted): per global parameter set, the sum of the
         kept samples' histograms of the replicates the last accept() accepted under row `threshold`,
         [n_param_sets][hist_bins] u64. Shards' arrays sum to the whole run's."""
-        if not (0 <= int(threshold) < (1 << 32)):
-            raise ValueError(f"threshold = {threshold} does not fit the ABI's u32 field")
-        p = self.params
-        out = np.zeros((p.n_param_sets, p.hist_bins), dtype=np.uint64)
-        _check(self._keep_lib().ecdna_ssa_ctx_pool_accepted(self.h, int(threshold), out.ctypes.data),
-               "ecdna_ssa_ctx_pool_accepted")
-        return out
+        return self._pool_accepted(self._keep_lib, "ecdna_ssa_ctx_pool_accepted", 1, threshold)[0]
 
     def download_kept(self, ids=None, count: Optional[int] = None):
         """Kept samples of the last launch (ecdna_ssa_ctx_download_kept): (headers [k] abi.KEPT_DTYPE, cells
@@ -651,28 +671,7 @@ class Context:
         come), or of the call's first `count` replicates (default: all). cells[j][:headers[j]["nplus"]] are the N+
         cells' true copy numbers, ascending; the rest of a row is unspecified."""
         m = int(self.keep.keep_cells) if self.keep is not None else 0
-        if ids is not None:
-            if count is not None:
-                raise ValueError("give ids or count, not both")
-            idv = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
-            k = len(idv)
-        else:
-            idv = None
-            k = int(self.params.n_replicates) if count is None else int(count)
-            if not (0 <= k < (1 << 64)):
-                raise ValueError(f"count = {count} does not fit the ABI's u64 field")
-        headers = np.zeros(k, dtype=abi.KEPT_DTYPE)
-        cells = np.zeros((k, m), dtype=np.uint16)
-        _check(self._keep_lib().ecdna_ssa_ctx_download_kept(self.h, k, idv.ctypes.data if idv is not None and k else None,
-                                                            headers.ctypes.data if k else None,
-                                                            cells.ctypes.data if cells.size else None),
-               "ecdna_ssa_ctx_download_kept")
-        return headers, cells
-
-    def _keep_timepoints_lib(self):
-        if not hasattr(lib(), "ecdna_ssa_ctx_create_keep_timepoints"):
-            raise EngineError(f"{LIB_PATH} predates ecdna_ssa_ctx_create_keep_timepoints (kept timepoint samples)")
-        return lib()
+        return self._download_kept(self._keep_lib, "ecdna_ssa_ctx_download_kept", (), m, ids, count)
 
     def timepoints(self) -> int:
         """T of the timepoint keep block: the context's growth phases, else its snapshots with snapshot statistics."""
@@ -681,6 +680,9 @@ class Context:
         if self.ext is not None and self.ext.snapshot_stats:
             return int(self.params.n_snapshots)
         return 0
+
+    def _kept_timepoints(self) -> int:
+        return self.timepoints() if self.keep_timepoints is not None else 0
 
     def rescore_timepoints_enqueue(self, targets):
         """Enqueue the late scoring of the kept timepoint samples against one longitudinal target, `targets`
@@ -695,8 +697,7 @@ class Context:
     def download_rescored_timepoints(self) -> np.ndarray:
         """The records of the last rescore_timepoints, [T][n] abi.STATS_DTYPE
         (ecdna_ssa_ctx_download_rescored_timepoints; synchronises)."""
-        T = self.timepoints() if self.keep_timepoints is not None else 0
-        out = np.zeros((T, int(self.params.n_replicates)), dtype=abi.STATS_DTYPE)
+        out = np.zeros((self._kept_timepoints(), int(self.params.n_replicates)), dtype=abi.STATS_DTYPE)
         _check(self._keep_timepoints_lib().ecdna_ssa_ctx_download_rescored_timepoints(
             self.h, out.ctypes.data if out.size else None), "ecdna_ssa_ctx_download_rescored_timepoints")
         return out
@@ -714,15 +715,8 @@ class Context:
         """The posterior predictive histogram per timepoint (ecdna_ssa_ctx_pool_accepted_timepoints): per timepoint and
         global parameter set, the sum of the kept samples' histograms of the replicates the last accept() accepted
         under row `threshold`, [T][n_param_sets][hist_bins] u64. Shards' arrays sum to the whole run's."""
-        if not (0 <= int(threshold) < (1 << 32)):
-            raise ValueError(f"threshold = {threshold} does not fit the ABI's u32 field")
-        p = self.params
-        T = self.timepoints() if self.keep_timepoints is not None else 0
-        out = np.zeros((max(T, 1), p.n_param_sets, p.hist_bins), dtype=np.uint64)
-        _check(self._keep_timepoints_lib().ecdna_ssa_ctx_pool_accepted_timepoints(self.h, int(threshold),
-                                                                                  out.ctypes.data),
-               "ecdna_ssa_ctx_pool_accepted_timepoints")
-        return out[:T]
+        return self._pool_accepted(self._keep_timepoints_lib, "ecdna_ssa_ctx_pool_accepted_timepoints",
+                                   self._kept_timepoints(), threshold)
 
     def download_kept_timepoints(self, ids=None, count: Optional[int] = None):
         """Kept timepoint samples of the last launch (ecdna_ssa_ctx_download_kept_timepoints): (headers [T][k]
@@ -730,24 +724,8 @@ class Context:
         or of the call's first `count` replicates (default: all). cells[t][j][:headers[t][j]["nplus"]] are the N+
         cells' true copy numbers, ascending; the rest of a row is unspecified."""
         m = int(self.keep_timepoints.keep_cells) if self.keep_timepoints is not None else 0
-        T = self.timepoints() if self.keep_timepoints is not None else 0
-        if ids is not None:
-            if count is not None:
-                raise ValueError("give ids or count, not both")
-            idv = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
-            k = len(idv)
-        else:
-            idv = None
-            k = int(self.params.n_replicates) if count is None else int(count)
-            if not (0 <= k < (1 << 64)):
-                raise ValueError(f"count = {count} does not fit the ABI's u64 field")
-        headers = np.zeros((T, k), dtype=abi.KEPT_DTYPE)
-        cells = np.zeros((T, k, m), dtype=np.uint16)
-        _check(self._keep_timepoints_lib().ecdna_ssa_ctx_download_kept_timepoints(
-            self.h, k, idv.ctypes.data if idv is not None and k else None,
-            headers.ctypes.data if headers.size else None, cells.ctypes.data if cells.size else None),
-            "ecdna_ssa_ctx_download_kept_timepoints")
-        return headers, cells
+        return self._download_kept(self._keep_timepoints_lib, "ecdna_ssa_ctx_download_kept_timepoints",
+                                   (self._kept_timepoints(),), m, ids, count)
 
     def download(self, want_rows: bool = False) -> Result:
         p = self.params

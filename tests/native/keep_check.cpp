@@ -82,8 +82,8 @@ static int check_validate() {
 int main(int argc, char** argv) {
     if (argc > 1 && std::strcmp(argv[1], "index") == 0) return print_index(argc, argv);
     if (argc == 4 && std::strcmp(argv[1], "bytes") == 0) {
-        std::printf("cells %llu headers %llu\n", (unsigned long long)kp::cells_bytes(u64(argv[2]), (uint32_t)u64(argv[3])),
-                    (unsigned long long)kp::headers_bytes(u64(argv[2])));
+        std::printf("cells %llu headers %llu\n", (unsigned long long)kp::cells_bytes(1u, u64(argv[2]), (uint32_t)u64(argv[3])),
+                    (unsigned long long)kp::headers_bytes(1u, u64(argv[2])));
         return 0;
     }
     if (argc > 1 && std::strcmp(argv[1], "validate") == 0) return check_validate();

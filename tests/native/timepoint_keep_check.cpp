@@ -1,4 +1,4 @@
-// timepoint_keep_check.cpp — the host side of the timepoint keep block (ecdna-evo_amd/csrc/ssa_keep_timepoints.hpp) on
+// timepoint_keep_check.cpp — the host side of the timepoint keep block (ecdna-evo_amd/csrc/ssa_keep.hpp) on
 // the CPU, for tests/test_timepoint_keep_native.py: the timepoints of a context, the bytes the kept samples take and
 // every branch of the block's validation. Built for the host alone, with the address and undefined-behaviour
 // sanitizers.
@@ -10,8 +10,9 @@
 #include <cstring>
 #include <string>
 
-#include "ssa_keep_timepoints.hpp"
+#include "ssa_keep.hpp"
 
+namespace kp = ecdna::keep;
 namespace kt = ecdna::keep_timepoints;
 
 static uint64_t u64(const char* s) { return std::strtoull(s, nullptr, 10); }
@@ -101,8 +102,8 @@ int main(int argc, char** argv) {
     if (argc == 5 && std::strcmp(argv[1], "bytes") == 0) {
         const uint32_t T = (uint32_t)u64(argv[2]), m = (uint32_t)u64(argv[4]);
         const uint64_t n = u64(argv[3]);
-        std::printf("cells %llu headers %llu all %llu\n", (unsigned long long)kt::cells_bytes(T, n, m),
-                    (unsigned long long)kt::headers_bytes(T, n), (unsigned long long)kt::bytes(T, n, m));
+        std::printf("cells %llu headers %llu all %llu\n", (unsigned long long)kp::cells_bytes(T, n, m),
+                    (unsigned long long)kp::headers_bytes(T, n), (unsigned long long)kp::bytes(T, n, m));
         return 0;
     }
     if (argc > 1 && std::strcmp(argv[1], "validate") == 0) return check_validate();

@@ -509,6 +509,47 @@ def test_the_keep_block_beside_a_snapshot_context_stays_independent(engine_mod):
         assert ctx.download_rescored().tobytes() == want_rec.tobytes()
 
 
+@pytest.mark.gpu
+def test_two_blocks_of_different_sizes_share_the_gather_and_the_pool(engine_mod):
+    """Both blocks on one snapshot context with samples of 3 and of 5 cells: the gathers by ids and the pooled
+    histograms of the two, called in turn, go through the same staging and histogram buffers, and each is its own
+    block's — the rows of the whole download, and the sum of the accepted replicates' kept histograms."""
+    bins, n, rps = 65, 70, 35  # (70 replicates: more than one wave of them)
+    spec = abi.RunSpec(seed=11, process=abi.BIRTH_DEATH, rates=((1.0, 1.4, 0.3, 0.3), (1.0, 2.0, 0.5, 0.2)),
+                       reps_per_set=rps, n_replicates=n, max_cells=300, hist_bins=bins, init={1: 3, 40: 1},
+                       snapshots=(20, 150), flags=abi.FLAG_REP_STATS | abi.FLAG_EVENT_HASH | abi.FLAG_BIN_STORE,
+                       bin_kmax=32, snapshot_stats=True, snapshot_targets=_snap_targets(bins, 2), keep_cells=3,
+                       keep_timepoint_cells=5)
+    sets = (spec.replicate_ids() // np.uint64(rps)).astype(np.int64)
+    with _launched(engine_mod, spec) as ctx:
+        res = ctx.download()
+        h1, c1 = ctx.download_kept()
+        ht, ct = ctx.download_kept_timepoints()
+        assert c1.shape == (n, 3) and ct.shape == (2, n, 5)
+        assert (h1["nplus"] > 0).sum() > n // 2 and (ht["nplus"] > 0).sum() > n // 2
+        ids = np.asarray([64, 3, 37], dtype=np.uint64)  # (the call's ids are its indices)
+        index = ids.astype(np.int64)
+        first = ctx.download_kept(ids=ids)
+        timepoints = ctx.download_kept_timepoints(ids=ids)
+        third = ctx.download_kept(ids=ids)
+        assert first[1].shape == (3, 3) and timepoints[1].shape == (2, 3, 5)
+        for got_h, got_c in (first, third):
+            assert _canon(got_h, got_c) == _canon(h1[index], c1[index])
+        assert _canon_t(*timepoints) == _canon_t(ht[:, index], ct[:, index])
+        # one accept, on the snapshot at 150 cells: a proper subset of the replicates
+        ks = res.snapshot_stats[:, 1]["ks"]
+        acc = ctx.accept(abi.ACCEPT_SNAPSHOTS, [[float(np.median(ks)), INF, INF, INF]], [1])
+        assert 0 < acc.n_accepted < n
+        pool_first = ctx.pool_accepted(0)
+        pool_timepoints = ctx.pool_accepted_timepoints(0)
+        pool_third = ctx.pool_accepted(0)
+    want = tl.pooled(h1[None], c1[None], acc.mask, 0, sets, bins, 2)[0]
+    assert want.sum() > 0
+    np.testing.assert_array_equal(pool_first, want)
+    np.testing.assert_array_equal(pool_third, pool_first)
+    np.testing.assert_array_equal(pool_timepoints, tl.pooled(ht, ct, acc.mask, 0, sets, bins, 2))
+
+
 # ---- 9. limits ----
 
 @pytest.mark.gpu

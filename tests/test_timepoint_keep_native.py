@@ -1,4 +1,4 @@
-"""The host side of the timepoint keep block on the CPU (ecdna-evo_amd/csrc/ssa_keep_timepoints.hpp): the timepoints T of
+"""The host side of the timepoint keep block on the CPU (ecdna-evo_amd/csrc/ssa_keep.hpp): the timepoints T of
 a context, the bytes the kept samples take, and every branch of the block's validation.
 
 tests/native/timepoint_keep_check.cpp is a stand-alone program, built for the host alone with the address and
