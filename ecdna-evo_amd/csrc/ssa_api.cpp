@@ -137,7 +137,9 @@ int validate(const ecdna_ssa_params_t* p, const ecdna_ssa_ext_t* ext, const ecdn
             for (uint64_t j = 0; j < in.nplus; ++j) big += in.copies[j] > kmax;
             if (big > p->big_cap) return fail(ECDNA_E_INVALID, "initial cells above bin_kmax exceed big_cap");
         }
-        if (in.nminus > 0xffffffffull) return fail(ECDNA_E_INVALID, "initial N- cells must be < 2^32");
+        // (populations are u32: the bin stepper adds n- + n+ in 32 bits, and a sum of 2^32 would wrap past max_cells)
+        if (in.nminus > 0xffffffffull || in.nminus + in.nplus > 0xffffffffull)
+            return fail(ECDNA_E_INVALID, "initial cells (N- plus N+) must be < 2^32");
         for (uint64_t j = 0; j < in.nplus; ++j)
             if (in.copies[j] == 0) return fail(ECDNA_E_INVALID, "initial copy numbers must be >= 1");
         if (!p->init_set_offsets && !p->init_set_nminus) break;
@@ -817,6 +819,8 @@ ecdna::StepperArgs stepper_args(const ecdna_ssa_ctx* c, const Chunk& ch, size_t 
     a.stop_cells = (p.process == ECDNA_BIRTH_DEATH && (p.flags & ECDNA_FLAG_BD_CAP_COMPAT))
                        ? p.max_cells / 2 + (p.max_cells & 1)
                        : p.max_cells;
+    // (populations are u32 in every stepper: a larger bound acts as 2^32 - 1, include/ecdna_ssa.h)
+    a.stop_cells = std::min<uint64_t>(a.stop_cells, 0xffffffffull);
     a.n_snap = p.n_snapshots;
     a.snap_cells = c->d_snap_cells;
     a.snap_meta = c->d_snap_meta ? c->d_snap_meta + ch.first * p.n_snapshots : nullptr;

@@ -509,6 +509,12 @@ class RunSpec:
             p.init_nplus = len(copies)
             p.init_nminus = nm
             max_np = len(copies)
+            parts = [(copies, nm)]
+        # populations are u32 (include/ecdna_ssa.h): the library refuses an initial n- + n+ of 2^32 or more, and so does
+        # the spec, before the engine or the oracle sees it
+        for c, nm in parts:
+            if nm + len(c) >= 1 << 32:
+                raise ValueError(f"initial cells (N- {nm} plus N+ {len(c)}) must be < 2^32")
         cap = self.cell_cap
         if cap is None:
             cap = max(int(min(self.max_cells, 2**32 - 1)), max_np, 1)

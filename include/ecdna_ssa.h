@@ -207,7 +207,8 @@ typedef struct {
     uint64_t seed;                  /* --seed (src/clap_app.rs:63) */
     uint64_t first_replicate;       /* global id of the first replicate of this call (sharding) */
     uint64_t n_replicates;          /* replicates in this call */
-    uint64_t max_cells;             /* stop when n- + n+ >= max_cells (src/clap_app.rs:142-157) */
+    uint64_t max_cells;             /* stop when n- + n+ >= max_cells (src/clap_app.rs:142-157). Populations are
+                                       u32: a max_cells above 2^32 - 1 acts as 2^32 - 1 */
     double max_time;                /* stop when t >= max_time (years; src/clap_app.rs:151, 205) */
     uint64_t max_iter;              /* stop after max_iter events (1e9, src/main.rs:23); < 2^32 */
     uint32_t cell_cap;              /* capacity of the per-replicate N+ row (cells); rounded up to 64 */
@@ -215,7 +216,9 @@ typedef struct {
     /* Initial distribution (EcDNADistribution: n- plus one u16 per N+ cell; default {1: 1},
      * src/clap_app.rs:188-191). Either shared by every set (init_set_offsets == NULL: copies
      * init_copies[0 .. init_nplus), n- = init_nminus) or per set (init_set_offsets[n_param_sets+1]
-     * into init_copies, init_set_nminus[n_param_sets]). Copy numbers must be >= 1. */
+     * into init_copies, init_set_nminus[n_param_sets]). Copy numbers must be >= 1, and every set's initial
+     * n- + n+ must be < 2^32 (ECDNA_E_INVALID otherwise): cell counts are u32 in every stepper. A final state of
+     * 2^32 - 1 cells is reachable (it stops at once with MaxCells); its sample is the guard's (subsample mapping v1). */
     const uint16_t* init_copies;    /* host */
     uint32_t init_nplus;
     uint32_t bin_kmax;              /* ECDNA_FLAG_BIN_STORE: copy numbers 1..bin_kmax are binned; 32, 64 or

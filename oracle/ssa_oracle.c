@@ -560,7 +560,8 @@ static void simulate_replicate(const ecdna_ssa_params_t* p, uint64_t rid, uint16
             stop = ECDNA_STOP_MAX_ITER;
             break;
         }
-        if ((nminus + nplus) * cells_mul >= p->max_cells) {
+        /* (populations are u32: a bound above 2^32 - 1 acts as 2^32 - 1, include/ecdna_ssa.h) */
+        if ((nminus + nplus) * cells_mul >= p->max_cells || nminus + nplus >= 0xffffffffull) {
             stop = ECDNA_STOP_MAX_CELLS;
             break;
         }

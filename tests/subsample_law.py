@@ -36,10 +36,13 @@ def philox_blocks(c0, c1, c2, c3, seed):
     return np.stack(c, axis=1)
 
 
-def draws(first, count, N, seed, rid):
-    """Draws u_first .. u_(first + count - 1) below N."""
+def draw_trace(first, count, N, seed, rid):
+    """Draws u_first .. u_(first + count - 1) below N, the Philox blocks each took (1 = none wholly rejected) and how
+    many words each rejected before its accepted one."""
     idx = np.arange(first, first + count, dtype=np.uint64)
     out = np.zeros(count, dtype=np.uint64)
+    blocks = np.zeros(count, dtype=np.int64)
+    rejected = np.zeros(count, dtype=np.int64)
     todo = np.arange(count)
     thr = np.uint64((2**32 - N) % N)
     t = 0
@@ -50,9 +53,16 @@ def draws(first, count, N, seed, rid):
         got = ok.any(axis=1)
         first_ok = ok.argmax(axis=1)
         out[todo[got]] = (p[got, first_ok[got]] >> _S32)
+        blocks[todo] = t + 1
+        rejected[todo] += np.where(got, first_ok, 4)
         todo = todo[~got]
         t += 1
-    return out
+    return out, blocks, rejected
+
+
+def draws(first, count, N, seed, rid):
+    """Draws u_first .. u_(first + count - 1) below N."""
+    return draw_trace(first, count, N, seed, rid)[0]
 
 
 @lru_cache(maxsize=None)
@@ -118,6 +128,78 @@ def sample_stats(nminus, row, m, seed, rid, bins, target=None):
 def sample_hist(nminus, row, m, seed, rid, bins):
     """The sample's histogram [bins] (bin 0 = N- cells, last bin = overflow; zero under the guard)."""
     s = sample_cells(nminus, row, m, seed, rid)
+    h = np.zeros(bins, dtype=np.uint64)
+    if s is not None:
+        h += np.bincount(np.minimum(s[1], bins - 1), minlength=bins).astype(np.uint64)
+        h[0] += np.uint64(s[0])
+    return h
+
+
+# --- described states: a population given by its summary, bin counters and row, never expanded -----------------------
+# Download order (DESIGN.md §3.3, §3.4): the nminus N- cells, the counters' cells k = 1..K ascending, then the row.
+
+POSITION_LIMIT = 0xFFFFFFFF  # positions are u32 and 0xffffffff marks an empty table slot: N >= 2^32 - 1 is the guard
+_ZERO = dict(cells=0, mean=0.0, entropy=0.0, frequency=0.0, ks=0.0, mean_rel=0.0, entropy_rel=0.0, frequency_diff=0.0)
+
+
+def described_k(nminus, counters, row, pos):
+    """Copy numbers of the positions `pos` of the state (nminus, counters[K], row): 0 for an N- cell, -1 for a position
+    the counters and the row cannot account for. np.searchsorted on the inclusive prefix sums; nothing is expanded."""
+    nminus = int(nminus)
+    row = np.asarray(row, dtype=np.int64)
+    pos = np.asarray(pos, dtype=np.int64)
+    edges = nminus + np.cumsum(np.asarray(counters, dtype=np.uint64), dtype=np.uint64).astype(np.int64)
+    row_from = int(edges[-1]) if len(edges) else nminus
+    k = np.zeros(len(pos), dtype=np.int64)
+    binned = (pos >= nminus) & (pos < row_from)
+    k[binned] = np.searchsorted(edges, pos[binned], side="right") + 1  # the first counter whose prefix sum passes pos
+    j = pos[pos >= row_from] - row_from
+    kr = np.full(len(j), -1, dtype=np.int64)
+    kr[j < len(row)] = row[j[j < len(row)]]
+    k[pos >= row_from] = kr
+    return k
+
+
+def described_sample_cells(nminus, counters, row, m, seed, rid, nplus=None, table_slots=None):
+    """(n-, N+ copy numbers) of the sample of m cells of a described state, the N+ cells in sample_cells' order; None
+    under the guard. nplus: the summary's N+ cells (default: what the counters and the row hold); the row counts for
+    min(nplus - sum(counters), len(row)) cells. The guard: N >= 2^32 - 1 with m < N, counters that hold more cells than
+    the summary, a table of fewer than 2 * pow2ceil(m') slots (table_slots; None: as large as m' needs), 2^16 draws,
+    and a position of the sample's making (picked, or walked for a complement) that nothing accounts for."""
+    nminus, m = int(nminus), int(m)
+    small = int(np.asarray(counters, dtype=np.uint64).sum()) if len(counters) else 0
+    row = np.asarray(row, dtype=np.int64)
+    nplus = small + len(row) if nplus is None else int(nplus)
+    N = nminus + nplus
+    if m < N and (N >= POSITION_LIMIT or small > nplus):
+        return None
+    row = row[:max(0, min(nplus - small, len(row)))]
+    if m < N and table_slots is not None:
+        mp = min(m, N - m)
+        if table_slots < 2 * (1 << (mp - 1).bit_length() if mp > 1 else 1):
+            return None
+    pos, comp = sample_positions(N, m, seed, rid)
+    if pos is None:
+        return None
+    if comp:
+        keep = np.ones(N, dtype=bool)
+        keep[pos] = False
+        pos = np.flatnonzero(keep)
+    k = described_k(nminus, counters, row, pos)
+    if (k < 0).any():
+        return None
+    return int((pos < nminus).sum()), k[pos >= nminus]
+
+
+def described_sample_stats(nminus, counters, row, m, seed, rid, bins, target=None, **kw):
+    """ecdna_rep_stats_t of the sample of a described state (all zero under the guard)."""
+    s = described_sample_cells(nminus, counters, row, m, seed, rid, **kw)
+    return dict(_ZERO) if s is None else abc_stats.rep_stats(s[0], s[1], bins, target)
+
+
+def described_sample_hist(nminus, counters, row, m, seed, rid, bins, **kw):
+    """The sample's histogram [bins] of a described state (zero under the guard)."""
+    s = described_sample_cells(nminus, counters, row, m, seed, rid, **kw)
     h = np.zeros(bins, dtype=np.uint64)
     if s is not None:
         h += np.bincount(np.minimum(s[1], bins - 1), minlength=bins).astype(np.uint64)

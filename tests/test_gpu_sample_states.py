@@ -1,0 +1,543 @@
+"""The sampling passes on final states that are written down, not simulated (subsample mapping v1).
+
+A final state is a summary {n-, n+}, at most 256 bin counters and a row, so populations of up to 2^32 cells cost a few
+hundred bytes to describe. ecdna-evo_amd/bin/sample_state_check (tools/sample_state_check.hip, built by the product
+Makefile over the library's own ssa_subsample.o and ssa_passage.o) hands such states to launch_subsample, launch_passage
+(with founders, and without: the last phase) and launch_keep, and what comes back is compared with the numpy restatement
+(tests/subsample_law.py, described_*): cells, histograms, founder and kept headers and cells exactly, floats at the
+ABC-statistics tolerance of tests/test_gpu_subsample_stats.py. This reaches what populations from the steppers (8,200
+cells at most within a test) never do: Lemire rejection at rates 1/4 and 1/2, second and third Philox blocks per draw,
+positions and prefix sums above 2^31, u16 counters at 65,535, and every guard. Before any comparison the tests assert on
+the restatement alone that the inputs reach those paths (the floors below).
+
+All cases of the module travel in one file through one run of the program (well under a second); every population is
+one wave's work. Replicate ids carry a high word and a stride (2^40 + 5, step 3) and fall into two parameter sets."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import subsample_law as sl
+from ecdna_evo_amd import abi
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(REPO, "ecdna-evo_amd", "bin", "sample_state_check")
+MAGIC = 0x4B43485353
+RTOL, ATOL = 1e-12, 1e-14
+FLOATS = ("mean", "entropy", "frequency", "ks", "mean_rel", "entropy_rel", "frequency_diff")
+SEED = 2027
+RID0, RID_STRIDE = 2**40 + 5, 3
+RPS = RID0 + 4 * RID_STRIDE  # populations 0..3 fall into parameter set 0, the others into set 1
+N_SETS = 2
+SUBSAMPLE, PASSAGE, PASSAGE_LAST, KEEP = 0, 1, 2, 3
+FILL32, FILL16 = 0xEEEEEEEE, 0xEEEE  # what the program fills stats and founders with before a launch
+P31 = 2**31
+
+
+def rid(q):
+    return RID0 + q * RID_STRIDE
+
+
+def _target(bins):
+    rng = np.random.default_rng(5)
+    t = np.zeros(bins, np.uint64)
+    t[0] = 400
+    t[1:30] = rng.integers(0, 90, 29)
+    t[bins - 1] = 3
+    return t
+
+
+class Pop:
+    """One described population: nminus N- cells, counters[K] cells of k = 1..K, then the row's cells. nplus: what the
+    summary claims (default: what the counters and the row hold)."""
+
+    def __init__(self, nminus, counters, row, nplus=None):
+        self.nminus = int(nminus)
+        self.counters = np.asarray(counters, dtype=np.uint64)
+        self.row = np.asarray(row, dtype=np.uint16)
+        self.nplus = int(self.counters.sum()) + len(self.row) if nplus is None else int(nplus)
+        self.N = self.nminus + self.nplus
+
+
+class Case:
+    def __init__(self, name, which, pops, m, bins, cbytes=0, target=False, row_stride=None, row_pad=0, table_slots=0,
+                 reps_per_block=None):
+        self.name, self.which, self.pops, self.m, self.bins = name, which, pops, m, bins
+        self.bag_k = len(pops[0].counters)
+        assert all(len(p.counters) == self.bag_k for p in pops) and (cbytes != 0) == (self.bag_k != 0)
+        self.cbytes, self.target, self.table_slots, self.row_pad = cbytes, target, table_slots, row_pad
+        longest = max(len(p.row) for p in pops)
+        self.row_stride = row_stride or max(64, (longest + 63) // 64 * 64)
+        assert self.row_stride % 64 == 0 and longest <= self.row_stride
+        self.reps_per_block = reps_per_block or len(pops)
+        self.founder_stride = m if which == KEEP else (m + 63) // 64 * 64
+
+    def blob(self):
+        n = len(self.pops)
+        head = np.array([self.which, n, self.bag_k, self.cbytes, self.row_stride, self.row_pad, self.bins, self.m,
+                         self.table_slots, 0, SEED, RID0, RID_STRIDE, RPS, self.reps_per_block, int(self.target),
+                         N_SETS, self.founder_stride], dtype="<u8")
+        rows = np.zeros(n * self.row_stride + self.row_pad, dtype="<u2")
+        for q, p in enumerate(self.pops):
+            rows[q * self.row_stride:q * self.row_stride + len(p.row)] = p.row
+        parts = [head, np.array([p.nminus for p in self.pops], dtype="<u8"),
+                 np.array([p.nplus for p in self.pops], dtype="<u8")]
+        if self.bag_k:
+            ctr = np.stack([p.counters for p in self.pops])
+            assert int(ctr.max()) < 1 << (8 * self.cbytes)
+            parts.append(ctr.astype("<u2" if self.cbytes == 2 else "<u4"))
+        parts.append(rows)
+        if self.target:
+            parts.append(_target(self.bins).astype("<u8"))
+        return b"".join(x.tobytes() for x in parts)
+
+    def read(self, buf, at):
+        """This case's records of the result file from offset `at`: (dict, next offset)."""
+        n = len(self.pops)
+        out = {}
+        for key, dtype, count, shape in (("stats", abi.STATS_DTYPE, n, (n,)),
+                                         ("hist", "<u8", N_SETS * self.bins, (N_SETS, self.bins)),
+                                         ("headers", "<u4", 2 * n, (n, 2)),
+                                         ("cells", "<u2", n * self.founder_stride, (n, self.founder_stride))):
+            out[key] = np.frombuffer(buf, dtype=dtype, count=count, offset=at).reshape(shape)
+            at += out[key].nbytes
+        return out, at
+
+
+def _run_program(cases, tmp):
+    """Every case through one run of the program: the list of their result records."""
+    assert os.path.exists(EXE), "ecdna-evo_amd/bin/sample_state_check missing: run __graft_entry__.build()"
+    src, dst = os.path.join(tmp, "cases.bin"), os.path.join(tmp, "results.bin")
+    with open(src, "wb") as f:
+        f.write(np.array([MAGIC, len(cases)], dtype="<u8").tobytes())
+        for c in cases:
+            f.write(c.blob())
+    out = subprocess.run([EXE, src, dst], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    buf = open(dst, "rb").read()
+    top = np.frombuffer(buf, dtype="<u8", count=2)
+    assert int(top[0]) == MAGIC and int(top[1]) == len(cases)
+    res, at = [], 16
+    for c in cases:
+        r, at = c.read(buf, at)
+        res.append(r)
+    assert at == len(buf)
+    return res
+
+
+# --- the states -------------------------------------------------------------------------------------------------------
+
+def _spread(rng, K, total, empty=0.25):
+    """K counters that sum to `total`, a share of them empty, from the generator's multinomial."""
+    p = rng.dirichlet(np.ones(K))
+    p[rng.random(K) < empty] = 0.0
+    return rng.multinomial(total, p / p.sum()).astype(np.uint64)
+
+
+def _pops_a(N, K):
+    """Group A: N cells, nm in {0, 1000, 2^31}, 37 large-k cells in the row and the rest in K u32 counters."""
+    rng = np.random.default_rng([N % 1000003, K])
+    pops = []
+    for q in range(8):
+        nm = (0, 1000, P31)[q % 3]
+        row = rng.integers(K + 1, 65536, 37)
+        pops.append(Pop(nm, _spread(rng, K, N - nm - 37), row))
+        assert pops[-1].N == N
+    return pops
+
+
+A_SIZES = (3 * 2**30, P31 + 12345, 2**32 - 2)
+A_MS = (1, 64, 65, 4096)
+B_N = 1_000_003
+
+
+def _pops_b(binned):
+    """Group B, the workload's end state: 3 N- cells, 600,000 cells in K = 64 u32 counters and a 400,000-cell row; or
+    the same cells as a row only."""
+    rng = np.random.default_rng(64)
+    pops = []
+    for q in range(8):
+        ctr = _spread(rng, 64, 600_000, empty=0.1)
+        row = rng.integers(65, 3000, 400_000)
+        if not binned:
+            ctr, row = np.zeros(0), np.concatenate([np.repeat(np.arange(1, 65), ctr.astype(np.int64)), row])
+        pops.append(Pop(B_N - 1_000_000, ctr, row))
+        assert pops[-1].N == B_N
+    return pops
+
+
+def _pops_c16():
+    """Group C: K = 256 u16 counters, 150 of them at 65,535, about 1.2e7 cells."""
+    rng = np.random.default_rng(16)
+    pops = []
+    for q in range(8):
+        ctr = rng.integers(0, 40000, 256).astype(np.uint64)
+        ctr[rng.choice(256, 150, replace=False)] = 65535
+        ctr[0] = 65535 if q % 2 else 0
+        ctr[255] = 65535
+        pops.append(Pop((0, 5, 70000)[q % 3], ctr, rng.integers(257, 65536, 37)))
+        assert 1.1e7 < pops[-1].N < 1.3e7
+    return pops
+
+
+def _pops_c_rows():
+    """Group C, rows only: 3 * 2^30 cells, all but the row's 1,000 (copy numbers up to 32,767) N- cells."""
+    rng = np.random.default_rng(17)
+    return [Pop(3 * 2**30 - 1000, np.zeros(0), rng.integers(1, 32768, 1000)) for q in range(8)]
+
+
+def _pops_d():
+    """Group D, the size guard: n- + n+ of 2^32 - 1 (three ways), 2^32 (two ways) and 2^33 + 5 beside 2^32 - 2."""
+    rng = np.random.default_rng(32)
+    row = lambda n=37: rng.integers(33, 65536, n)
+    zero = np.zeros(32, np.uint64)
+    pops = [Pop(P31, _spread(rng, 32, P31 - 1 - 37), row()),        # 2^32 - 1
+            Pop(P31 + 1, _spread(rng, 32, P31 - 1 - 37), row()),    # 2^32
+            Pop(2**33, zero, row(5)),                               # 2^33 + 5
+            Pop(0, _spread(rng, 32, 2**32 - 2 - 37), row()),        # 2^32 - 2: sampled
+            Pop(2**32 - 1, zero, row(0)),                           # 2^32 - 1, N- cells only: a run can end here
+            Pop(0, _spread(rng, 32, 2**32 - 1 - 37), row()),        # 2^32 - 1, N+ cells only
+            Pop(2**32, zero, row(0)),                               # 2^32
+            Pop(1000, _spread(rng, 32, 2**32 - 2 - 1000 - 37), row())]  # 2^32 - 2: sampled
+    assert [p.N - 2**32 for p in pops] == [-1, 0, 2**32 + 5, -2, -1, -1, 0, -2]
+    return pops
+
+
+F_M = 128
+
+
+def _pops_f(K):
+    """Group F, small anchors for m = 128: the whole population with 0, 1, 64, 65 and m N+ cells, the complement with
+    m' = 1 (every sampled cell an N+ cell: m founders) and m' = m - 1, and N = 2m."""
+    rng = np.random.default_rng(7)
+
+    def pop(nm, nplus):
+        cells = np.sort(rng.integers(1, 400, nplus))
+        if not K:
+            return Pop(nm, np.zeros(0), rng.permutation(cells))
+        return Pop(nm, np.bincount(cells[cells <= K], minlength=K + 1)[1:], rng.permutation(cells[cells > K]))
+
+    return [pop(50, 0), pop(50, 1), pop(10, 64), pop(10, 65), pop(0, F_M), pop(0, F_M + 1), pop(100, 2 * F_M - 1 - 100),
+            pop(90, 2 * F_M - 90)]
+
+
+def _cases():
+    cases = []
+    for K in (256, 32):  # A
+        for N in A_SIZES:
+            pops = _pops_a(N, K)
+            for i, m in enumerate(A_MS):
+                kw = dict(m=m, bins=257 if K == 256 else 33, cbytes=4, target=bool((i + (K == 32)) % 2))
+                passes = (SUBSAMPLE, PASSAGE, KEEP) + ((PASSAGE_LAST,) if m == 65 else ())
+                cases += [Case(f"A K={K} N={N} m={m} pass={w}", w, pops, **kw) for w in passes]
+    for binned in (True, False):  # B
+        pops = _pops_b(binned)
+        for m in (200, 4096):
+            kw = dict(m=m, bins=257 if m == 200 else 33, cbytes=4 if binned else 0, target=m == 200)
+            cases += [Case(f"B binned={binned} m={m} pass={w}", w, pops, **kw) for w in (SUBSAMPLE, PASSAGE, KEEP)]
+    for tag, pops, cb in (("C u16", _pops_c16(), 2), ("C rows", _pops_c_rows(), 0)):  # C
+        for m in (65, 4096):
+            kw = dict(m=m, bins=257 if m == 65 else 33, cbytes=cb, target=m == 4096)
+            cases += [Case(f"{tag} m={m} pass={w}", w, pops, **kw) for w in (SUBSAMPLE, PASSAGE, KEEP)]
+    pops = _pops_d()  # D
+    for m in (64, 4096):
+        kw = dict(m=m, bins=33, cbytes=4, target=m == 64)
+        cases += [Case(f"D m={m} pass={w}", w, pops, **kw) for w in (SUBSAMPLE, PASSAGE, KEEP)]
+    cases += _cases_e()
+    for K in (0, 32):  # F
+        pops = _pops_f(K)
+        kw = dict(m=F_M, bins=33 if K else 257, cbytes=4 if K else 0, target=True)
+        cases += [Case(f"F K={K} pass={w}", w, pops, **kw) for w in (SUBSAMPLE, PASSAGE, PASSAGE_LAST, KEEP)]
+    return cases
+
+
+def _cases_e():
+    """Group E, states that contradict themselves. N stays below 400 and every row buffer carries 256 cells of padding
+    behind the last row, so every index the passes could form without their guards lies inside the buffers; in the table
+    case the populations of each workgroup's last wave are whole populations, which use no table, so a probe sequence
+    that ran past a table would end in the next wave's LDS and not outside the workgroup's."""
+    rng = np.random.default_rng(5)
+    cases = []
+    # counters that hold more cells (200) than the summary's n+ (150); the last two populations are consistent
+    pops = []
+    for q in range(8):
+        ctr = _spread(rng, 32, 200 if q < 6 else 150 - 20, empty=0.5)
+        pops.append(Pop(50, ctr, rng.integers(33, 900, 20), nplus=150))
+    kw = dict(m=60, bins=33, cbytes=2, target=True, row_pad=256)
+    cases += [Case(f"E counters pass={w}", w, pops, **kw) for w in (SUBSAMPLE, PASSAGE, KEEP)]
+    # a summary of 300 N+ cells over a row of 64: 100 picks among 300 positions leave the row; the last two are consistent
+    pops = [Pop(0 if q < 6 else 300, np.zeros(0), rng.integers(1, 900, 64), nplus=300 if q < 6 else 64) for q in range(8)]
+    kw = dict(m=100, bins=257, target=True, row_stride=64, row_pad=256)
+    cases += [Case(f"E row pass={w}", w, pops, **kw) for w in (SUBSAMPLE, PASSAGE, KEEP)]
+    # a table of 128 slots where m' = 100 needs 256; populations 3 and 7 (each workgroup's last wave) are whole
+    pops = [Pop(40, np.zeros(0), rng.integers(1, 900, 40 if q % 4 == 3 else 260)) for q in range(8)]
+    kw = dict(m=100, bins=257, target=True, row_pad=256, table_slots=128, reps_per_block=4)
+    cases += [Case(f"E table pass={w}", w, pops, **kw) for w in (SUBSAMPLE, PASSAGE, KEEP)]
+    return cases
+
+
+# --- the reference ----------------------------------------------------------------------------------------------------
+
+_STATE = {}
+
+
+def _all_cases():
+    if "cases" not in _STATE:
+        _STATE["cases"] = _cases()
+    return _STATE["cases"]
+
+
+def _want(case):
+    """The restatement's sample of every population of a case: [(n-, N+ cells) or None], computed once per state and m."""
+    key = ("want", id(case.pops), case.m, case.table_slots)
+    if key not in _STATE:
+        slots = case.table_slots or None
+        _STATE[key] = [sl.described_sample_cells(p.nminus, p.counters, p.row, case.m, SEED, rid(q), nplus=p.nplus,
+                                                 table_slots=slots) for q, p in enumerate(case.pops)]
+    return _STATE[key]
+
+
+@pytest.fixture(scope="module")
+def results(tmp_path_factory):
+    cases = _all_cases()
+    return dict(zip([c.name for c in cases], _run_program(cases, str(tmp_path_factory.mktemp("sample_states")))))
+
+
+def _compare(case, got):
+    """One case's records against the restatement."""
+    import abc_stats
+
+    want = _want(case)
+    n, bins, m = len(case.pops), case.bins, case.m
+    tgt = _target(bins) if case.target else None
+    hist = np.zeros((N_SETS, bins), dtype=np.uint64)
+    for q, (p, w) in enumerate(zip(case.pops, want)):
+        tag = f"{case.name}, population {q}"
+        if case.which != KEEP:
+            st = got["stats"][q]
+            ref = dict(sl._ZERO) if w is None else abc_stats.rep_stats(w[0], w[1], bins, tgt)
+            assert int(st["cells"]) == ref["cells"] == (0 if w is None else min(m, p.N)), tag
+            for f in FLOATS:
+                if w is None:
+                    assert st[f] == 0.0, f"{tag}: {f}"
+                else:
+                    np.testing.assert_allclose(st[f], ref[f], rtol=RTOL, atol=ATOL, err_msg=f"{tag}: {f}")
+            if w is not None:
+                hist[rid(q) // RPS] += np.bincount(np.minimum(w[1], bins - 1), minlength=bins).astype(np.uint64)
+                hist[rid(q) // RPS, 0] += np.uint64(w[0])
+        else:  # the keep pass writes neither
+            assert got["stats"][q].tobytes() == b"\xee" * 64, tag
+        head, cells = got["headers"][q].tolist(), got["cells"][q]
+        if case.which in (SUBSAMPLE, PASSAGE_LAST):  # no founders: nothing is written
+            assert head == [FILL32, FILL32] and np.all(cells == FILL16), tag
+            continue
+        if w is None:
+            guard = abi.KEPT_GUARD if case.which == KEEP else 0
+            assert head == [guard, guard] and np.all(cells == FILL16), tag
+            continue
+        assert head == [w[0], len(w[1])] and w[0] + len(w[1]) == min(m, p.N), tag
+        np.testing.assert_array_equal(cells[:len(w[1])], np.sort(w[1]), err_msg=tag)
+        assert np.all(cells[len(w[1]):] == FILL16), tag  # a row is written up to its n+ cells only
+    np.testing.assert_array_equal(got["hist"], hist, err_msg=case.name)
+
+
+def _group(results, prefix):
+    cases = [c for c in _all_cases() if c.name.startswith(prefix)]
+    assert cases
+    for c in cases:
+        _compare(c, results[c.name])
+    return cases
+
+
+def _trace(N, count=4096):
+    """Over the first `count` draws of the eight ids at N: (draws that took >= 2 blocks, >= 3 blocks, rejected words)."""
+    two = three = words = 0
+    for q in range(8):
+        _, blocks, rejected = sl.draw_trace(0, count, N, SEED, rid(q))
+        two, three, words = two + int((blocks >= 2).sum()), three + int((blocks >= 3).sum()), words + int(rejected.sum())
+    return two, three, words
+
+
+# --- the tests --------------------------------------------------------------------------------------------------------
+
+@pytest.mark.gpu
+def test_huge_populations_in_u32_counters(results):
+    """Group A: N in {3 * 2^30, 2^31 + 12345, 2^32 - 2} in K = 256 and K = 32 u32 counters beside 37 large-k cells,
+    nm in {0, 1000, 2^31}, m in {1, 64, 65, 4096}. Floors (the restatement alone, draws 0..4095 of the eight ids): at
+    3 * 2^30 a word is rejected with probability 1/4 and >= 50 draws reject their whole first block; at 2^31 + 12345
+    (1/2) >= 50 draws reject the second block too; >= 1,000 picked positions lie at or above 2^31."""
+    two, _, _ = _trace(3 * 2**30)
+    _, three, _ = _trace(P31 + 12345)
+    print(f"floors: first block rejected at 3 * 2^30: {two}; second block rejected at 2^31 + 12345: {three}")
+    assert two >= 50 and three >= 50
+    high = 0
+    for c in (c for c in _all_cases() if c.name.startswith("A ") and c.which == SUBSAMPLE and c.m == 4096):
+        for q, p in enumerate(c.pops):
+            pos, comp = sl.sample_positions(p.N, c.m, SEED, rid(q))
+            high += int((pos >= P31).sum())
+            assert not comp
+    print(f"floors: picked positions >= 2^31: {high}")
+    assert high >= 1000
+    cases = _group(results, "A ")
+    assert len(cases) == 2 * 3 * (4 * 3 + 1)
+    assert all(w is not None for c in cases for w in _want(c))
+
+
+@pytest.mark.gpu
+def test_workload_sized_populations(results):
+    """Group B, the shape the bench's largest configuration ends in: 1,000,003 cells, 600,000 of them in K = 64 u32
+    counters and 400,000 in the row, then the same cells as a row only; m in {200, 4096}. Floors: >= 1 rejected word
+    among the first 4,096 draws of the eight ids, and >= 100 picks each in the counters' and the row's positions."""
+    _, _, words = _trace(B_N)
+    in_counters = in_row = 0
+    for c in (c for c in _all_cases() if c.name.startswith("B binned=True") and c.which == SUBSAMPLE):
+        for q, p in enumerate(c.pops):
+            pos, _ = sl.sample_positions(p.N, c.m, SEED, rid(q))
+            small = int(p.counters.sum())
+            in_counters += int(((pos >= p.nminus) & (pos < p.nminus + small)).sum())
+            in_row += int((pos >= p.nminus + small).sum())
+    print(f"floors: rejected words at N = {B_N}: {words}; picks in counters: {in_counters}, in the row: {in_row}")
+    assert words >= 1 and in_counters >= 100 and in_row >= 100
+    cases = _group(results, "B ")
+    assert len(cases) == 12
+    for c in cases[:6]:  # the same cells in the same order, binned or not: the same sample, cell for cell
+        twin = c.name.replace("binned=True", "binned=False")
+        for key in ("hist", "headers", "cells"):
+            assert results[c.name][key].tobytes() == results[twin][key].tobytes(), (c.name, key)
+
+
+@pytest.mark.gpu
+def test_u16_counters_at_their_ceiling_and_a_row_behind_3e9_nminus_cells(results):
+    """Group C: K = 256 u16 counters, 150 and more of them at 65,535 (about 1.2e7 cells), and a row-only state of
+    3 * 2^30 cells of which the last 1,000 are the row (copy numbers up to 32,767)."""
+    cases = _group(results, "C ")
+    assert len(cases) == 12
+    assert all(w is not None for c in cases for w in _want(c))
+    assert max(int(p.counters.max()) for c in cases for p in c.pops if c.bag_k) == 65535
+
+
+@pytest.mark.gpu
+def test_the_size_guard(results):
+    """Group D: summaries of 2^32 - 1, 2^32 and 2^33 + 5 cells get the all-zero record and add nothing to the histogram,
+    found {0, 0} and keep the header {0xffffffff, 0xffffffff}; 2^32 - 2 beside them is sampled. (2^32 - 1 N- cells is a
+    state a run can end in: ecdna_ssa_ctx_create accepts it as an initial population.)"""
+    cases = _group(results, "D ")
+    assert len(cases) == 6
+    for c in cases:
+        assert [w is None for w in _want(c)] == [True, True, True, False, True, True, True, False]
+
+
+@pytest.mark.gpu
+def test_inconsistent_states(results):
+    """Group E: counters that hold more cells than the summary, a summary beyond the row's memory and a table of half
+    the slots m' needs each end the population with the guard's outputs; the consistent (and, in the table case, the
+    whole) populations beside them are sampled."""
+    cases = _group(results, "E ")
+    assert len(cases) == 9
+    for c in cases:
+        guarded = [w is None for w in _want(c)]
+        assert guarded == ([True, True, True, False] * 2 if "table" in c.name else [True] * 6 + [False] * 2), c.name
+        if "table" in c.name:  # the whole populations take the last wave of either workgroup
+            assert [p.N <= c.m for p in c.pops] == [False, False, False, True] * 2
+
+
+@pytest.mark.gpu
+def test_small_anchors_and_the_sort_edges(results):
+    """Group F (m = 128, rows only and K = 32): the whole population, the complement with m' = 1 and m' = m - 1 and
+    N = 2m, with 0, 1, 64, 65 and m founders among them: the exact ascending founders at the bitonic sort's edges."""
+    cases = _group(results, "F ")
+    assert len(cases) == 8
+    for c in cases:
+        assert [p.N for p in c.pops] == [50, 51, 74, 75, F_M, F_M + 1, 2 * F_M - 1, 2 * F_M]
+        assert {0, 1, 64, 65, F_M} <= {len(w[1]) for w in _want(c)}
+
+
+# --- end to end at large N through the C ABI -------------------------------------------------------------------------
+
+E2E_BINS = 33
+E2E_INIT = {0: 3 * 2**30 - 10**6, 1: 600_000, 3: 400_000}
+
+
+def _e2e_spec(store, init, **kw):
+    """64 replicates under ids with a high word and a stride, the sample, the keep block and a cohort of two targets
+    with sample sizes (200, 4096)."""
+    t = _target(E2E_BINS)
+    flags = abi.FLAG_REP_STATS | (abi.FLAG_BIN_STORE if store == "bins" else 0)
+    return abi.RunSpec(seed=SEED, process=abi.BIRTH_DEATH, rates=((1.0, 1.4, 0.3, 0.3),), n_replicates=64,
+                       first_replicate=RID0, replicate_stride=RID_STRIDE, hist_bins=E2E_BINS, init=init, flags=flags,
+                       bin_kmax=64 if store == "bins" else 0, stats_target=t, subsample_cells=4096, keep_cells=4096,
+                       cohort_targets=np.stack([t[::-1].copy(), t]), cohort_sample_cells=(200, 4096), **kw)
+
+
+def _e2e_run(engine_mod, oracle_mod, spec):
+    with engine_mod.Context(spec) as ctx:
+        ctx.launch()
+        ctx.sync()
+        res = ctx.download()
+        headers, cells = ctx.download_kept()
+    cpu = oracle_mod.run(spec)
+    for f in res.summaries.dtype.names:
+        a, b = res.summaries[f], cpu.summaries[f]
+        if f == "time":
+            a, b = a.view(np.uint64), b.view(np.uint64)
+        np.testing.assert_array_equal(a, b, err_msg=f)
+    return res, headers, cells
+
+
+def _same_record(got, want, tag):
+    assert int(got["cells"]) == want["cells"], tag
+    for f in FLOATS:
+        np.testing.assert_allclose(got[f], want[f], rtol=RTOL, atol=ATOL, err_msg=f"{tag}: {f}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("store", ["rows", "bins"])
+def test_end_to_end_at_3e9_cells(engine_mod, oracle_mod, store):
+    """3 * 2^30 cells through ecdna_ssa_ctx_create .. download: 3 * 2^30 - 10^6 N- cells, 600,000 cells with one copy and
+    400,000 with three, max_iter = 0 (every stepper stops at its first test, whatever its cell arithmetic), so the final
+    state is the initial one in download order. Records, sample histogram, kept headers and cells and the cohort's sample
+    records against the restatement, summaries against the oracle. The N+ share is 3e-4 (a sample of 4,096 holds one or
+    two N+ cells), so this mostly pins the host's plumbing of a u64 nminus into the passes (summaries, chunk ids, the
+    three passes' argument blocks); the positions, the lookup and rejection at this size are the described states' above."""
+    import abc_stats
+
+    spec = _e2e_spec(store, E2E_INIT, max_cells=2**32 - 1, max_iter=0, cell_cap=1_100_000)
+    res, headers, cells = _e2e_run(engine_mod, oracle_mod, spec)
+    assert np.all(res.summaries["stop_reason"] == abi.STOP_MAX_ITER) and np.all(res.summaries["iters"] == 0)
+    assert np.all(res.summaries["nminus"] == E2E_INIT[0]) and np.all(res.summaries["nplus"] == 10**6)
+    t = spec.cohort_targets
+    hist = np.zeros(E2E_BINS, dtype=np.uint64)
+    seen_nplus = 0
+    for i, r in enumerate(spec.replicate_ids()):
+        for m, checks in ((4096, (("sample", res.sample_stats[i], spec.stats_target),
+                                  ("cohort 1", res.cohort.sample_stats[1][i], t[1]))),
+                          (200, (("cohort 0", res.cohort.sample_stats[0][i], t[0]),))):
+            w = sl.described_sample_cells(E2E_INIT[0], [600_000, 0, 400_000], [], m, SEED, int(r))
+            assert w[0] + len(w[1]) == m
+            for name, got, target in checks:
+                _same_record(got, abc_stats.rep_stats(w[0], w[1], E2E_BINS, target), f"{name}, replicate {i}")
+            if m == 4096:
+                hist += np.bincount(w[1], minlength=E2E_BINS).astype(np.uint64)
+                hist[0] += np.uint64(w[0])
+                assert (int(headers[i]["nminus"]), int(headers[i]["nplus"])) == (w[0], len(w[1])), i
+                np.testing.assert_array_equal(cells[i, :len(w[1])], np.sort(w[1]), err_msg=f"replicate {i}")
+                seen_nplus += len(w[1])
+    np.testing.assert_array_equal(res.sample_hist[0], hist)
+    assert seen_nplus >= 20  # (about 1.3 N+ cells per sample of 4,096)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("store", ["rows", "bins"])
+def test_end_to_end_at_the_size_guard(engine_mod, oracle_mod, store):
+    """n- + n+ = 2^32 - 1 exactly (the largest initial population ecdna_ssa_ctx_create accepts; the sum does not wrap in
+    u32): every replicate stops at once with MaxCells, and its sample is the guard's: the all-zero record, nothing in
+    the sample histogram, the kept header {0xffffffff, 0xffffffff}."""
+    spec = _e2e_spec(store, {0: 2**32 - 3, 1: 2}, max_cells=10, cell_cap=64)
+    res, headers, cells = _e2e_run(engine_mod, oracle_mod, spec)
+    assert np.all(res.summaries["stop_reason"] == abi.STOP_MAX_CELLS) and np.all(res.summaries["iters"] == 0)
+    assert np.all(res.summaries["nminus"] == 2**32 - 3) and np.all(res.summaries["nplus"] == 2)
+    zero = np.zeros(64, dtype=abi.STATS_DTYPE).tobytes()
+    assert res.sample_stats.tobytes() == zero and not res.sample_hist.any()
+    assert res.cohort.sample_stats[0].tobytes() == zero and res.cohort.sample_stats[1].tobytes() == zero
+    assert np.all(headers["nminus"] == abi.KEPT_GUARD) and np.all(headers["nplus"] == abi.KEPT_GUARD)

@@ -72,6 +72,33 @@ def test_create_rejects_bad_subsample_parameters(product_lib):
         abi.RunSpec(subsample_cells=-1).params()
 
 
+def test_create_refuses_initial_populations_of_2_to_32_cells(product_lib):
+    """Populations are u32 (the bin stepper adds n- + n+ in 32 bits): an initial n- + n+ of 2^32 - 1 is accepted, its
+    final state being the one that reaches the sampling passes' N >= 2^32 - 1 guard; 2^32 is refused with E_INVALID by
+    ecdna_ssa_ctx_create and ecdna_ssa_run, shared or per set, and by RunSpec before the engine or the oracle runs."""
+    small = dict(n_replicates=4, max_cells=10, cell_cap=64, flags=abi.FLAG_REP_STATS, subsample_cells=5)
+    rc, msg = _create(product_lib, abi.RunSpec(init={0: 2**32 - 3, 1: 2}, **small).params())
+    assert rc in (abi.OK, abi.E_NODEVICE), (rc, msg)
+    rc, msg = _create(product_lib, abi.RunSpec(init_per_set=[{0: 2**32 - 1}], **small).params())
+    assert rc in (abi.OK, abi.E_NODEVICE), (rc, msg)
+    for nm, per_set in ((2**32 - 2, False), (2**32 - 2, True), (2**32, False), (2**40, True)):
+        spec = abi.RunSpec(init={0: 5, 1: 2}, **small) if not per_set else \
+            abi.RunSpec(init_per_set=[{0: 5, 1: 2}], **small)
+        p = spec.params()  # (the spec itself refuses such a population: the field is set behind it)
+        if per_set:
+            nms = np.asarray([nm], dtype=np.uint64)
+            p.init_set_nminus = nms.ctypes.data_as(C.POINTER(C.c_uint64))
+        else:
+            p.init_nminus = nm
+        rc, msg = _create(product_lib, p)
+        assert rc == abi.E_INVALID and "2^32" in msg and "initial cells" in msg, (nm, per_set, rc, msg)
+        assert product_lib.ecdna_ssa_run(C.byref(p), None, None, None, None) == abi.E_INVALID
+    for bad in (dict(init={0: 2**32 - 2, 1: 2}), dict(init={0: 2**32}), dict(init_per_set=[{0: 2**32 - 1, 7: 1}])):
+        with pytest.raises(ValueError, match="2\\^32"):
+            abi.RunSpec(**bad, **small).params()
+    abi.RunSpec(init={0: 2**32 - 2, 1: 1}, **small).params()
+
+
 def test_vector_philox_is_the_scalar_model():
     from test_host import _philox
 
@@ -167,3 +194,61 @@ def test_sample_statistics_are_those_of_the_sampled_cells():
         cnt = np.bincount(row, minlength=400) - np.bincount(row_s, minlength=400)
         assert cnt.min() >= 0 and nm_s <= nminus
     assert sl.sample_stats(0, [], 10, 3, 4, bins, tgt)["ks"] == 1.0  # extinct: as the full statistics
+
+
+@pytest.mark.parametrize("shape", ["rows", "counters", "both"])
+def test_described_states_sample_as_their_expansion(shape):
+    """The position -> copy number map of a described state (N- cells, counters k = 1..K ascending, row; searchsorted
+    on the prefix sums, nothing expanded) against sample_cells on the same state written out cell by cell: rows only,
+    counters only (with empty counters between full ones) and both, at N around m, 2m - 1 and 2m (the whole population,
+    the complement down to m' = 1 and up to m' = m - 1, the first direct sample), with and without N- cells."""
+    rng = np.random.default_rng(23)
+    m, bins = 64, 33
+    tgt = np.zeros(bins, np.uint64)
+    tgt[:20] = 5
+    for N in (m - 1, m, m + 1, 2 * m - 2, 2 * m - 1, 2 * m, 2 * m + 1, 5 * m):
+        for nminus in (0, 7):
+            nplus = N - nminus
+            n_row = {"rows": nplus, "counters": 0, "both": nplus // 3}[shape]
+            row = rng.integers(33, 400, n_row)
+            K = 0 if shape == "rows" else 32
+            counters = np.zeros(K, np.int64)
+            if K:  # nplus - n_row cells over a third of the counters: most counters stay empty
+                np.add.at(counters, rng.choice(K, 10, replace=False)[rng.integers(0, 10, nplus - n_row)], 1)
+            expanded = np.concatenate([np.repeat(np.arange(1, K + 1), counters), row]).astype(np.int64)
+            assert len(expanded) == nplus
+            pos = np.arange(N)
+            k_all = sl.described_k(nminus, counters, row, pos)
+            assert np.array_equal(k_all, np.concatenate([np.zeros(nminus, np.int64), expanded]))
+            assert sl.described_k(nminus, counters, row, [N, N + 5]).tolist() == [-1, -1]
+            for rid in (0, 2**40 + 5):
+                want = sl.sample_cells(nminus, expanded, m, 2027, rid)
+                got = sl.described_sample_cells(nminus, counters, row, m, 2027, rid)
+                assert got[0] == want[0] and np.array_equal(got[1], want[1]), (N, nminus, rid)
+                assert got[0] + len(got[1]) == min(m, N)
+                assert sl.described_sample_stats(nminus, counters, row, m, 2027, rid, bins, tgt) == \
+                    sl.sample_stats(nminus, expanded, m, 2027, rid, bins, tgt)
+                assert np.array_equal(sl.described_sample_hist(nminus, counters, row, m, 2027, rid, bins),
+                                      sl.sample_hist(nminus, expanded, m, 2027, rid, bins))
+
+
+def test_described_states_guards_and_trace():
+    """The guards of a described state, and the draw trace's bookkeeping against the draws themselves."""
+    zero = sl.described_sample_stats(0, [], [], 5, 1, 2, 17)
+    assert zero["cells"] == 0
+    row = np.arange(1, 301)
+    assert sl.described_sample_cells(10, [], row, 100, 1, 2) is not None
+    assert sl.described_sample_cells(2**32 - 1 - 300, [], row, 100, 1, 2) is None  # N = 2^32 - 1
+    assert sl.described_sample_cells(2**33, [], row, 100, 1, 2) is None
+    assert sl.described_sample_cells(2**32 - 2 - 300, [], row, 100, 1, 2) is not None  # N = 2^32 - 2: sampled
+    assert sl.described_sample_cells(10, [200, 200], [], 100, 1, 2, nplus=399) is None  # counters above the summary
+    assert sl.described_sample_cells(0, [], row[:64], 100, 1, 2, nplus=300) is None  # a summary beyond the row
+    assert sl.described_sample_cells(10, [], row, 100, 1, 2, table_slots=128) is None  # m' = 100 needs 256 slots
+    assert sl.described_sample_cells(10, [], row, 100, 1, 2, table_slots=256) is not None
+    assert sl.described_sample_stats(10, [], row, 100, 1, 2, 17, table_slots=128) == zero
+    assert not sl.described_sample_hist(10, [], row, 100, 1, 2, 17, table_slots=128).any()
+    for N in (1000, 3 * 2**30, 2**31 + 12345):
+        val, blocks, rejected = sl.draw_trace(3, 500, N, 77, 2**40 + 5)
+        assert np.array_equal(val, sl.draws(3, 500, N, 77, 2**40 + 5)) and val.max() < N
+        assert np.array_equal(blocks, rejected // 4 + 1) and blocks.min() == 1
+        assert (rejected > 0).any() == (N > 1000)
