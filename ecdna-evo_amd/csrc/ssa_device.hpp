@@ -221,6 +221,19 @@ __device__ __forceinline__ void stage_logtab(float2* lds) {
     __syncthreads();
 }
 
+// Popcount of the stream's next n bits (1 <= n <= 96) where the event's own words hold them all, branch-free:
+// the low min(n, 32) bits of w3, then of spare0 (n > 32), then of spare1 (n > 64), i.e. the words and bit ranges of
+// the first loop of WordStream::binomial_half_with from position 1 with enough spares. The low n bits of the
+// 64-bit word (spare0 : w3) go to its top by one shift (none from n = 64 on), the low n - 64 bits of spare1 to
+// its top likewise (a shift by 96 - n, 0 .. 31; no bits below n = 65). Other n give an unused value.
+__host__ __device__ __forceinline__ uint32_t popcount_base_words(uint32_t w3, uint32_t s0, uint32_t s1, uint32_t n) {
+    const bool third = n > 64u;
+    const uint64_t x64 = (((uint64_t)s0 << 32) | w3) << (third ? 0u : ((64u - n) & 63u));
+    const uint32_t x32 = third ? (s1 << ((96u - n) & 31u)) : 0u;
+    return (uint32_t)__builtin_popcount((uint32_t)(x64 >> 32)) + (uint32_t)__builtin_popcount((uint32_t)x64) +
+           (uint32_t)__builtin_popcount(x32);
+}
+
 // Stream words of one event (draw mapping v5): [w2, w3, spare0 .. spare(nsp-1), blk1.x,
 // blk1.y, blk1.z, blk1.w, blk2.x, ...], blk j = Philox(e, j, rid). The spares are words of earlier events'
 // blocks that no draw used, a two-slot stack (newest first). Only the rare paths (Lemire rejection, copy

@@ -1453,7 +1453,16 @@ __global__ void __launch_bounds__(BLK, SCH == 2 ? 4 : 1) ssa_stepper_bins(const 
                 k1v = __popc((uint32_t)(x64 >> 32)) + __popc((uint32_t)x64);
                 if (prolif && fast) ws.pos = (n + 63u) >> 5;  // 2 (w3 used) or 3 (w3 and the first spare)
                 if (prolif && !fast) {  // larger copy numbers or a rejected pick: more words
-                    if (k <= 32767u) {  // (larger ones stop with ECDNA_REP_ERR_OVERFLOW below)
+                    if (NG == 4 && ((seg_lim != 0u) & (nsp == 2u) & (n <= 96u))) {
+                        // 65 .. 96 bits with both spares in hand and no word taken by a rejection (seg_lim = 64 here): the
+                        // third base word covers them, as binomial_half's first loop would take it, with no Philox block
+                        // (four in ten of the wave-iterations that came here at C3 formed a block for this alone). In
+                        // the branch, not beside the two-word popcount: there it cost every event five VALU, most of its
+                        // gain. K = 32 only: the K = 64 and 256 instances serve populations whose divisions mostly exceed
+                        // 96 bits, so that their waves would run this and the block loop (whole C4 +1.5 %)
+                        k1v = popcount_base_words(w.w, sp0, sp1, n);
+                        ws.pos = 4u;
+                    } else if (k <= 32767u) {  // (larger ones stop with ECDNA_REP_ERR_OVERFLOW below)
                         PATH_STAT(5);
                         k1v = ws.binomial_half<kAhead, kB3>(n, rk);
                     }
