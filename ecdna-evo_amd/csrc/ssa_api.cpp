@@ -27,6 +27,7 @@
 #include "ssa_launch.h"
 #include "ssa_plan.hpp"
 #include "ssa_select.hpp"
+#include "ssa_thin.hpp"
 
 namespace {
 
@@ -1297,9 +1298,48 @@ int select_pass(ecdna_ssa_ctx* c, uint32_t source, const SelectSource& s, uint32
 // keep block do after their own argument checks. Slice t of the buffers is a run of kept samples as the keep block's, so
 // each is the keep block's pass once per slice, on offset pointers. `who`: the calling entry point, for the messages ----
 
+// The sizes of a sized rescore (thinning mapping v1): target p of slice t is scored on sample_cells[t * P + p] cells of
+// the kept sample, on thinning draw draws[t * P + p] (draws == nullptr: 0).
+struct ThinSizes {
+    const uint32_t* sample_cells;  // [T][P]
+    const uint32_t* draws;         // [T][P] or nullptr
+};
+
+// The thinning pass over slice t of a store (ssa_thin.hip), on the pointers rescore_store made for the slice: the key
+// and the stream are the ones the slice's own samples were drawn under — the run's seed and field 0 for the end of the
+// run, seed_t and field 0 for phase t of a passage context, the run's seed and field (t + 1) << 16 for snapshot t.
+int launch_thin_pass(const ecdna_ssa_ctx* c, const KeptStore& s, uint64_t t, uint32_t P, const ThinSizes& sizes,
+                     ecdna::ThinArgs a, hipStream_t st) {
+    namespace th = ecdna::thin;
+    const ecdna_ssa_params_t& p = c->p;
+    const bool timepoints = &s == &c->kept_tp;
+    const bool phases = timepoints && c->n_passages;
+    const th::Groups g = th::group_by_size_and_draw(sizes.sample_cells + t * P,
+                                                    sizes.draws ? sizes.draws + t * P : nullptr, P, s.m);
+    const th::LdsPlan l = th::lds_plan(p.hist_bins, g.max_mp);
+    a.seed = phases ? passage_seed(p.seed, (uint32_t)t) : p.seed;
+    a.rid0 = p.first_replicate;
+    a.rid_stride = rid_stride(p);
+    a.n_groups = g.n_groups;
+    a.table_slots = l.table_slots;
+    a.scratch_words = l.scratch_words;
+    const uint32_t field = (timepoints && !phases) ? (uint32_t)t + 1u : 0u;
+    for (uint32_t j = 0; j < g.n_groups; ++j) {
+        a.group_m[j] = g.m[j];
+        a.group_tag[j] = th::stream_tag(field, g.d[j]);
+    }
+    std::copy_n(g.offset, ecdna::kMaxCohortTargets + 1u, a.group_offset);
+    std::copy_n(g.targets, ecdna::kMaxCohortTargets, a.group_targets);
+    a.reps_per_block = pass_reps_per_block(c, a.n, l.waves);
+    TRY(ecdna::launch_thin(a, st));
+    return ECDNA_OK;
+}
+
 // Slice t's samples against its P targets, target_hists [T][P][bins]: the store's records [T][P][n], enqueued on the
-// stream of the last launch.
-int rescore_store(ecdna_ssa_ctx* c, KeptStore* s, uint32_t P, const uint64_t* target_hists, const char* who) {
+// stream of the last launch. sizes (nullptr: every target on the whole kept sample): each target on its own number of
+// measured cells.
+int rescore_store(ecdna_ssa_ctx* c, KeptStore* s, uint32_t P, const uint64_t* target_hists, const char* who,
+                  const ThinSizes* sizes = nullptr) {
     const uint32_t bins = c->p.hist_bins;
     const uint64_t n = c->p.n_replicates, targets = (uint64_t)s->T * P;
     TRY(hipSetDevice(c->device));
@@ -1323,6 +1363,20 @@ int rescore_store(ecdna_ssa_ctx* c, KeptStore* s, uint32_t P, const uint64_t* ta
         s->pending = true;
         s->stream = st;
         for (uint64_t t = 0; t < s->T; ++t) {
+            if (sizes) {
+                ecdna::ThinArgs ta{};
+                ta.headers = s->d_headers + t * n;
+                ta.cells = s->d_cells + t * n * s->m;
+                ta.out = static_cast<ecdna_rep_stats_t*>(s->stats.ptr) + t * P * n;
+                ta.target_cdf = static_cast<const double*>(s->cdf.ptr) + t * P * bins;
+                ta.target_scalars = static_cast<const double*>(s->scalars.ptr) + t * P * 3u;
+                ta.n = (uint32_t)n;
+                ta.m = s->m;
+                ta.bins = bins;
+                ta.n_targets = P;
+                TRY(launch_thin_pass(c, *s, t, P, *sizes, ta, st));
+                continue;
+            }
             ecdna::RescoreArgs a{};
             a.headers = s->d_headers + t * n;
             a.cells = s->d_cells + t * n * s->m;
@@ -1985,6 +2039,37 @@ int ecdna_ssa_ctx_rescore_timepoints(ecdna_ssa_ctx* c, const uint64_t* target_hi
     TRY(ctx_launched(c, "rescore_timepoints before launch"));
     // timepoint t's samples against target t: one target per slice
     return rescore_store(c, &c->kept_tp, 1u, target_hists, "ecdna_ssa_ctx_rescore_timepoints");
+}
+
+int ecdna_ssa_ctx_rescore_sized(ecdna_ssa_ctx* c, const ecdna_ssa_rescore_t* r) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!r) return fail(ECDNA_E_INVALID, "rescore_sized: the block is NULL");
+    const std::string bad = ecdna::thin::invalid(c->p.hist_bins, c->kept.m ? c->kept.m : ecdna::kMaxSubsampleCells, *r);
+    if (!bad.empty()) return fail(ECDNA_E_INVALID, bad);
+    if (!c->kept.m) return fail(ECDNA_E_STATE, "rescore_sized: the kept samples need ecdna_ssa_ctx_create_keep");
+    TRY(ctx_launched(c, "rescore_sized before launch"));
+    // (no sizes: every target on the whole kept sample, the unsized call's pass; the draws then thin nothing)
+    const ThinSizes sizes{r->sample_cells, r->sample_draws};
+    return rescore_store(c, &c->kept, r->n_targets, r->target_hists, "ecdna_ssa_ctx_rescore_sized",
+                         r->sample_cells ? &sizes : nullptr);
+}
+
+int ecdna_ssa_ctx_rescore_timepoints_sized(ecdna_ssa_ctx* c, const uint64_t* target_hists, const uint32_t* sample_cells,
+                                           uint32_t draw) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!target_hists) return fail(ECDNA_E_INVALID, "rescore_timepoints_sized.target_hists is NULL");
+    if (draw > ecdna::thin::kMaxDraw) return fail(ECDNA_E_INVALID, "rescore_timepoints_sized.draw must be in [0, 63]");
+    if (!c->kept_tp.m) return fail(ECDNA_E_STATE, std::string("rescore_timepoints_sized") + kNeedsTimepoints);
+    const uint32_t T = c->kept_tp.T;
+    const std::string bad =
+        ecdna::thin::invalid_timepoints(c->p.hist_bins, c->kept_tp.m, T, target_hists, sample_cells, draw);
+    if (!bad.empty()) return fail(ECDNA_E_INVALID, bad);
+    TRY(ctx_launched(c, "rescore_timepoints_sized before launch"));
+    // timepoint t's samples against target t on sample_cells[t] cells: one target per slice, all on draw `draw`
+    const std::vector<uint32_t> draws(T, draw);
+    const ThinSizes sizes{sample_cells, draws.data()};
+    return rescore_store(c, &c->kept_tp, 1u, target_hists, "ecdna_ssa_ctx_rescore_timepoints_sized",
+                         sample_cells ? &sizes : nullptr);
 }
 
 int ecdna_ssa_ctx_download_rescored(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out) {

@@ -1,7 +1,8 @@
 // ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by the device
 // code (steppers: ssa_kernels.hip, ssa_refdraws.hip; end-of-run passes: ssa_hist.hip,
 // ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip, ssa_cohort.hip; the passes over the kept samples:
-// ssa_rescore.hip; the acceptance pass: ssa_accept.hip; the select passes: ssa_select.hip) and ssa_api.cpp (the C ABI).
+// ssa_rescore.hip, ssa_thin.hip; the acceptance pass: ssa_accept.hip; the select passes: ssa_select.hip) and ssa_api.cpp
+// (the C ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -262,6 +263,36 @@ struct KeptGatherArgs {
     uint32_t n_ids;
     uint32_t m;
 };
+// ssa_thin (ssa_thin.hip; ecdna_ssa_ctx_rescore_sized, thinning mapping v1) scores one slice of kept samples, each
+// target on its own number of measured cells: the kept sample of header {a, b} is the population "a N- cells, then
+// cells[0 .. b)", and a target of m1 < a + b cells is scored on the sample of m1 cells that subsample mapping v1 draws
+// from it on the slice's thinning stream. The targets are grouped by (m1, draw index) in order of first appearance
+// (ssa_thin.hpp): group g draws one sample of group_m[g] cells on stream group_tag[g] — a group whose m1 reaches a + b
+// scores the whole kept sample instead, which depends on the replicate — and scores it against the targets
+// group_targets[group_offset[g] .. group_offset[g + 1]). Every target is in one group. The groups travel in the argument
+// block itself: wave-uniform, read with scalar loads. Records lie [P][n], as RescoreArgs'.
+struct ThinArgs {
+    const uint2* headers;                 // [n]
+    const uint16_t* cells;                // [n][m]
+    ecdna_rep_stats_t* out;               // [P][n]
+    const double* target_cdf;             // [P][bins]
+    const double* target_scalars;         // [P][3]
+    uint64_t seed;                        // the key the slice's own samples were drawn under
+    uint64_t rid0, rid_stride;            // replicate i of the run has the global id rid0 + i * rid_stride
+    uint32_t n;                           // replicates of the run
+    uint32_t m;                           // keep_cells
+    uint32_t bins;
+    uint32_t n_targets;                   // P, 1 .. kMaxCohortTargets
+    uint32_t reps_per_block;
+    uint32_t n_groups;                    // 1 .. P
+    uint32_t table_slots;                 // per-wave table of drawn positions: subsample_table_slots(largest m'), or 0
+    uint32_t scratch_words;               // per-wave u32 words shared by that table and the scored sample's CDF:
+                                          // cohort_scratch_words(bins, table_slots)
+    uint32_t group_m[kMaxCohortTargets];
+    uint32_t group_tag[kMaxCohortTargets];  // counter word 1 of the group's draws, without the block index t
+    uint32_t group_offset[kMaxCohortTargets + 1];
+    uint32_t group_targets[kMaxCohortTargets];
+};
 constexpr uint32_t kKeptGuard = 0xffffffffu;  // both words of the header of a sample the guard ended
 constexpr int kPoolBlock = 256;
 constexpr int kGatherBlock = 256;
@@ -422,6 +453,12 @@ inline uint32_t keep_waves(uint32_t bins, uint32_t bag_k, uint32_t table_slots, 
 inline uint32_t rescore_waves(uint32_t bins, size_t* lds_bytes) {
     return pass_waves(0, (size_t)bins * 4u + (size_t)bins * 8u, lds_bytes);
 }
+// ssa_thin: per wave the kept sample's full histogram, the thinned sample's histogram, and one scratch area that holds
+// the table (u32) while a sample is drawn and the scored sample's CDF (f64 per bin) while it is scored: 8 + 8 + 16 KiB at
+// 2,048 bins and keep_cells = 4096 (m' <= 2048: a table of 4,096 slots), two waves per workgroup
+inline uint32_t thin_waves(uint32_t bins, uint32_t table_slots, size_t* lds_bytes) {
+    return pass_waves(0, (2u * (size_t)bins + cohort_scratch_words(bins, table_slots)) * 4u, lds_bytes);
+}
 // ssa_pool_accepted: the workgroup's u64 sum of the accepted samples' histograms (one parameter set at a time), 16 KiB
 // at 2,048 bins; its waves keep nothing of their own
 inline uint32_t pool_accepted_waves(uint32_t bins, size_t* lds_bytes) {
@@ -437,6 +474,7 @@ inline uint32_t keep_snapshots_waves(uint32_t bins, uint32_t table_slots, uint32
 hipError_t launch_keep(const PassageArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_keep_snapshots(const PassageArgs& a, uint32_t blocks, hipStream_t stream);
 hipError_t launch_rescore(const RescoreArgs& a, hipStream_t stream);
+hipError_t launch_thin(const ThinArgs& a, hipStream_t stream);
 hipError_t launch_pool_accepted(const PoolAcceptedArgs& a, hipStream_t stream);
 hipError_t launch_kept_gather(const KeptGatherArgs& a, hipStream_t stream);
 hipError_t launch_subsample(const SubsampleArgs& a, uint32_t blocks, hipStream_t stream);

@@ -157,6 +157,23 @@ class KeepTimepoints(C.Structure):
     ]
 
 
+class Rescore(C.Structure):
+    """ecdna_ssa_rescore_t: the block of ecdna_ssa_ctx_rescore_sized — the kept samples scored against each target on
+    its own number of measured cells (added within ABI v13; thinning mapping v1)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_targets", C.c_uint32),
+        ("target_hists", C.POINTER(C.c_uint64)),
+        ("sample_cells", C.POINTER(C.c_uint32)),
+        ("sample_draws", C.POINTER(C.c_uint32)),
+        ("reserved", C.c_uint64),
+    ]
+
+
+THIN_MAX_DRAW = 63  # the draw index of a thinning takes 6 bits (thinning mapping v1)
+
+
 class Kept(C.Structure):
     """ecdna_kept_t: one kept sample's header, its N- and N+ cell counts."""
 

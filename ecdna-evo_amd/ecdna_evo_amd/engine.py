@@ -52,6 +52,8 @@ EXPORTS = [
     "ecdna_ssa_ctx_download_rescored_timepoints",
     "ecdna_ssa_ctx_pool_accepted_timepoints",
     "ecdna_ssa_ctx_download_kept_timepoints",
+    "ecdna_ssa_ctx_rescore_sized",
+    "ecdna_ssa_ctx_rescore_timepoints_sized",
     "ecdna_ssa_ctx_accept",
     "ecdna_ssa_ctx_download_accept",
     "ecdna_ssa_ctx_select",
@@ -204,6 +206,12 @@ def lib():
         L.ecdna_ssa_ctx_pool_accepted_timepoints.restype = C.c_int
         L.ecdna_ssa_ctx_download_kept_timepoints.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ecdna_ssa_ctx_download_kept_timepoints.restype = C.c_int
+    # (likewise added within v13: the kept samples at each target's own number of measured cells)
+    if hasattr(L, "ecdna_ssa_ctx_rescore_sized"):
+        L.ecdna_ssa_ctx_rescore_sized.argtypes = [C.c_void_p, P(abi.Rescore)]
+        L.ecdna_ssa_ctx_rescore_sized.restype = C.c_int
+        L.ecdna_ssa_ctx_rescore_timepoints_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ecdna_ssa_ctx_rescore_timepoints_sized.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -632,16 +640,45 @@ class Context:
                                         cells.ctypes.data if cells.size else None), name)
         return headers, cells
 
-    def rescore_enqueue(self, targets):
+    @staticmethod
+    def _sized_lib():
+        return _lib_with("ecdna_ssa_ctx_rescore_sized", "sized rescoring")
+
+    @staticmethod
+    def _u32_list(name: str, values, count: int) -> np.ndarray:
+        """`values` (one number for all, or one per target) as the ABI's [count] u32 array."""
+        arr = np.asarray(values)
+        if arr.ndim == 0:
+            arr = np.full(count, arr)
+        if arr.shape != (count,):
+            raise ValueError(f"{name} must be one number, or one per target ({count})")
+        if arr.size and not (np.issubdtype(arr.dtype, np.integer) and arr.min() >= 0 and arr.max() < (1 << 32)):
+            raise ValueError(f"{name} does not fit the ABI's u32 fields")
+        return np.ascontiguousarray(arr, dtype=np.uint32)
+
+    def rescore_enqueue(self, targets, sample_cells=None, draws=None):
         """Enqueue the late scoring of the kept samples against `targets` [P][hist_bins] on the stream of the last
-        launch (ecdna_ssa_ctx_rescore); download_rescored returns the records."""
+        launch (ecdna_ssa_ctx_rescore; with sample_cells or draws, ecdna_ssa_ctx_rescore_sized); download_rescored
+        returns the records."""
         tgt = np.ascontiguousarray(targets, dtype=np.uint64)
         if tgt.ndim != 2 or tgt.shape[1] != self.params.hist_bins:
             raise ValueError("targets must be [P][hist_bins]: one histogram of hist_bins entries per target")
         if not (0 <= tgt.shape[0] < (1 << 32)):
             raise ValueError(f"{tgt.shape[0]} targets do not fit the ABI's u32 field")
         self._rescore_targets = 0
-        _check(self._keep_lib().ecdna_ssa_ctx_rescore(self.h, tgt.shape[0], tgt.ctypes.data), "ecdna_ssa_ctx_rescore")
+        if sample_cells is None and draws is None:
+            _check(self._keep_lib().ecdna_ssa_ctx_rescore(self.h, tgt.shape[0], tgt.ctypes.data),
+                   "ecdna_ssa_ctx_rescore")
+        else:
+            cells = None if sample_cells is None else self._u32_list("sample_cells", sample_cells, tgt.shape[0])
+            dr = None if draws is None else self._u32_list("draws", draws, tgt.shape[0])
+            r = abi.Rescore(struct_size=C.sizeof(abi.Rescore), n_targets=tgt.shape[0])
+            r.target_hists = tgt.ctypes.data_as(C.POINTER(C.c_uint64))
+            if cells is not None:
+                r.sample_cells = cells.ctypes.data_as(C.POINTER(C.c_uint32))
+            if dr is not None:
+                r.sample_draws = dr.ctypes.data_as(C.POINTER(C.c_uint32))
+            _check(self._sized_lib().ecdna_ssa_ctx_rescore_sized(self.h, C.byref(r)), "ecdna_ssa_ctx_rescore_sized")
         self._rescore_targets = tgt.shape[0]
 
     def download_rescored(self) -> np.ndarray:
@@ -651,12 +688,15 @@ class Context:
                "ecdna_ssa_ctx_download_rescored")
         return out
 
-    def rescore(self, targets) -> np.ndarray:
+    def rescore(self, targets, sample_cells=None, draws=None) -> np.ndarray:
         """Score every replicate's kept sample (RunSpec.keep_cells) against targets that need not have been known at
         create: records [P][n] abi.STATS_DTYPE, byte for byte those of a run with stats_target = targets[p] and
         subsample_cells = keep_cells. They are the acceptance source abi.ACCEPT_RESCORED until the next rescore or
-        launch."""
-        self.rescore_enqueue(targets)
+        launch.
+        sample_cells (one number, or one per target, each 1 .. keep_cells): target p is scored on a uniform sample of
+        sample_cells[p] of the kept cells instead — the law of having measured that many cells (thinning mapping v1) —
+        and draws (each 0 .. 63) picks one of 64 independent such thinnings per target."""
+        self.rescore_enqueue(targets, sample_cells, draws)
         return self.download_rescored()
 
     def pool_accepted(self, threshold: int) -> np.ndarray:
@@ -684,15 +724,24 @@ class Context:
     def _kept_timepoints(self) -> int:
         return self.timepoints() if self.keep_timepoints is not None else 0
 
-    def rescore_timepoints_enqueue(self, targets):
+    def rescore_timepoints_enqueue(self, targets, sample_cells=None, draw: int = 0):
         """Enqueue the late scoring of the kept timepoint samples against one longitudinal target, `targets`
-        [T][hist_bins], on the stream of the last launch (ecdna_ssa_ctx_rescore_timepoints);
-        download_rescored_timepoints returns the records."""
+        [T][hist_bins], on the stream of the last launch (ecdna_ssa_ctx_rescore_timepoints; with sample_cells,
+        ecdna_ssa_ctx_rescore_timepoints_sized); download_rescored_timepoints returns the records."""
         tgt = np.ascontiguousarray(targets, dtype=np.uint64)
         if self.keep_timepoints is not None and (tgt.ndim != 2 or tgt.shape != (self.timepoints(), self.params.hist_bins)):
             raise ValueError("targets must be [T][hist_bins]: one histogram of hist_bins entries per timepoint")
-        _check(self._keep_timepoints_lib().ecdna_ssa_ctx_rescore_timepoints(self.h, tgt.ctypes.data if tgt.size else None),
-               "ecdna_ssa_ctx_rescore_timepoints")
+        if sample_cells is None and draw == 0:
+            _check(self._keep_timepoints_lib().ecdna_ssa_ctx_rescore_timepoints(self.h, tgt.ctypes.data if tgt.size else None),
+                   "ecdna_ssa_ctx_rescore_timepoints")
+            return
+        _check_u32("draw", draw)
+        # (a context without the block: the library says so, whatever the sizes' shape)
+        count = self.timepoints() if self.keep_timepoints is not None else int(np.size(sample_cells))
+        cells = None if sample_cells is None else self._u32_list("sample_cells", sample_cells, count)
+        _check(self._sized_lib().ecdna_ssa_ctx_rescore_timepoints_sized(
+            self.h, tgt.ctypes.data if tgt.size else None, cells.ctypes.data if cells is not None and cells.size else None,
+            int(draw)), "ecdna_ssa_ctx_rescore_timepoints_sized")
 
     def download_rescored_timepoints(self) -> np.ndarray:
         """The records of the last rescore_timepoints, [T][n] abi.STATS_DTYPE
@@ -702,13 +751,15 @@ class Context:
             self.h, out.ctypes.data if out.size else None), "ecdna_ssa_ctx_download_rescored_timepoints")
         return out
 
-    def rescore_timepoints(self, targets) -> np.ndarray:
+    def rescore_timepoints(self, targets, sample_cells=None, draw: int = 0) -> np.ndarray:
         """Score every replicate's kept sample of every timepoint (RunSpec.keep_timepoint_cells) against a longitudinal
         target that need not have been known at create: records [T][n] abi.STATS_DTYPE, byte for byte the sample
         records of a run created with these targets as passage_targets (or as snapshot_targets with
         snapshot_subsample_cells = keep_timepoint_cells). They are the acceptance source
-        abi.ACCEPT_RESCORED_TIMEPOINTS until the next rescore_timepoints or launch."""
-        self.rescore_timepoints_enqueue(targets)
+        abi.ACCEPT_RESCORED_TIMEPOINTS until the next rescore_timepoints or launch.
+        sample_cells (one number, or one per timepoint, each 1 .. keep_timepoint_cells): timepoint t is scored on a
+        uniform sample of sample_cells[t] of its kept cells instead (thinning mapping v1), on thinning `draw` (0 .. 63)."""
+        self.rescore_timepoints_enqueue(targets, sample_cells, draw)
         return self.download_rescored_timepoints()
 
     def pool_accepted_timepoints(self, threshold: int) -> np.ndarray:

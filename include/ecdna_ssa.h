@@ -43,7 +43,11 @@
 extern "C" {
 #endif
 
-/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): the sample of every
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): the kept samples
+ * rescored at each target's own number of measured cells — the block ecdna_ssa_rescore_t, ecdna_ssa_ctx_rescore_sized
+ * and ecdna_ssa_ctx_rescore_timepoints_sized (below; thinning mapping v1). They write the records of
+ * ecdna_ssa_ctx_rescore and _rescore_timepoints; a context that never calls them allocates and launches nothing new.
+ * Added within v13 (additive: no layout and no existing function changes, the version stays 13): the sample of every
  * timepoint of a longitudinal run kept on the GPU — the timepoint keep block ecdna_ssa_keep_timepoints_t and
  * ecdna_ssa_ctx_create_keep_timepoints, late scoring of a longitudinal target (ecdna_ssa_ctx_rescore_timepoints,
  * ecdna_ssa_ctx_download_rescored_timepoints and the acceptance source ECDNA_ACCEPT_RESCORED_TIMEPOINTS), the posterior
@@ -640,6 +644,65 @@ int ecdna_ssa_ctx_download_kept_timepoints(ecdna_ssa_ctx* c, uint64_t n_ids,
                                            const uint64_t* ids /* host, global ids; NULL: the first n_ids replicates */,
                                            ecdna_kept_t* out_headers /* [T][n_ids] */,
                                            uint16_t* out_cells /* [T][n_ids][keep_cells] */);
+
+/* The kept samples rescored at each target's own number of measured cells (added within ABI v13). A cohort target has
+ * its own number of measured cells (ecdna_ssa_cohort_t.sample_cells), and that number is part of the distance's noise;
+ * ecdna_ssa_ctx_rescore and _rescore_timepoints score a late target on all keep_cells cells of the kept sample. The two
+ * calls below score target p on sample_cells[p] <= keep_cells cells instead, without a new sweep: a patient with 80
+ * measured cells against a sweep kept at 200, the hundred measured cells of a flask passaged at thousands
+ * (keep_cells == passage_cells stays the bottleneck), the biopsies of one patient with their own cell counts. A uniform
+ * m1-subset of a uniform m-subset of a population is a uniform m1-subset of that population (m1 <= min(m, N)), so
+ * thinning the kept sample has exactly the law of having measured m1 cells.
+ *
+ * Thinning mapping v1. The scored object is the kept sample of (replicate r, slice tau): the one slice of the keep
+ * block, or timepoint t of the timepoint keep block, with header {a, b} and cells[0 .. b), ascending true copy numbers.
+ *  - A header {0xffffffff, 0xffffffff} gives the all-zero record for every target, as ecdna_ssa_ctx_rescore does.
+ *  - The population is N_k = a + b cells in this order: positions 0 .. a - 1 are N- cells (k = 0), position a + j is
+ *    cells[j]. This is the shape of a snapshot's population ("nminus N- cells, then the row").
+ *  - A target with m1 >= N_k is scored on the whole kept sample: its record is byte for byte ecdna_ssa_ctx_rescore's
+ *    (respectively _rescore_timepoints') against the same histogram. This covers {0, 0} and populations that were
+ *    smaller than m1.
+ *  - Otherwise subsample mapping v1 (ecdna_ssa_params_t.subsample_cells above) is applied unchanged to this population
+ *    with N = N_k and m = m1: m' = min(m1, N_k - m1) positions, the first m' distinct draws, the complement when
+ *    m' != m1, the Lemire draw with rejection, the guard after 2^16 draws (the all-zero record) — under the key and on
+ *    the stream below.
+ *  - The key is the one under which slice tau's own sample was drawn: the run's seed, or seed_g for growth phase g of a
+ *    passage context (passage mapping v1).
+ *  - The stream: counter word 1 is base_tau | 0x20000000 | (d << 10) | t, t < 2^10 the block index. base_tau is the tag
+ *    slice tau's own sample used — 0xC0000000 for the end of the run and for passage phases, 0xC0000000 | (s + 1) << 16
+ *    for snapshot s — and d in 0 .. 63 is the target's draw index: up to 64 independent thinnings of the same kept
+ *    sample, which estimate a replicate's acceptance probability under measurement noise. Counter word 0 is the draw
+ *    index i, words 2 and 3 the GLOBAL replicate id. t takes bits 0-9, d bits 10-15, the snapshot field bits 16-22, the
+ *    thinning flag bit 29, the tag bits 30-31: the fields do not meet. No existing stream has bits 29, 30 and 31 all
+ *    set: the steppers use small numbers, ecdna_host_subsample uses 0x80000000 | block with block < 2^30, and the
+ *    sampling passes keep bit 29 clear.
+ *  - The record is the statistics of the thinned sample — its clipped histogram, its true sum of k, its size m1 and its
+ *    N+ count — against the target, computed as the cohort pass scores a group's sample.
+ *  - Targets with equal (m1, d) see the same thinned sample.
+ *  - Nothing depends on chunk, shard, grid or device.
+ *  - A thinned record is NOT byte for byte a relaunch with subsample_cells = m1: the kept cells are sorted and the draw
+ *    order is gone. It has the same law.
+ *  - ecdna_ssa_ctx_pool_accepted*, ecdna_ssa_ctx_download_kept* still pool and return the whole kept samples.
+ *
+ * The two calls write the records that ecdna_ssa_ctx_rescore and _rescore_timepoints write: the same buffers [P][n] and
+ * [T][n], the same validity rules, the acceptance sources 12 and 13, the same drop of the keys ecdna_ssa_ctx_select
+ * cached; ecdna_ssa_ctx_download_rescored*, _accept, _select and _select_digits take them unchanged. With sample_cells
+ * == NULL the draws are ignored (a non-zero draw with nothing thinned is legal and has no effect) and the result is
+ * byte for byte the unsized call's.
+ * ECDNA_E_INVALID (the message names the entry): NULL arguments, a wrong struct_size, reserved != 0, n_targets outside
+ * 1 .. 64, an all-zero target row, a draw above 63, sample_cells[p] outside 1 .. keep_cells — a target with more
+ * measured cells than were kept cannot be served honestly. ECDNA_E_STATE: before a launch; a context without the block. */
+typedef struct {
+    uint32_t struct_size;          /* sizeof(ecdna_ssa_rescore_t) */
+    uint32_t n_targets;            /* P, 1 .. 64 */
+    const uint64_t* target_hists;  /* host [P][hist_bins], no all-zero row */
+    const uint32_t* sample_cells;  /* host [P] or NULL (every target: the whole kept sample); each 1 .. keep_cells */
+    const uint32_t* sample_draws;  /* host [P] or NULL (all 0); each 0 .. 63 */
+    uint64_t reserved;             /* must be 0 */
+} ecdna_ssa_rescore_t;
+int ecdna_ssa_ctx_rescore_sized(ecdna_ssa_ctx* c, const ecdna_ssa_rescore_t* r);
+int ecdna_ssa_ctx_rescore_timepoints_sized(ecdna_ssa_ctx* c, const uint64_t* target_hists /* [T][hist_bins] */,
+                                           const uint32_t* sample_cells /* [T] or NULL */, uint32_t draw /* 0..63 */);
 /* Use caller-owned DEVICE buffers for the histogram [n_param_sets*hist_bins] u64 and totals
  * [n_param_sets] (e.g. tensors later all-reduced over RCCL). NULL keeps the internal buffer. */
 int ecdna_ssa_ctx_set_outputs(ecdna_ssa_ctx* c, uint64_t* d_hist, ecdna_totals_t* d_totals);
