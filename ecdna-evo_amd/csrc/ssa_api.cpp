@@ -2,7 +2,7 @@
 // device-resident run contexts, chunking by HBM capacity, and launches of the
 // stepper and end-of-run kernels (ssa_kernels.hip, ssa_hist.hip, ssa_subsample.hip, ssa_snapstats.hip,
 // ssa_passage.hip, ssa_cohort.hip), of the post-launch acceptance pass (ssa_accept.hip) and of the passes over the kept
-// samples (ssa_rescore.hip). The kept samples of the keep block and of the timepoint keep block lie in one kind of store
+// samples (ssa_rescore.hip, ssa_thin.hip, ssa_accept_draws.hip). The kept samples of the keep block and of the timepoint keep block lie in one kind of store
 // (KeptStore), and every pass over them has one implementation, which the two blocks' entry points call.
 //
 // This file replaces, for one GPU, the per-replicate driver loop of the
@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/ecdna_ssa.h"
+#include "ssa_accept_draws.hpp"
 #include "ssa_cohort.hpp"
 #include "ssa_keep.hpp"
 #include "ssa_launch.h"
@@ -386,6 +387,14 @@ struct ecdna_ssa_ctx {
     // over either share: the pooled histogram [T][sets][bins], the gather's index [n_ids] and staging [T][n_ids]
     KeptStore kept, kept_tp;
     AcceptBuf pool_hist, gat_index, gat_headers, gat_cells;
+    // the acceptance over repeated thinnings (ecdna_ssa_ctx_accept_draws): the call's own target CDFs [targets][bins]
+    // and scalars [targets][3] (and their host copies, which an asynchronous upload reads), passes [n][Q] u8 and sums
+    // [Q][n_sets] u64; what the last call left for ecdna_ssa_ctx_download_accept_draws (a launch invalidates it)
+    AcceptBuf adr_cdf, adr_scalars, adr_passes, adr_sums;
+    std::vector<double> adr_host_cdf, adr_host_scalars;
+    bool adr_valid = false, adr_pending = false;
+    uint32_t adr_rows = 0;
+    hipStream_t adr_stream = nullptr;
 };
 
 namespace {
@@ -417,7 +426,8 @@ void free_ctx(ecdna_ssa_ctx* c) {
     for (void* d : c->owned) (void)hipFree(d);
     for (AcceptBuf* b : {&c->acc_mask, &c->acc_counts, &c->acc_blocks, &c->acc_ids, &c->acc_list, &c->sel_keys,
                          &c->sel_hist, &c->pool_hist, &c->gat_index, &c->gat_headers, &c->gat_cells, &c->kept.stats,
-                         &c->kept.cdf, &c->kept.scalars, &c->kept_tp.stats, &c->kept_tp.cdf, &c->kept_tp.scalars})
+                         &c->kept.cdf, &c->kept.scalars, &c->kept_tp.stats, &c->kept_tp.cdf, &c->kept_tp.scalars,
+                         &c->adr_cdf, &c->adr_scalars, &c->adr_passes, &c->adr_sums})
         if (b->ptr) (void)hipFree(b->ptr);
     delete c;
 }
@@ -1676,6 +1686,7 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
     c->accept_valid = false;  // (the acceptance pass's results were the previous launch's)
     c->sel_keys_valid = false;  // (and the select passes' keys were made from its records)
     c->kept.valid = c->kept_tp.valid = false;  // (and the rescored records from its kept samples)
+    c->adr_valid = false;  // (and the thinned acceptance's counts)
     return ECDNA_OK;
 }
 
@@ -2070,6 +2081,111 @@ int ecdna_ssa_ctx_rescore_timepoints_sized(ecdna_ssa_ctx* c, const uint64_t* tar
     const ThinSizes sizes{sample_cells, draws.data()};
     return rescore_store(c, &c->kept_tp, 1u, target_hists, "ecdna_ssa_ctx_rescore_timepoints_sized",
                          sample_cells ? &sizes : nullptr);
+}
+
+// ---- the acceptance over repeated thinnings of the kept samples (thinned acceptance mapping v1): ssa_thin and the
+// acceptance pass run together over a range of draws, on buffers of its own ----
+
+int ecdna_ssa_ctx_accept_draws(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a) {
+    namespace ad = ecdna::accept_draws;
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!a) return fail(ECDNA_E_INVALID, "accept_draws: the block is NULL");
+    const ecdna_ssa_params_t& p = c->p;
+    const bool timepoints = a->timepoints == 1u;
+    KeptStore* s = timepoints ? &c->kept_tp : &c->kept;
+    const std::string bad = ad::invalid(p.hist_bins, s->m ? s->m : ecdna::kMaxSubsampleCells, c->kept_tp.T,
+                                        p.n_replicates, *a);
+    if (!bad.empty()) return fail(ECDNA_E_INVALID, bad);
+    if (!s->m)
+        return fail(ECDNA_E_STATE, timepoints ? std::string("accept_draws") + kNeedsTimepoints
+                                              : std::string("accept_draws: the kept samples need ecdna_ssa_ctx_create_keep"));
+    TRY(ctx_launched(c, "accept_draws before launch"));
+
+    const uint32_t bins = p.hist_bins, Q = a->n_thresholds, P = a->n_targets;
+    const uint64_t n = p.n_replicates;
+    const bool phases = timepoints && c->n_passages;
+    TRY(hipSetDevice(c->device));
+    hipStream_t st = c->last_stream;
+    // an earlier call may still read the targets this one replaces (and its upload their host copies)
+    if (c->adr_pending) TRY(hipStreamSynchronize(c->adr_stream));
+    c->adr_pending = false;
+    c->adr_valid = false;
+    TRY(accept_reserve(&c->adr_cdf, ad::cdf_bytes(P, bins), "target CDFs", "ecdna_ssa_ctx_accept_draws"));
+    TRY(accept_reserve(&c->adr_scalars, ad::scalars_bytes(P), "target scalars", "ecdna_ssa_ctx_accept_draws"));
+    TRY(accept_reserve(&c->adr_sums, ad::sums_bytes(Q, p.n_param_sets), "sums", "ecdna_ssa_ctx_accept_draws"));
+    if (n) TRY(accept_reserve(&c->adr_passes, ad::passes_bytes(n, Q), "passes", "ecdna_ssa_ctx_accept_draws"));
+    TRY(hipMemsetAsync(c->adr_sums.ptr, 0, ad::sums_bytes(Q, p.n_param_sets), st));
+    if (n) {
+        c->adr_host_cdf.resize((uint64_t)P * bins);
+        c->adr_host_scalars.resize((uint64_t)P * 3u);
+        summarize_targets(a->target_hists, P, bins, c->adr_host_cdf.data(), c->adr_host_scalars.data());
+        TRY(hipMemcpyAsync(c->adr_cdf.ptr, c->adr_host_cdf.data(), ad::cdf_bytes(P, bins), hipMemcpyHostToDevice, st));
+        TRY(hipMemcpyAsync(c->adr_scalars.ptr, c->adr_host_scalars.data(), ad::scalars_bytes(P), hipMemcpyHostToDevice,
+                           st));
+        c->adr_pending = true;
+        c->adr_stream = st;
+        const ad::Plan pl = ad::plan(bins, s->m, timepoints, P, a->sample_cells, a->timepoint_mask);
+        ecdna::AcceptDrawsArgs k{};
+        k.headers = s->d_headers;
+        k.cells = s->d_cells;
+        // rule 1 as the sources 12 and 13 have it: the one summary, or on a passage context every participating phase's
+        k.summaries = phases ? c->d_pas_summ : c->d_summ;
+        k.err_stride = phases ? n : 0u;
+        k.target_cdf = static_cast<const double*>(c->adr_cdf.ptr);
+        k.target_scalars = static_cast<const double*>(c->adr_scalars.ptr);
+        k.passes = static_cast<uint8_t*>(c->adr_passes.ptr);
+        k.sums = static_cast<unsigned long long*>(c->adr_sums.ptr);
+        k.slice_mask = pl.slice_mask;
+        k.rid0 = p.first_replicate;
+        k.rid_stride = rid_stride(p);
+        k.reps_per_set = p.reps_per_set;
+        k.n = (uint32_t)n;
+        k.m = s->m;
+        k.bins = bins;
+        k.n_slices = pl.n_slices;
+        k.n_targets = P;
+        k.n_groups = pl.n_groups;
+        k.Q = Q;
+        k.n_sets = p.n_param_sets;
+        k.first_draw = a->first_draw;
+        k.n_draws = a->n_draws;
+        k.reps_per_block = pass_reps_per_block(c, k.n, pl.lds.waves);
+        k.table_slots = pl.lds.table_slots;
+        k.scratch_words = pl.lds.scratch_words;
+        // the key and the stream each slice's own samples were drawn under (launch_thin_pass)
+        for (uint32_t t = 0; t < pl.n_slices; ++t) {
+            k.slice_seed[t] = phases ? passage_seed(p.seed, t) : p.seed;
+            k.slice_tag[t] = ecdna::thin::stream_tag((timepoints && !phases) ? t + 1u : 0u, 0u);
+        }
+        std::copy_n(pl.slice_group, ecdna::kMaxCohortTargets + 1u, k.slice_group);
+        std::copy_n(pl.group_m, ecdna::kMaxCohortTargets, k.group_m);
+        std::copy_n(pl.group_offset, ecdna::kMaxCohortTargets + 1u, k.group_offset);
+        std::copy_n(pl.group_targets, ecdna::kMaxCohortTargets, k.group_targets);
+        for (uint32_t q = 0; q < Q; ++q) {
+            const ecdna_accept_threshold_t& t = a->thresholds[q];
+            k.thr[q][0] = t.ks;
+            k.thr[q][1] = t.mean_rel;
+            k.thr[q][2] = t.entropy_rel;
+            k.thr[q][3] = t.frequency_diff;
+        }
+        TRY(ecdna::launch_accept_draws(k, st));
+    }
+    c->adr_rows = Q;
+    c->adr_valid = true;
+    return ECDNA_OK;
+}
+
+int ecdna_ssa_ctx_download_accept_draws(ecdna_ssa_ctx* c, uint64_t* out_sums, uint8_t* out_passes) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!c->launched || !c->adr_valid)
+        return fail(ECDNA_E_STATE, "download_accept_draws before accept_draws (a launch invalidates its results)");
+    TRY(ctx_drain(c));
+    const ecdna_ssa_params_t& p = c->p;
+    if (out_sums)
+        TRY(to_host(out_sums, static_cast<const uint64_t*>(c->adr_sums.ptr), (uint64_t)c->adr_rows * p.n_param_sets));
+    if (out_passes && p.n_replicates)
+        TRY(to_host(out_passes, static_cast<const uint8_t*>(c->adr_passes.ptr), p.n_replicates * c->adr_rows));
+    return ECDNA_OK;
 }
 
 int ecdna_ssa_ctx_download_rescored(ecdna_ssa_ctx* c, ecdna_rep_stats_t* out) {

@@ -1,7 +1,8 @@
 // ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by the device
 // code (steppers: ssa_kernels.hip, ssa_refdraws.hip; end-of-run passes: ssa_hist.hip,
 // ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip, ssa_cohort.hip; the passes over the kept samples:
-// ssa_rescore.hip, ssa_thin.hip; the acceptance pass: ssa_accept.hip; the select passes: ssa_select.hip) and ssa_api.cpp
+// ssa_rescore.hip, ssa_thin.hip, ssa_accept_draws.hip; the acceptance pass: ssa_accept.hip; the select passes:
+// ssa_select.hip) and ssa_api.cpp
 // (the C ABI).
 #pragma once
 
@@ -326,6 +327,49 @@ struct AcceptArgs {
     double thr[kMaxAcceptRows][4];        // per row: ks, mean_rel, entropy_rel, frequency_diff (+inf: off)
 };
 
+// The thinned acceptance pass over the whole run (ssa_accept_draws.hip; ecdna_ssa_ctx_accept_draws, thinned acceptance
+// mapping v1): per replicate and threshold row, the number of thinning draws first_draw .. first_draw + n_draws - 1 on
+// which acceptance mapping v1 accepts the records ssa_thin would write for that draw — the records stay in registers.
+// The store's slices 0 .. n_slices - 1 (headers [n_slices][n], cells [n_slices][n][m]) are walked per replicate; slice
+// s takes part when bit s of slice_mask is set, draws under slice_seed[s] on stream slice_tag[s] | (d << 10), and owns
+// the groups slice_group[s] .. slice_group[s + 1) of the flat group tables, which are ThinArgs' (group_targets index
+// target_cdf / target_scalars). The keep store is one slice with the participating targets' groups; the timepoint store
+// a slice per timepoint with one group of one target. The error words lie as AcceptArgs' (err_stride 0: one summary per
+// replicate; else slice s's is summaries[i + s * err_stride], over the slices of slice_mask). Tables and thresholds
+// travel in the argument block: wave-uniform, read with scalar loads (below the 4 KiB a launch takes).
+struct AcceptDrawsArgs {
+    const uint2* headers;                 // [n_slices][n]
+    const uint16_t* cells;                // [n_slices][n][m]
+    const ecdna_rep_summary_t* summaries;
+    const double* target_cdf;             // [targets][bins]
+    const double* target_scalars;         // [targets][3]
+    uint8_t* passes;                      // [n][Q]
+    unsigned long long* sums;             // [Q][n_sets], zeroed before the launch
+    uint64_t err_stride;
+    uint64_t slice_mask;                  // participating slices (bits below n_slices, never 0)
+    uint64_t rid0, rid_stride, reps_per_set;
+    uint32_t n;                           // replicates of the run
+    uint32_t m;                           // the store's kept cells per sample
+    uint32_t bins;
+    uint32_t n_slices;                    // 1 .. 64
+    uint32_t n_targets;                   // rows of target_cdf, 1 .. kMaxCohortTargets
+    uint32_t n_groups;                    // over all slices, 1 .. n_targets
+    uint32_t Q;                           // threshold rows, 1 .. kMaxAcceptRows
+    uint32_t n_sets;
+    uint32_t first_draw, n_draws;         // first_draw + n_draws <= 64, n_draws >= 1
+    uint32_t reps_per_block;
+    uint32_t table_slots;                 // as ThinArgs'
+    uint32_t scratch_words;
+    uint64_t slice_seed[kMaxCohortTargets];
+    uint32_t slice_tag[kMaxCohortTargets];        // thin::stream_tag(field, 0)
+    uint32_t slice_group[kMaxCohortTargets + 1];
+    uint32_t group_m[kMaxCohortTargets];
+    uint32_t group_offset[kMaxCohortTargets + 1];
+    uint32_t group_targets[kMaxCohortTargets];
+    double thr[kMaxAcceptRows][4];        // per row: ks, mean_rel, entropy_rel, frequency_diff (+inf: off)
+};
+static_assert(sizeof(AcceptDrawsArgs) <= 4096, "the argument block of a launch");
+
 // The select passes over the whole run (ssa_select.hip; ecdna_ssa_ctx_select / _select_digits, select mapping v1): an
 // 8-bit radix select of order statistics of the four distances. ssa_select_keys writes every replicate's key per
 // distance once per (source, timepoint mask), from records and error words that lie as AcceptArgs' do;
@@ -487,6 +531,9 @@ hipError_t launch_passage(const PassageArgs& a, uint32_t blocks, hipStream_t str
 // ever waits for another. a.n > 0.
 hipError_t launch_accept_mask(const AcceptArgs& a, hipStream_t stream);
 hipError_t launch_accept_list(const AcceptArgs& a, hipStream_t stream);
+// The thinned acceptance pass (ssa_accept_draws.hip): ssa_thin's LDS plan (thin_waves) for a.table_slots; a.sums zeroed
+// on the stream before it. A block that disagrees with the plan is refused: hipErrorInvalidValue.
+hipError_t launch_accept_draws(const AcceptDrawsArgs& a, hipStream_t stream);
 // The select passes (ssa_select.hip): the keys of every replicate (a.n > 0), and one digit pass over them (a.hist zeroed
 // on the stream before it; the dynamic LDS table is 1 KiB per group of the distance with most, 32 KiB at most).
 hipError_t launch_select_keys(const SelectKeyArgs& a, hipStream_t stream);

@@ -113,10 +113,14 @@ __device__ __forceinline__ void wave_rep_stats(const uint32_t* wh, unsigned long
 // complete (wave_sync_lds). F[bins] is the wave's scratch for the population's CDF; every lane reads back only the bins
 // it wrote (b = lane mod 64). Per target the operations and their order are wave_rep_stats': the lane's
 // ks = fmax(ks, |F(b) - F_t(b)|) over its bins ascending, then the wave maximum (max is exact in any order).
-__device__ __forceinline__ void wave_cohort_stats(const uint32_t* wh, double* F, uint32_t bins, uint64_t cells,
-                                                  uint64_t ksum, uint64_t nplus, const double* target_cdf,
-                                                  const double* target_scalars, const uint32_t* list, uint32_t count,
-                                                  uint32_t lane, ecdna_rep_stats_t* out, uint64_t out_stride) {
+//
+// wave_cohort_record is the register-level core: lane j < count returns the record of the j-th target of the list (the
+// other lanes an unspecified one) and nothing is stored, so a pass that keeps no records (ssa_accept_draws.hip) tests
+// the very numbers wave_cohort_stats writes.
+__device__ __forceinline__ ecdna_rep_stats_t wave_cohort_record(const uint32_t* wh, double* F, uint32_t bins,
+                                                                uint64_t cells, uint64_t ksum, uint64_t nplus,
+                                                                const double* target_cdf, const double* target_scalars,
+                                                                const uint32_t* list, uint32_t count, uint32_t lane) {
     const double inv = cells ? 1.0 / (double)cells : 0.0;
     double carry = 0.0, ent = 0.0;
     for (uint32_t base = 0; base < bins; base += 64u) {
@@ -138,11 +142,11 @@ __device__ __forceinline__ void wave_cohort_stats(const uint32_t* wh, double* F,
         ks = wave_max(ks);
         if (lane == j) my_ks = ks;
     }
+    ecdna_rep_stats_t st{};
     if (lane < count) {
         const uint32_t t = list ? list[lane] : lane;
         const double target_mean = target_scalars[3u * t], target_entropy = target_scalars[3u * t + 1u],
                      target_freq = target_scalars[3u * t + 2u];
-        ecdna_rep_stats_t st;
         st.cells = cells;
         st.mean = cells ? (double)ksum * inv : 0.0;
         st.entropy = ent;
@@ -152,8 +156,17 @@ __device__ __forceinline__ void wave_cohort_stats(const uint32_t* wh, double* F,
         st.mean_rel = target_mean > 0.0 ? dm / target_mean : dm;
         st.entropy_rel = target_entropy > 0.0 ? de / target_entropy : de;
         st.frequency_diff = fabs(st.frequency - target_freq);
-        out[(uint64_t)t * out_stride] = st;
     }
+    return st;
+}
+
+__device__ __forceinline__ void wave_cohort_stats(const uint32_t* wh, double* F, uint32_t bins, uint64_t cells,
+                                                  uint64_t ksum, uint64_t nplus, const double* target_cdf,
+                                                  const double* target_scalars, const uint32_t* list, uint32_t count,
+                                                  uint32_t lane, ecdna_rep_stats_t* out, uint64_t out_stride) {
+    const ecdna_rep_stats_t st =
+        wave_cohort_record(wh, F, bins, cells, ksum, nplus, target_cdf, target_scalars, list, count, lane);
+    if (lane < count) out[(uint64_t)(list ? list[lane] : lane) * out_stride] = st;
 }
 
 }  // namespace ecdna

@@ -223,6 +223,28 @@ SELECT_PASSES = 8  # 8 bits of the 64-bit key per pass
 SELECT_FIELDS = ("ks", "mean_rel", "entropy_rel", "frequency_diff")  # the distance order of the select's arrays
 
 
+class AcceptDraws(C.Structure):
+    """ecdna_ssa_accept_draws_t: the block of ecdna_ssa_ctx_accept_draws — acceptance counted over a range of thinning
+    draws of the kept samples (added within ABI v13; thinned acceptance mapping v1)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("timepoints", C.c_uint32),
+        ("n_targets", C.c_uint32),
+        ("target_hists", C.POINTER(C.c_uint64)),
+        ("sample_cells", C.POINTER(C.c_uint32)),
+        ("first_draw", C.c_uint32),
+        ("n_draws", C.c_uint32),
+        ("n_thresholds", C.c_uint32),
+        ("thresholds", C.POINTER(AcceptThreshold)),
+        ("timepoint_mask", C.c_uint64),
+        ("reserved", C.c_uint64),
+    ]
+
+
+ACCEPT_DRAWS_MAX = 64  # thinning draws of one kept sample: the draw index takes 6 bits
+
+
 class Select(C.Structure):
     """ecdna_ssa_select_t: the argument block of ecdna_ssa_ctx_select (added within ABI v13)."""
 

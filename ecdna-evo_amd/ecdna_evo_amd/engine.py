@@ -56,6 +56,8 @@ EXPORTS = [
     "ecdna_ssa_ctx_rescore_timepoints_sized",
     "ecdna_ssa_ctx_accept",
     "ecdna_ssa_ctx_download_accept",
+    "ecdna_ssa_ctx_accept_draws",
+    "ecdna_ssa_ctx_download_accept_draws",
     "ecdna_ssa_ctx_select",
     "ecdna_ssa_ctx_select_digits",
     "ecdna_ssa_ctx_download_rng_words",
@@ -212,6 +214,12 @@ def lib():
         L.ecdna_ssa_ctx_rescore_sized.restype = C.c_int
         L.ecdna_ssa_ctx_rescore_timepoints_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.ecdna_ssa_ctx_rescore_timepoints_sized.restype = C.c_int
+    # (likewise added within v13: acceptance over repeated thinnings of the kept samples)
+    if hasattr(L, "ecdna_ssa_ctx_accept_draws"):
+        L.ecdna_ssa_ctx_accept_draws.argtypes = [C.c_void_p, P(abi.AcceptDraws)]
+        L.ecdna_ssa_ctx_accept_draws.restype = C.c_int
+        L.ecdna_ssa_ctx_download_accept_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ecdna_ssa_ctx_download_accept_draws.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -351,6 +359,18 @@ class AcceptResult:
         self.n_accepted = n_accepted
         self.ids = ids
         self.stats = stats
+
+
+class AcceptDrawsResult:
+    """What ecdna_ssa_ctx_accept_draws keeps (thinned acceptance mapping v1, include/ecdna_ssa.h): sums [Q][n_sets] u64,
+    per threshold row and global parameter set the sum of passes over the call's replicates (shards' arrays sum to the
+    whole run's); passes [n][Q] u8, the number of the n_draws thinnings on which replicate i is accepted under row q.
+    passes / n_draws estimates the replicate's acceptance probability under measurement noise."""
+
+    def __init__(self, sums, passes, n_draws):
+        self.sums = sums
+        self.passes = passes
+        self.n_draws = n_draws
 
 
 class SelectResult:
@@ -550,6 +570,60 @@ class Context:
         any number of times after one launch."""
         self.accept_enqueue(source, thresholds, timepoints, list_threshold, list_capacity)
         return self.download_accept()
+
+    def accept_draws_enqueue(self, targets, sample_cells, thresholds, n_draws: int = 64, first_draw: int = 0,
+                             timepoints=None, store: str = "keep"):
+        """Enqueue the acceptance over thinning draws first_draw .. first_draw + n_draws - 1 on the stream of the last
+        launch (ecdna_ssa_ctx_accept_draws); download_accept_draws returns its results. Arguments as accept_draws()."""
+        L = _lib_with("ecdna_ssa_ctx_accept_draws", "acceptance over repeated thinnings")
+        if store not in ("keep", "timepoints"):
+            raise ValueError('store must be "keep" or "timepoints"')
+        tgt = np.ascontiguousarray(targets, dtype=np.uint64)
+        if tgt.ndim != 2 or tgt.shape[1] != self.params.hist_bins:
+            raise ValueError("targets must be [P][hist_bins]: one histogram of hist_bins entries per target")
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+        if thr.ndim != 2 or thr.shape[1] != 4:
+            raise ValueError("thresholds must be [Q][4]: ks, mean_rel, entropy_rel, frequency_diff per row")
+        for name, v in (("n_targets", tgt.shape[0]), ("n_thresholds", thr.shape[0]), ("n_draws", n_draws),
+                        ("first_draw", first_draw)):
+            _check_u32(name, v)
+        cells = self._u32_list("sample_cells", sample_cells, tgt.shape[0])
+        a = abi.AcceptDraws(struct_size=C.sizeof(abi.AcceptDraws), timepoints=int(store == "timepoints"),
+                            n_targets=tgt.shape[0], first_draw=int(first_draw), n_draws=int(n_draws),
+                            n_thresholds=thr.shape[0], timepoint_mask=timepoint_mask(timepoints))
+        a.target_hists = tgt.ctypes.data_as(C.POINTER(C.c_uint64))
+        a.sample_cells = cells.ctypes.data_as(C.POINTER(C.c_uint32))
+        a.thresholds = thr.ctypes.data_as(C.POINTER(abi.AcceptThreshold))
+        self._accept_draws_shape = None
+        _check(L.ecdna_ssa_ctx_accept_draws(self.h, C.byref(a)), "ecdna_ssa_ctx_accept_draws")
+        self._accept_draws_shape = (thr.shape[0], int(n_draws))
+
+    def download_accept_draws(self) -> AcceptDrawsResult:
+        """The results of the last accept_draws_enqueue (ecdna_ssa_ctx_download_accept_draws; synchronises)."""
+        shape = getattr(self, "_accept_draws_shape", None)
+        if shape is None:
+            raise EngineError("download_accept_draws before accept_draws")
+        Q, n_draws = shape
+        p = self.params
+        sums = np.zeros((Q, p.n_param_sets), dtype=np.uint64)
+        passes = np.zeros((p.n_replicates, Q), dtype=np.uint8)
+        _check(lib().ecdna_ssa_ctx_download_accept_draws(self.h, sums.ctypes.data,
+                                                         passes.ctypes.data if passes.size else None),
+               "ecdna_ssa_ctx_download_accept_draws")
+        return AcceptDrawsResult(sums, passes, n_draws)
+
+    def accept_draws(self, targets, sample_cells, thresholds, n_draws: int = 64, first_draw: int = 0, timepoints=None,
+                     store: str = "keep") -> AcceptDrawsResult:
+        """Acceptance over repeated thinnings of the kept samples (thinned acceptance mapping v1): for every replicate
+        and row of `thresholds` [Q][4], on how many of the thinning draws first_draw .. first_draw + n_draws - 1 the
+        replicate is accepted when target p is scored on sample_cells[p] of its kept cells — what rescore(targets,
+        sample_cells, [d] * P) and accept(ACCEPT_RESCORED, ...) give, summed over d, in one pass that stores no record.
+        store "keep": `targets` [P][hist_bins] against the kept sample, `timepoints` names the participating targets
+        (None: all, jointly); "timepoints": one target per timepoint of the timepoint keep block, as
+        rescore_timepoints and ACCEPT_RESCORED_TIMEPOINTS. The rescored records, accept's results and select's keys are
+        left as they are."""
+        self.accept_draws_enqueue(targets, sample_cells, thresholds, n_draws, first_draw, timepoints, store)
+        return self.download_accept_draws()
 
     def select(self, source: int, ranks=None, fractions=None, timepoints=None) -> SelectResult:
         """ABC thresholds on the GPU (ecdna_ssa_ctx_select, select mapping v1): the exact `ranks`-th smallest values

@@ -257,6 +257,24 @@ def pool_accepted(ctx, threshold: int, group=None, device=None):
     return t.cpu().numpy().view(np.uint64)
 
 
+def accept_draws(ctx, targets, sample_cells, thresholds, n_draws: int = 64, first_draw: int = 0, timepoints=None,
+                 store: str = "keep", group=None, device=None):
+    """Context.accept_draws over every rank's shard: the result's passes are the rank's own replicates', its sums
+    [Q][n_param_sets] u64 the whole run's, the same on every rank. One all-reduce (int64, sum) joins the shards' arrays:
+    integer sums, exact in any order. `device` as for select()."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    res = ctx.accept_draws(targets, sample_cells, thresholds, n_draws, first_draw, timepoints, store)
+    t = torch.from_numpy(res.sums.view(np.int64))  # (sums stay far below 2^63)
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    res.sums = t.cpu().numpy().view(np.uint64)
+    return res
+
+
 def pool_accepted_timepoints(ctx, threshold: int, group=None, device=None):
     """Context.pool_accepted_timepoints over every rank's shard: the whole run's posterior predictive histogram per
     timepoint, [T][n_param_sets][hist_bins] u64, the same on every rank. Each rank pools its own accepted replicates'

@@ -43,7 +43,12 @@
 extern "C" {
 #endif
 
-/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): the kept samples
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): acceptance over
+ * repeated thinnings of the kept samples — the block ecdna_ssa_accept_draws_t, ecdna_ssa_ctx_accept_draws and
+ * ecdna_ssa_ctx_download_accept_draws (below; thinned acceptance mapping v1): per replicate and threshold row, on how many
+ * of up to 64 thinning draws the replicate is accepted, counted in one pass that stores no record. A context that never
+ * calls them allocates and launches nothing new.
+ * Added within v13 (additive: no layout and no existing function changes, the version stays 13): the kept samples
  * rescored at each target's own number of measured cells — the block ecdna_ssa_rescore_t, ecdna_ssa_ctx_rescore_sized
  * and ecdna_ssa_ctx_rescore_timepoints_sized (below; thinning mapping v1). They write the records of
  * ecdna_ssa_ctx_rescore and _rescore_timepoints; a context that never calls them allocates and launches nothing new.
@@ -826,6 +831,65 @@ int ecdna_ssa_ctx_accept(ecdna_ssa_ctx* c, const ecdna_ssa_accept_t* a);
 int ecdna_ssa_ctx_download_accept(ecdna_ssa_ctx* c, uint64_t* out_counts, uint32_t* out_mask,
                                   uint64_t* out_n_accepted, uint64_t* out_ids,
                                   ecdna_rep_stats_t* out_list_stats);
+/* Acceptance over repeated thinnings of the kept samples (added within ABI v13). Thinning mapping v1 reserves a draw
+ * index d in 0 .. 63: 64 independent thinnings of one kept sample, and the share of them a replicate passes estimates
+ * its acceptance probability under measurement noise — the weight of the simulation in ABC with measurement noise, the
+ * mean of the acceptance indicator over the sampling of the patient's m1 cells. The call below counts that share in one
+ * pass over the kept samples and keeps only the counts: no record is stored, no target slot is spent on a draw, and
+ * several targets (two biopsies, every timepoint) are accepted jointly on each draw.
+ *
+ * Thinned acceptance mapping v1. A call names a store (timepoints = 0: the keep block's one slice; 1: the timepoint
+ * keep block's T slices), target histograms, a number of measured cells per target, Q <= 32 threshold rows, a
+ * timepoint mask and a draw range first_draw .. first_draw + n_draws - 1 inside 0 .. 63.
+ *  - Keep store: n_targets = P in 1 .. 64 targets for the same slice; for acceptance they are the timepoints (T = P), as
+ *    for source 12. Timepoint store: exactly one target per timepoint (n_targets == T), as for source 13.
+ *  - For one draw d, every target is scored on the thinned sample that thinning mapping v1 defines for
+ *    (sample_cells[slot], d). Nothing in that mapping changes: the same key per slice (seed, or seed_g), the same stream
+ *    tag, the same grouping (targets with equal m1 see the same thinned sample), the same whole-sample rule when
+ *    m1 >= a + b, the same guard records.
+ *  - Replicate i passes row q on draw d iff acceptance mapping v1 accepts it on those records: rule 1 (errors) as source
+ *    12 for the keep store and as source 13 for the timepoint store (on a passage context: per participating phase);
+ *    rule 2 (distances) over the participating targets or timepoints. A tie passes, +inf switches a statistic off, a
+ *    NaN fails.
+ *  - passes[i][q], u8, laid out [n][Q]: the number of draws of the range that replicate i passes under row q (0 .. 64).
+ *  - sums[Q][n_param_sets], u64: per row and GLOBAL parameter set, the sum of passes over the call's replicates.
+ *    Integers: shards' arrays sum to the whole run's.
+ *  - By construction passes[i][q] equals the sum over d of bit q of the mask that ecdna_ssa_ctx_rescore_sized /
+ *    _rescore_timepoints_sized at draw d, followed by ecdna_ssa_ctx_accept on source 12 / 13 with the same thresholds
+ *    and mask, would give. That equality is part of the contract: the records are never stored, but they are the same
+ *    numbers (the same f64 operations in the same order), so a threshold that ecdna_ssa_ctx_select took from one draw's
+ *    records cuts in exactly the same place.
+ *  - Nothing depends on chunk, shard, grid or device.
+ *
+ * The call owns its buffers (target CDFs and scalars, passes, sums) and leaves untouched the rescored records of both
+ * stores and their validity, the keys ecdna_ssa_ctx_select cached, the results of ecdna_ssa_ctx_accept and what
+ * ecdna_ssa_ctx_pool_accepted* pool. It needs no earlier rescore. */
+typedef struct {
+    uint32_t struct_size;          /* sizeof(ecdna_ssa_accept_draws_t) */
+    uint32_t timepoints;           /* 0: the keep block's store, 1: the timepoint keep block's */
+    uint32_t n_targets;            /* keep store: P, 1 .. 64; timepoint store: T */
+    const uint64_t* target_hists;  /* host [n_targets][hist_bins], no all-zero row */
+    const uint32_t* sample_cells;  /* host [n_targets], required; each 1 .. keep_cells of the store */
+    uint32_t first_draw;           /* first thinning draw of the range */
+    uint32_t n_draws;              /* 1 .. 64, first_draw + n_draws <= 64 */
+    uint32_t n_thresholds;         /* Q, 1 .. 32 */
+    const ecdna_accept_threshold_t* thresholds; /* host, [Q] */
+    uint64_t timepoint_mask;       /* bit t = target (keep store) or timepoint t takes part; 0 = all */
+    uint64_t reserved;             /* must be 0 */
+} ecdna_ssa_accept_draws_t;
+/* Enqueue the pass on the stream of the last launch, as ecdna_ssa_ctx_accept does. Asynchronous; a later call replaces
+ * the results, a relaunch invalidates them.
+ * ECDNA_E_INVALID (the message names the field): NULL c or block, a wrong struct_size, reserved != 0, timepoints above 1,
+ * n_targets outside 1 .. 64 or different from T on the timepoint store, NULL target_hists, an all-zero target row,
+ * sample_cells NULL or an entry outside 1 .. keep_cells, n_draws outside 1 .. 64, first_draw + n_draws > 64,
+ * n_thresholds outside 1 .. 32, NULL thresholds, a negative or NaN threshold, timepoint_mask bits at or above T,
+ * n_replicates >= 2^32.
+ * ECDNA_E_STATE: before a launch; a context without the named block.
+ * ECDNA_E_NOMEM: the call's buffers do not fit; the context stays usable and its other outputs intact. */
+int ecdna_ssa_ctx_accept_draws(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a);
+/* The results of the last ecdna_ssa_ctx_accept_draws (ECDNA_E_STATE before one, and after a relaunch until the next).
+ * Synchronises. Either pointer may be NULL. out_sums [Q][n_param_sets], out_passes [n_replicates][Q]. */
+int ecdna_ssa_ctx_download_accept_draws(ecdna_ssa_ctx* c, uint64_t* out_sums, uint8_t* out_passes);
 /* ABC thresholds on the GPU (added within ABI v13): exact order statistics of the four distances over the statistics a
  * context already holds, so that "keep the closest 1 % of the runs" needs neither a download of every record nor, on
  * several GPUs, a gather of them. An 8-bit radix select: each of eight passes leaves a small integer histogram, and
