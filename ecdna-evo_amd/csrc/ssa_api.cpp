@@ -2,7 +2,7 @@
 // device-resident run contexts, chunking by HBM capacity, and launches of the
 // stepper and end-of-run kernels (ssa_kernels.hip, ssa_hist.hip, ssa_subsample.hip, ssa_snapstats.hip,
 // ssa_passage.hip, ssa_cohort.hip), of the post-launch acceptance pass (ssa_accept.hip) and of the passes over the kept
-// samples (ssa_rescore.hip, ssa_thin.hip, ssa_accept_draws.hip). The kept samples of the keep block and of the timepoint keep block lie in one kind of store
+// samples (ssa_rescore.hip, ssa_thin.hip, ssa_accept_draws.hip, ssa_pool_draws.hip). The kept samples of the keep block and of the timepoint keep block lie in one kind of store
 // (KeptStore), and every pass over them has one implementation, which the two blocks' entry points call.
 //
 // This file replaces, for one GPU, the per-replicate driver loop of the
@@ -23,6 +23,7 @@
 
 #include "../../include/ecdna_ssa.h"
 #include "ssa_accept_draws.hpp"
+#include "ssa_pool_draws.hpp"
 #include "ssa_cohort.hpp"
 #include "ssa_keep.hpp"
 #include "ssa_launch.h"
@@ -395,6 +396,9 @@ struct ecdna_ssa_ctx {
     bool adr_valid = false, adr_pending = false;
     uint32_t adr_rows = 0;
     hipStream_t adr_stream = nullptr;
+    // the pooling over thinning draws (ecdna_ssa_ctx_pool_draws): the call's own target CDFs and scalars, and its pooled
+    // arrays, thinned [targets][sets][bins] then kept [slices][sets][bins] u64. The call is synchronous and holds no result.
+    AcceptBuf pdr_cdf, pdr_scalars, pdr_pool;
 };
 
 namespace {
@@ -427,7 +431,8 @@ void free_ctx(ecdna_ssa_ctx* c) {
     for (AcceptBuf* b : {&c->acc_mask, &c->acc_counts, &c->acc_blocks, &c->acc_ids, &c->acc_list, &c->sel_keys,
                          &c->sel_hist, &c->pool_hist, &c->gat_index, &c->gat_headers, &c->gat_cells, &c->kept.stats,
                          &c->kept.cdf, &c->kept.scalars, &c->kept_tp.stats, &c->kept_tp.cdf, &c->kept_tp.scalars,
-                         &c->adr_cdf, &c->adr_scalars, &c->adr_passes, &c->adr_sums})
+                         &c->adr_cdf, &c->adr_scalars, &c->adr_passes, &c->adr_sums, &c->pdr_cdf, &c->pdr_scalars,
+                         &c->pdr_pool})
         if (b->ptr) (void)hipFree(b->ptr);
     delete c;
 }
@@ -2185,6 +2190,109 @@ int ecdna_ssa_ctx_download_accept_draws(ecdna_ssa_ctx* c, uint64_t* out_sums, ui
         TRY(to_host(out_sums, static_cast<const uint64_t*>(c->adr_sums.ptr), (uint64_t)c->adr_rows * p.n_param_sets));
     if (out_passes && p.n_replicates)
         TRY(to_host(out_passes, static_cast<const uint8_t*>(c->adr_passes.ptr), p.n_replicates * c->adr_rows));
+    return ECDNA_OK;
+}
+
+// ---- the accepted thinnings pooled (thinned pooling mapping v1): the verdict of ecdna_ssa_ctx_accept_draws for one
+// row and the pools of what passes it, in one synchronous pass on buffers of its own ----
+
+int ecdna_ssa_ctx_pool_draws(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a, uint32_t threshold,
+                             uint64_t* out_thinned, uint64_t* out_kept) {
+    namespace pd = ecdna::pool_draws;
+    const char* who = "ecdna_ssa_ctx_pool_draws";
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!a) return fail(ECDNA_E_INVALID, "pool_draws: the block is NULL");
+    const ecdna_ssa_params_t& p = c->p;
+    const bool timepoints = a->timepoints == 1u;
+    const KeptStore* s = timepoints ? &c->kept_tp : &c->kept;
+    const std::string bad = pd::invalid(p.hist_bins, s->m ? s->m : ecdna::kMaxSubsampleCells, c->kept_tp.T,
+                                        p.n_replicates, *a, threshold, out_thinned, out_kept);
+    if (!bad.empty()) return fail(ECDNA_E_INVALID, bad);
+    if (!s->m)
+        return fail(ECDNA_E_STATE, timepoints ? std::string("pool_draws") + kNeedsTimepoints
+                                              : std::string("pool_draws: the kept samples need ecdna_ssa_ctx_create_keep"));
+    TRY(ctx_launched(c, "pool_draws before launch"));
+
+    const uint32_t bins = p.hist_bins, P = a->n_targets, sets = p.n_param_sets;
+    const uint64_t n = p.n_replicates;
+    const pd::Plan pl = pd::plan(bins, s->m, timepoints, P, a->sample_cells, a->timepoint_mask);
+    const uint32_t S = pl.pool.n_slices;
+    const uint64_t thinned_words = pd::thinned_words(P, sets, bins), kept_words = pd::kept_words(S, sets, bins);
+    if (out_thinned) std::fill(out_thinned, out_thinned + thinned_words, 0ull);
+    if (out_kept) std::fill(out_kept, out_kept + kept_words, 0ull);
+    if (!n) return ECDNA_OK;
+    const bool phases = timepoints && c->n_passages;
+    TRY(hipSetDevice(c->device));
+    hipStream_t st = c->last_stream;
+    TRY(accept_reserve(&c->pdr_cdf, pd::cdf_bytes(P, bins), "target CDFs", who));
+    TRY(accept_reserve(&c->pdr_scalars, pd::scalars_bytes(P), "target scalars", who));
+    TRY(accept_reserve(&c->pdr_pool, pd::pooled_bytes(P, S, sets, bins), "pooled histograms", who));
+    unsigned long long* d_thinned = static_cast<unsigned long long*>(c->pdr_pool.ptr);
+    unsigned long long* d_kept = d_thinned + thinned_words;
+    TRY(hipMemsetAsync(c->pdr_pool.ptr, 0, pd::pooled_bytes(P, S, sets, bins), st));
+    // (the call synchronises below, so the uploads' host copies live on its stack)
+    std::vector<double> host_cdf((uint64_t)P * bins), host_scalars((uint64_t)P * 3u);
+    summarize_targets(a->target_hists, P, bins, host_cdf.data(), host_scalars.data());
+    TRY(hipMemcpyAsync(c->pdr_cdf.ptr, host_cdf.data(), pd::cdf_bytes(P, bins), hipMemcpyHostToDevice, st));
+    const hipError_t up =
+        hipMemcpyAsync(c->pdr_scalars.ptr, host_scalars.data(), pd::scalars_bytes(P), hipMemcpyHostToDevice, st);
+    if (up != hipSuccess) {
+        (void)hipStreamSynchronize(st);  // (the first upload may still read host_cdf)
+        TRY(up);
+    }
+
+    ecdna::PoolDrawsArgs k{};
+    k.headers = s->d_headers;
+    k.cells = s->d_cells;
+    // rule 1 as ecdna_ssa_ctx_accept_draws has it: the one summary, or on a passage context every participating phase's
+    k.summaries = phases ? c->d_pas_summ : c->d_summ;
+    k.err_stride = phases ? n : 0u;
+    k.target_cdf = static_cast<const double*>(c->pdr_cdf.ptr);
+    k.target_scalars = static_cast<const double*>(c->pdr_scalars.ptr);
+    k.thinned = out_thinned ? d_thinned : nullptr;
+    k.kept = out_kept ? d_kept : nullptr;
+    k.slice_mask = pl.verdict.slice_mask;
+    k.rid0 = p.first_replicate;
+    k.rid_stride = rid_stride(p);
+    k.reps_per_set = p.reps_per_set;
+    k.n = (uint32_t)n;
+    k.m = s->m;
+    k.bins = bins;
+    k.n_slices = S;
+    k.n_targets = P;
+    k.v_groups = pl.verdict.n_groups;
+    k.p_groups = pl.pool.n_groups;
+    k.n_sets = sets;
+    k.first_draw = a->first_draw;
+    k.n_draws = a->n_draws;
+    k.reps_per_block = pass_reps_per_block(c, k.n, pl.lds.waves);
+    k.table_slots = pl.lds.table_slots;
+    k.scratch_words = pl.lds.scratch_words;
+    k.wave_words = ecdna::pool_draws_wave_words(bins, pl.lds.table_slots);
+    const ecdna_accept_threshold_t& t = a->thresholds[threshold];
+    k.thr[0] = t.ks;
+    k.thr[1] = t.mean_rel;
+    k.thr[2] = t.entropy_rel;
+    k.thr[3] = t.frequency_diff;
+    // the key and the stream each slice's own samples were drawn under (launch_thin_pass)
+    for (uint32_t i = 0; i < S; ++i) {
+        k.slice_seed[i] = phases ? passage_seed(p.seed, i) : p.seed;
+        k.slice_tag[i] = ecdna::thin::stream_tag((timepoints && !phases) ? i + 1u : 0u, 0u);
+    }
+    std::copy_n(pl.verdict.slice_group, ecdna::kMaxCohortTargets + 1u, k.v_slice_group);
+    std::copy_n(pl.verdict.group_m, ecdna::kMaxCohortTargets, k.v_group_m);
+    std::copy_n(pl.verdict.group_offset, ecdna::kMaxCohortTargets + 1u, k.v_group_offset);
+    std::copy_n(pl.verdict.group_targets, ecdna::kMaxCohortTargets, k.v_group_targets);
+    std::copy_n(pl.pool.slice_group, ecdna::kMaxCohortTargets + 1u, k.p_slice_group);
+    std::copy_n(pl.pool.group_m, ecdna::kMaxCohortTargets, k.p_group_m);
+    std::copy_n(pl.pool.group_offset, ecdna::kMaxCohortTargets + 1u, k.p_group_offset);
+    std::copy_n(pl.pool.group_targets, ecdna::kMaxCohortTargets, k.p_group_targets);
+    const hipError_t le = ecdna::launch_pool_draws(k, st);
+    const hipError_t se = hipStreamSynchronize(st);  // (also when the launch was refused: the uploads read the stack)
+    TRY(le);
+    TRY(se);
+    if (out_thinned) TRY(to_host(out_thinned, reinterpret_cast<const uint64_t*>(d_thinned), thinned_words));
+    if (out_kept) TRY(to_host(out_kept, reinterpret_cast<const uint64_t*>(d_kept), kept_words));
     return ECDNA_OK;
 }
 

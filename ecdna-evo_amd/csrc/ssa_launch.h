@@ -1,7 +1,7 @@
 // ssa_launch.h — host-visible kernel argument blocks and launch wrappers shared by the device
 // code (steppers: ssa_kernels.hip, ssa_refdraws.hip; end-of-run passes: ssa_hist.hip,
 // ssa_subsample.hip, ssa_snapstats.hip, ssa_passage.hip, ssa_cohort.hip; the passes over the kept samples:
-// ssa_rescore.hip, ssa_thin.hip, ssa_accept_draws.hip; the acceptance pass: ssa_accept.hip; the select passes:
+// ssa_rescore.hip, ssa_thin.hip, ssa_accept_draws.hip, ssa_pool_draws.hip; the acceptance pass: ssa_accept.hip; the select passes:
 // ssa_select.hip) and ssa_api.cpp
 // (the C ABI).
 #pragma once
@@ -370,6 +370,50 @@ struct AcceptDrawsArgs {
 };
 static_assert(sizeof(AcceptDrawsArgs) <= 4096, "the argument block of a launch");
 
+// The pooling pass over thinning draws (ssa_pool_draws.hip; ecdna_ssa_ctx_pool_draws, thinned pooling mapping v1): per
+// replicate the 64-bit set of the draws it passes under the one threshold row thr — AcceptDrawsArgs' verdict for that
+// row, over the groups v_* of the participating slices — and then, for a replicate that passes any, the pools over
+// every slice of the store: kept[s] takes popcount(set) times the slice's full histogram, thinned[target] the thinned
+// histograms of the passing draws of the target's group among p_* (the pooling grouping: every slot, whatever the
+// mask). Store, error words, seeds, tags and tables lie as AcceptDrawsArgs'. Either output may be null: it is then
+// neither computed nor written.
+struct PoolDrawsArgs {
+    const uint2* headers;                 // [n_slices][n]
+    const uint16_t* cells;                // [n_slices][n][m]
+    const ecdna_rep_summary_t* summaries;
+    const double* target_cdf;             // [targets][bins]
+    const double* target_scalars;         // [targets][3]
+    unsigned long long* thinned;          // [n_targets][n_sets][bins] or null, zeroed before the launch
+    unsigned long long* kept;             // [n_slices][n_sets][bins] or null, zeroed before the launch
+    uint64_t err_stride;
+    uint64_t slice_mask;                  // the verdict's participating slices (bits below n_slices, never 0)
+    uint64_t rid0, rid_stride, reps_per_set;
+    uint32_t n;                           // replicates of the run
+    uint32_t m;                           // the store's kept cells per sample
+    uint32_t bins;
+    uint32_t n_slices;                    // 1 .. 64
+    uint32_t n_targets;                   // rows of target_cdf, 1 .. kMaxCohortTargets
+    uint32_t v_groups, p_groups;          // over all slices, 1 .. n_targets each
+    uint32_t n_sets;
+    uint32_t first_draw, n_draws;         // first_draw + n_draws <= 64, n_draws >= 1
+    uint32_t reps_per_block;
+    uint32_t table_slots;                 // as ThinArgs', for the largest m' of either grouping
+    uint32_t scratch_words;
+    uint32_t wave_words;                  // per-wave u32 words of LDS: pool_draws_wave_words(bins, table_slots)
+    double thr[4];                        // the row: ks, mean_rel, entropy_rel, frequency_diff (+inf: off)
+    uint64_t slice_seed[kMaxCohortTargets];
+    uint32_t slice_tag[kMaxCohortTargets];        // thin::stream_tag(field, 0)
+    uint32_t v_slice_group[kMaxCohortTargets + 1];
+    uint32_t v_group_m[kMaxCohortTargets];
+    uint32_t v_group_offset[kMaxCohortTargets + 1];
+    uint32_t v_group_targets[kMaxCohortTargets];
+    uint32_t p_slice_group[kMaxCohortTargets + 1];
+    uint32_t p_group_m[kMaxCohortTargets];
+    uint32_t p_group_offset[kMaxCohortTargets + 1];
+    uint32_t p_group_targets[kMaxCohortTargets];
+};
+static_assert(sizeof(PoolDrawsArgs) <= 4096, "the argument block of a launch");
+
 // The select passes over the whole run (ssa_select.hip; ecdna_ssa_ctx_select / _select_digits, select mapping v1): an
 // 8-bit radix select of order statistics of the four distances. ssa_select_keys writes every replicate's key per
 // distance once per (source, timepoint mask), from records and error words that lie as AcceptArgs' do;
@@ -503,6 +547,19 @@ inline uint32_t rescore_waves(uint32_t bins, size_t* lds_bytes) {
 inline uint32_t thin_waves(uint32_t bins, uint32_t table_slots, size_t* lds_bytes) {
     return pass_waves(0, (2u * (size_t)bins + cohort_scratch_words(bins, table_slots)) * 4u, lds_bytes);
 }
+// ssa_pool_draws: ssa_thin's per-wave plan plus the wave's pooled accumulator, [bins] u32 rounded up to an even number
+// of words (the next wave's CDF stays 8-byte aligned). The accumulator lives only while samples are drawn and none is
+// scored, so it lies in the scratch behind the table, where the CDF's upper part would be, and the plan grows only by
+// the words that do not fit there: none when 2 * bins >= table_slots + bins (ssa_thin's plan and occupancy, e.g. 1,025
+// bins beside keep_cells = 200), all of them at 2,048 bins and keep_cells = 4096 (8 + 8 + 16 + 8 = 40 KiB, one wave
+// per workgroup).
+inline uint32_t pool_draws_wave_words(uint32_t bins, uint32_t table_slots) {
+    const uint32_t scratch = cohort_scratch_words(bins, table_slots), need = table_slots + bins + (bins & 1u);
+    return 2u * bins + (need > scratch ? need : scratch);
+}
+inline uint32_t pool_draws_waves(uint32_t bins, uint32_t table_slots, size_t* lds_bytes) {
+    return pass_waves(0, (size_t)pool_draws_wave_words(bins, table_slots) * 4u, lds_bytes);
+}
 // ssa_pool_accepted: the workgroup's u64 sum of the accepted samples' histograms (one parameter set at a time), 16 KiB
 // at 2,048 bins; its waves keep nothing of their own
 inline uint32_t pool_accepted_waves(uint32_t bins, size_t* lds_bytes) {
@@ -534,6 +591,9 @@ hipError_t launch_accept_list(const AcceptArgs& a, hipStream_t stream);
 // The thinned acceptance pass (ssa_accept_draws.hip): ssa_thin's LDS plan (thin_waves) for a.table_slots; a.sums zeroed
 // on the stream before it. A block that disagrees with the plan is refused: hipErrorInvalidValue.
 hipError_t launch_accept_draws(const AcceptDrawsArgs& a, hipStream_t stream);
+// The pooling pass over thinning draws (ssa_pool_draws.hip): pool_draws_waves' LDS plan for a.table_slots; a.thinned
+// and a.kept zeroed on the stream before it. A block that disagrees with the plan is refused: hipErrorInvalidValue.
+hipError_t launch_pool_draws(const PoolDrawsArgs& a, hipStream_t stream);
 // The select passes (ssa_select.hip): the keys of every replicate (a.n > 0), and one digit pass over them (a.hist zeroed
 // on the stream before it; the dynamic LDS table is 1 KiB per group of the distance with most, 32 KiB at most).
 hipError_t launch_select_keys(const SelectKeyArgs& a, hipStream_t stream);

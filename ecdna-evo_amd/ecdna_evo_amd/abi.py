@@ -243,6 +243,10 @@ class AcceptDraws(C.Structure):
 
 
 ACCEPT_DRAWS_MAX = 64  # thinning draws of one kept sample: the draw index takes 6 bits
+# int ecdna_ssa_ctx_pool_draws(c, const ecdna_ssa_accept_draws_t* a, uint32_t threshold, uint64_t* out_thinned,
+# uint64_t* out_kept) (added within ABI v13; thinned pooling mapping v1): the block of accept_draws, one row of it, and
+# the host arrays [n_targets][n_param_sets][hist_bins] and [n_slices][n_param_sets][hist_bins] (either may be NULL)
+POOL_DRAWS_ARGTYPES = [C.c_void_p, C.POINTER(AcceptDraws), C.c_uint32, C.c_void_p, C.c_void_p]
 
 
 class Select(C.Structure):

@@ -58,6 +58,7 @@ EXPORTS = [
     "ecdna_ssa_ctx_download_accept",
     "ecdna_ssa_ctx_accept_draws",
     "ecdna_ssa_ctx_download_accept_draws",
+    "ecdna_ssa_ctx_pool_draws",
     "ecdna_ssa_ctx_select",
     "ecdna_ssa_ctx_select_digits",
     "ecdna_ssa_ctx_download_rng_words",
@@ -220,6 +221,10 @@ def lib():
         L.ecdna_ssa_ctx_accept_draws.restype = C.c_int
         L.ecdna_ssa_ctx_download_accept_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ecdna_ssa_ctx_download_accept_draws.restype = C.c_int
+    # (likewise added within v13: the accepted thinnings pooled)
+    if hasattr(L, "ecdna_ssa_ctx_pool_draws"):
+        L.ecdna_ssa_ctx_pool_draws.argtypes = list(abi.POOL_DRAWS_ARGTYPES)
+        L.ecdna_ssa_ctx_pool_draws.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -371,6 +376,18 @@ class AcceptDrawsResult:
         self.sums = sums
         self.passes = passes
         self.n_draws = n_draws
+
+
+class PoolDrawsResult:
+    """What ecdna_ssa_ctx_pool_draws returns (thinned pooling mapping v1, include/ecdna_ssa.h), per global parameter set:
+    thinned [n_targets][n_sets][hist_bins] u64, the pooled histograms of each slot's thinned samples on the draws its
+    replicates pass under the threshold row — the posterior predictive of the measurement; kept
+    [n_slices][n_sets][hist_bins] u64, the whole kept samples weighted by the number of passing draws. Shards' arrays
+    sum to the whole run's."""
+
+    def __init__(self, thinned, kept):
+        self.thinned = thinned
+        self.kept = kept
 
 
 class SelectResult:
@@ -576,6 +593,13 @@ class Context:
         """Enqueue the acceptance over thinning draws first_draw .. first_draw + n_draws - 1 on the stream of the last
         launch (ecdna_ssa_ctx_accept_draws); download_accept_draws returns its results. Arguments as accept_draws()."""
         L = _lib_with("ecdna_ssa_ctx_accept_draws", "acceptance over repeated thinnings")
+        a, _alive = self._accept_draws_block(targets, sample_cells, thresholds, n_draws, first_draw, timepoints, store)
+        self._accept_draws_shape = None
+        _check(L.ecdna_ssa_ctx_accept_draws(self.h, C.byref(a)), "ecdna_ssa_ctx_accept_draws")
+        self._accept_draws_shape = (int(a.n_thresholds), int(n_draws))
+
+    def _accept_draws_block(self, targets, sample_cells, thresholds, n_draws, first_draw, timepoints, store):
+        """The block ecdna_ssa_accept_draws_t of accept_draws' arguments, and the arrays it points into."""
         if store not in ("keep", "timepoints"):
             raise ValueError('store must be "keep" or "timepoints"')
         tgt = np.ascontiguousarray(targets, dtype=np.uint64)
@@ -594,9 +618,7 @@ class Context:
         a.target_hists = tgt.ctypes.data_as(C.POINTER(C.c_uint64))
         a.sample_cells = cells.ctypes.data_as(C.POINTER(C.c_uint32))
         a.thresholds = thr.ctypes.data_as(C.POINTER(abi.AcceptThreshold))
-        self._accept_draws_shape = None
-        _check(L.ecdna_ssa_ctx_accept_draws(self.h, C.byref(a)), "ecdna_ssa_ctx_accept_draws")
-        self._accept_draws_shape = (thr.shape[0], int(n_draws))
+        return a, (tgt, cells, thr)
 
     def download_accept_draws(self) -> AcceptDrawsResult:
         """The results of the last accept_draws_enqueue (ecdna_ssa_ctx_download_accept_draws; synchronises)."""
@@ -624,6 +646,27 @@ class Context:
         left as they are."""
         self.accept_draws_enqueue(targets, sample_cells, thresholds, n_draws, first_draw, timepoints, store)
         return self.download_accept_draws()
+
+    def pool_draws(self, targets, sample_cells, thresholds, threshold: int = 0, n_draws: int = 64, first_draw: int = 0,
+                   timepoints=None, store: str = "keep") -> PoolDrawsResult:
+        """The accepted thinnings pooled (ecdna_ssa_ctx_pool_draws, thinned pooling mapping v1): the arguments of
+        accept_draws() and one row `threshold` of `thresholds`. Per global parameter set, .thinned[slot] sums the
+        histograms of the thinned samples of sample_cells[slot] cells over the replicates and the draws that pass the
+        row — every slot, those `timepoints` leaves out of the verdict included — and .kept[slice] the whole kept
+        samples times the number of passing draws (one slice on store "keep", T on "timepoints"). Synchronous; needs
+        neither an earlier accept_draws nor a rescore and leaves their results as they are."""
+        L = _lib_with("ecdna_ssa_ctx_pool_draws", "pooling over thinning draws")
+        a, _alive = self._accept_draws_block(targets, sample_cells, thresholds, n_draws, first_draw, timepoints, store)
+        _check_u32("threshold", threshold)
+        if int(threshold) >= int(a.n_thresholds):
+            raise ValueError(f"threshold = {threshold} must be a row of thresholds, < {int(a.n_thresholds)}")
+        p = self.params
+        slices = int(a.n_targets) if store == "timepoints" else 1
+        thinned = np.zeros((int(a.n_targets), p.n_param_sets, p.hist_bins), dtype=np.uint64)
+        kept = np.zeros((slices, p.n_param_sets, p.hist_bins), dtype=np.uint64)
+        _check(L.ecdna_ssa_ctx_pool_draws(self.h, C.byref(a), int(threshold), thinned.ctypes.data, kept.ctypes.data),
+               "ecdna_ssa_ctx_pool_draws")
+        return PoolDrawsResult(thinned, kept)
 
     def select(self, source: int, ranks=None, fractions=None, timepoints=None) -> SelectResult:
         """ABC thresholds on the GPU (ecdna_ssa_ctx_select, select mapping v1): the exact `ranks`-th smallest values

@@ -275,6 +275,26 @@ def accept_draws(ctx, targets, sample_cells, thresholds, n_draws: int = 64, firs
     return res
 
 
+def pool_draws(ctx, targets, sample_cells, thresholds, threshold: int = 0, n_draws: int = 64, first_draw: int = 0,
+               timepoints=None, store: str = "keep", group=None, device=None):
+    """Context.pool_draws over every rank's shard: the whole run's pooled histograms, thinned
+    [n_targets][n_param_sets][hist_bins] and kept [n_slices][n_param_sets][hist_bins] u64, the same on every rank. Each
+    rank pools its own replicates and one all-reduce (int64, sum) per array joins them: integer sums, exact in any
+    order. `device` as for select()."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    res = ctx.pool_draws(targets, sample_cells, thresholds, threshold, n_draws, first_draw, timepoints, store)
+    for name in ("thinned", "kept"):
+        t = torch.from_numpy(getattr(res, name).view(np.int64))  # (counts stay far below 2^63)
+        if device is not None:
+            t = t.to(device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        setattr(res, name, t.cpu().numpy().view(np.uint64))
+    return res
+
+
 def pool_accepted_timepoints(ctx, threshold: int, group=None, device=None):
     """Context.pool_accepted_timepoints over every rank's shard: the whole run's posterior predictive histogram per
     timepoint, [T][n_param_sets][hist_bins] u64, the same on every rank. Each rank pools its own accepted replicates'

@@ -43,7 +43,12 @@
 extern "C" {
 #endif
 
-/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): acceptance over
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): the accepted
+ * thinnings pooled — ecdna_ssa_ctx_pool_draws (below; thinned pooling mapping v1): per global parameter set, the
+ * histograms of the thinned samples on the draws that pass one threshold row of ecdna_ssa_accept_draws_t, and the whole
+ * kept samples weighted by the number of passing draws, in one synchronous pass. A context that never calls it allocates
+ * and launches nothing new.
+ * Added within v13 (additive: no layout and no existing function changes, the version stays 13): acceptance over
  * repeated thinnings of the kept samples — the block ecdna_ssa_accept_draws_t, ecdna_ssa_ctx_accept_draws and
  * ecdna_ssa_ctx_download_accept_draws (below; thinned acceptance mapping v1): per replicate and threshold row, on how many
  * of up to 64 thinning draws the replicate is accepted, counted in one pass that stores no record. A context that never
@@ -890,6 +895,56 @@ int ecdna_ssa_ctx_accept_draws(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t*
 /* The results of the last ecdna_ssa_ctx_accept_draws (ECDNA_E_STATE before one, and after a relaunch until the next).
  * Synchronises. Either pointer may be NULL. out_sums [Q][n_param_sets], out_passes [n_replicates][Q]. */
 int ecdna_ssa_ctx_download_accept_draws(ecdna_ssa_ctx* c, uint64_t* out_sums, uint8_t* out_passes);
+/* The accepted thinnings pooled (added within ABI v13): the posterior predictive check of ABC with measurement noise.
+ * ecdna_ssa_ctx_accept_draws gives a replicate its weight, the number of thinning draws it passes; this call pools what
+ * was accepted. The pseudo-data that were actually accepted are the thinned samples of m1 cells on the passing draws:
+ * their pooled histogram is the posterior predictive of the measurement itself. It is not the weighted pool of the kept
+ * samples scaled by m1 / m: conditioning on "this draw passed" selects thinnings that resemble the target.
+ *
+ * Thinned pooling mapping v1.
+ *  - The block means what it means for ecdna_ssa_ctx_accept_draws: the store (the keep block's one slice or the
+ *    timepoint keep block's T slices), n_targets slots (the targets of the keep store, or one target per timepoint),
+ *    sample_cells[slot], the draw range, the Q threshold rows and timepoint_mask. threshold is a row q < Q.
+ *  - Verdict. Replicate i passes row q on draw d exactly when thinned acceptance mapping v1 says so: the error rule, the
+ *    participating slots, ties, +inf, NaN and guard records that pass are all as in that mapping. Nothing of that mapping
+ *    or of thinning mapping v1 changes.
+ *  - out_thinned[slot][s], for every slot — slots the mask leaves out of the verdict are included: a held-out biopsy or
+ *    timepoint is predicted, not conditioned on. It is the sum, over the call's replicates i of global set s and over
+ *    the draws d of the range that i passes under row q, of the clipped histogram of the slot's scored sample on draw d:
+ *    the sample thinning mapping v1 defines for (sample_cells[slot], d) on the slot's slice, under the same key, stream
+ *    tag and draw index; when m1 >= a + b it is the whole kept sample, on every passing draw. Binning is that of
+ *    ecdna_ssa_ctx_pool_accepted: bin 0 holds the N- cells, true copy numbers are clipped at hist_bins - 1. A guard
+ *    header, a size the plan refuses and the 2^16-draw guard add nothing.
+ *  - out_kept[slice][s], for every slice (n_slices is 1 on the keep store and T on the timepoint store): the sum over
+ *    the replicates i of set s of passes[i][q] times the histogram of i's whole kept sample of the slice, binned the
+ *    same way. A guard header adds nothing.
+ *  - Contracts, equalities of integers.
+ *    K1. out_kept equals the sum over d of ecdna_ssa_ctx_pool_accepted(q) (respectively _pool_accepted_timepoints(q))
+ *        taken after the sized rescore at draw d and ecdna_ssa_ctx_accept on source 12 / 13 with the same thresholds and
+ *        mask.
+ *    K2. For a slot with sample_cells[slot] == keep_cells of its store, so that every replicate is scored whole,
+ *        out_thinned[slot] equals out_kept[slice of the slot].
+ *    K3. The bin sum of out_thinned[slot][s] equals the sum over i in s of passes[i][q] x min(sample_cells[slot],
+ *        a_i + b_i), the term being 0 under a guard header; passes is that of ecdna_ssa_ctx_accept_draws with the same
+ *        block.
+ *    K4. Targets with equal m1 on one slice add the same thinned histograms to their rows.
+ *    K5. Shards' arrays sum to the whole run's. Nothing depends on chunk, shard, grid or device.
+ *
+ * The call owns its buffers: target CDFs and scalars, and the two pooled arrays, (n_targets + n_slices) x n_param_sets x
+ * hist_bins x 8 bytes, allocated at the first call, grown by later ones and freed at destroy. It needs neither an earlier
+ * ecdna_ssa_ctx_accept_draws nor a rescore, and leaves untouched the results of ecdna_ssa_ctx_accept_draws and
+ * ecdna_ssa_ctx_accept, the rescored records of both stores and their validity, the keys ecdna_ssa_ctx_select cached and
+ * what ecdna_ssa_ctx_pool_accepted* pool. A relaunch invalidates nothing of this call: it holds no result.
+ *
+ * Synchronous, as ecdna_ssa_ctx_pool_accepted is; runs on the stream of the last launch. out_thinned: host
+ * [n_targets][n_param_sets][hist_bins] or NULL; out_kept: host [n_slices][n_param_sets][hist_bins] or NULL; an output
+ * that is NULL is not computed.
+ * ECDNA_E_INVALID (the message names the field): everything ecdna_ssa_ctx_accept_draws refuses, with the same messages;
+ * threshold >= n_thresholds; both outputs NULL.
+ * ECDNA_E_STATE: before a launch; a context without the named block.
+ * ECDNA_E_NOMEM: the call's buffers do not fit; the context stays usable and its other outputs intact. */
+int ecdna_ssa_ctx_pool_draws(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a, uint32_t threshold,
+                             uint64_t* out_thinned, uint64_t* out_kept);
 /* ABC thresholds on the GPU (added within ABI v13): exact order statistics of the four distances over the statistics a
  * context already holds, so that "keep the closest 1 % of the runs" needs neither a download of every record nor, on
  * several GPUs, a gather of them. An 8-bit radix select: each of eight passes leaves a small integer histogram, and
