@@ -18,7 +18,7 @@
 namespace ecdna {
 namespace accept_draws {
 
-constexpr uint32_t kMaxDraws = thin::kMaxDraw + 1u;  // 64: the draw index takes 6 bits
+constexpr uint32_t kMaxDraws = kThinDraws;  // 64: the draw index takes 6 bits
 
 // What is wrong with the block on a context of hist_bins bins and n_replicates replicates, as the message of
 // ECDNA_E_INVALID, which names the field; "" for a block the engine takes. keep_cells: the kept cells of the store the
@@ -64,18 +64,18 @@ inline std::string invalid(uint32_t hist_bins, uint32_t keep_cells, uint32_t sto
     return "";
 }
 
-// The call's tables, as AcceptDrawsArgs carries them. Keep store: one slice whose groups are the participating targets
-// grouped by m1, in order of first appearance, a group's targets ascending. Timepoint store: slice t has one group of
-// one target, t, and takes part when the mask names it. A target the mask leaves out is in no group: it is neither
-// drawn nor scored. max_mp: the largest number of positions a group picks, which sizes the table of the LDS plan.
-struct Plan {
-    uint32_t n_slices = 0, n_groups = 0, max_mp = 0;
+// The call's tables: the Grouping AcceptDrawsArgs carries (ssa_launch.h), which the plan is — its base, so the call
+// assigns it to the argument block — and the slices it is over. Keep store: one slice whose groups are the
+// participating targets grouped by m1, in order of first appearance, a group's targets ascending. Timepoint store:
+// slice t has one group of one target, t, and takes part when the mask names it. A target the mask leaves out is in no
+// group: it is neither drawn nor scored. max_mp: the largest number of positions a group picks, which sizes the table
+// of the LDS plan.
+struct Plan : Grouping {
+    uint32_t n_slices = 0, max_mp = 0;
     uint64_t slice_mask = 0;
-    uint32_t slice_group[kMaxCohortTargets + 1] = {};
-    uint32_t group_m[kMaxCohortTargets] = {};
-    uint32_t group_offset[kMaxCohortTargets + 1] = {};
-    uint32_t group_targets[kMaxCohortTargets] = {};
     thin::LdsPlan lds{};
+    Plan() : Grouping{} {}
+    const Grouping& grouping() const { return *this; }
 };
 inline Plan plan(uint32_t bins, uint32_t keep_cells, bool timepoints, uint32_t n_targets, const uint32_t* sample_cells,
                  uint64_t timepoint_mask) {

@@ -1320,33 +1320,55 @@ struct ThinSizes {
     const uint32_t* draws;         // [T][P] or nullptr
 };
 
-// The thinning pass over slice t of a store (ssa_thin.hip), on the pointers rescore_store made for the slice: the key
-// and the stream are the ones the slice's own samples were drawn under — the run's seed and field 0 for the end of the
-// run, seed_t and field 0 for phase t of a passage context, the run's seed and field (t + 1) << 16 for snapshot t.
+// The key and the stream field (thin::stream_tag) slice t of a store was drawn under, which its thinnings are drawn
+// under too: the run's seed and field 0 for the keep store (the end of the run), seed_t and field 0 for phase t of a
+// passage context, the run's seed and field t + 1 for snapshot t.
+struct SliceStream {
+    uint64_t seed;
+    uint32_t field;
+};
+SliceStream slice_stream(const ecdna_ssa_ctx* c, const KeptStore& s, uint32_t t) {
+    if (&s != &c->kept_tp) return {c->p.seed, 0u};
+    if (c->n_passages) return {passage_seed(c->p.seed, t), 0u};
+    return {c->p.seed, t + 1u};
+}
+
+// The thinning pass over slice t of a store (ssa_thin.hip), on the pointers rescore_store made for the slice.
 int launch_thin_pass(const ecdna_ssa_ctx* c, const KeptStore& s, uint64_t t, uint32_t P, const ThinSizes& sizes,
                      ecdna::ThinArgs a, hipStream_t st) {
     namespace th = ecdna::thin;
     const ecdna_ssa_params_t& p = c->p;
-    const bool timepoints = &s == &c->kept_tp;
-    const bool phases = timepoints && c->n_passages;
     const th::Groups g = th::group_by_size_and_draw(sizes.sample_cells + t * P,
                                                     sizes.draws ? sizes.draws + t * P : nullptr, P, s.m);
     const th::LdsPlan l = th::lds_plan(p.hist_bins, g.max_mp);
-    a.seed = phases ? passage_seed(p.seed, (uint32_t)t) : p.seed;
+    const SliceStream drawn = slice_stream(c, s, (uint32_t)t);
+    a.seed = drawn.seed;
     a.rid0 = p.first_replicate;
     a.rid_stride = rid_stride(p);
     a.n_groups = g.n_groups;
     a.table_slots = l.table_slots;
     a.scratch_words = l.scratch_words;
-    const uint32_t field = (timepoints && !phases) ? (uint32_t)t + 1u : 0u;
     for (uint32_t j = 0; j < g.n_groups; ++j) {
         a.group_m[j] = g.m[j];
-        a.group_tag[j] = th::stream_tag(field, g.d[j]);
+        a.group_tag[j] = th::stream_tag(drawn.field, g.d[j]);
     }
     std::copy_n(g.offset, ecdna::kMaxCohortTargets + 1u, a.group_offset);
     std::copy_n(g.targets, ecdna::kMaxCohortTargets, a.group_targets);
     a.reps_per_block = pass_reps_per_block(c, a.n, l.waves);
     TRY(ecdna::launch_thin(a, st));
+    return ECDNA_OK;
+}
+
+// The targets' CDFs and scalars (summarize_targets) into the host copies, and their two uploads enqueued on st. The
+// host copies must outlive the uploads: where they live is the caller's rule.
+int upload_targets(const uint64_t* target_hists, uint64_t targets, uint32_t bins, std::vector<double>* host_cdf,
+                   std::vector<double>* host_scalars, void* d_cdf, void* d_scalars, hipStream_t st) {
+    host_cdf->resize(targets * bins);
+    host_scalars->resize(targets * 3u);
+    summarize_targets(target_hists, targets, bins, host_cdf->data(), host_scalars->data());
+    TRY(hipMemcpyAsync(d_cdf, host_cdf->data(), host_cdf->size() * sizeof(double), hipMemcpyHostToDevice, st));
+    TRY(hipMemcpyAsync(d_scalars, host_scalars->data(), host_scalars->size() * sizeof(double), hipMemcpyHostToDevice,
+                       st));
     return ECDNA_OK;
 }
 
@@ -1368,31 +1390,11 @@ int rescore_store(ecdna_ssa_ctx* c, KeptStore* s, uint32_t P, const uint64_t* ta
     TRY(accept_reserve(&s->cdf, targets * bins * sizeof(double), "target CDFs", who));
     TRY(accept_reserve(&s->scalars, targets * 3u * sizeof(double), "target scalars", who));
     if (n) {
-        s->host_cdf.resize(targets * bins);
-        s->host_scalars.resize(targets * 3u);
-        summarize_targets(target_hists, targets, bins, s->host_cdf.data(), s->host_scalars.data());
-        TRY(hipMemcpyAsync(s->cdf.ptr, s->host_cdf.data(), s->host_cdf.size() * sizeof(double), hipMemcpyHostToDevice,
-                           st));
-        TRY(hipMemcpyAsync(s->scalars.ptr, s->host_scalars.data(), s->host_scalars.size() * sizeof(double),
-                           hipMemcpyHostToDevice, st));
+        TRY(upload_targets(target_hists, targets, bins, &s->host_cdf, &s->host_scalars, s->cdf.ptr, s->scalars.ptr, st));
         s->pending = true;
         s->stream = st;
-        for (uint64_t t = 0; t < s->T; ++t) {
-            if (sizes) {
-                ecdna::ThinArgs ta{};
-                ta.headers = s->d_headers + t * n;
-                ta.cells = s->d_cells + t * n * s->m;
-                ta.out = static_cast<ecdna_rep_stats_t*>(s->stats.ptr) + t * P * n;
-                ta.target_cdf = static_cast<const double*>(s->cdf.ptr) + t * P * bins;
-                ta.target_scalars = static_cast<const double*>(s->scalars.ptr) + t * P * 3u;
-                ta.n = (uint32_t)n;
-                ta.m = s->m;
-                ta.bins = bins;
-                ta.n_targets = P;
-                TRY(launch_thin_pass(c, *s, t, P, *sizes, ta, st));
-                continue;
-            }
-            ecdna::RescoreArgs a{};
+        // slice t's part of the store, the same for either pass (RescoreArgs' fields, which ThinArgs repeats)
+        auto slice = [&](auto a, uint64_t t) {
             a.headers = s->d_headers + t * n;
             a.cells = s->d_cells + t * n * s->m;
             a.out = static_cast<ecdna_rep_stats_t*>(s->stats.ptr) + t * P * n;
@@ -1402,6 +1404,14 @@ int rescore_store(ecdna_ssa_ctx* c, KeptStore* s, uint32_t P, const uint64_t* ta
             a.m = s->m;
             a.bins = bins;
             a.n_targets = P;
+            return a;
+        };
+        for (uint64_t t = 0; t < s->T; ++t) {
+            if (sizes) {
+                TRY(launch_thin_pass(c, *s, t, P, *sizes, slice(ecdna::ThinArgs{}, t), st));
+                continue;
+            }
+            ecdna::RescoreArgs a = slice(ecdna::RescoreArgs{}, t);
             a.reps_per_block = pass_reps_per_block(c, (uint32_t)n, ecdna::rescore_waves(bins, nullptr));
             TRY(ecdna::launch_rescore(a, st));
         }
@@ -1507,6 +1517,73 @@ int download_kept_store(ecdna_ssa_ctx* c, const KeptStore& s, uint64_t n_ids, co
 }
 
 const char* const kNeedsTimepoints = ": the kept timepoint samples need ecdna_ssa_ctx_create_keep_timepoints";
+
+// ---- ecdna_ssa_ctx_accept_draws and _pool_draws: what both do with the block they share ----
+
+// The store the block names, under the checks both calls make and in their order. name: "accept_draws" or "pool_draws",
+// the prefix of the messages; invalid(keep_cells): the call's own validation (accept_draws::invalid, pool_draws::invalid).
+template <class Invalid>
+int draws_store(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a, const std::string& name, Invalid invalid,
+                KeptStore** out) {
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    if (!a) return fail(ECDNA_E_INVALID, name + ": the block is NULL");
+    const bool timepoints = a->timepoints == 1u;
+    KeptStore* s = timepoints ? &c->kept_tp : &c->kept;
+    const std::string bad = invalid(s->m ? s->m : ecdna::kMaxSubsampleCells);
+    if (!bad.empty()) return fail(ECDNA_E_INVALID, bad);
+    if (!s->m)
+        return fail(ECDNA_E_STATE,
+                    timepoints ? name + kNeedsTimepoints : name + ": the kept samples need ecdna_ssa_ctx_create_keep");
+    TRY(ctx_launched(c, (name + " before launch").c_str()));
+    *out = s;
+    return ECDNA_OK;
+}
+
+// The part of the argument block both passes share, for the block's draws on store s: its slices and the mask are the
+// plan's (accept_draws::plan), the LDS plan the call's, the targets the call's own device copies.
+ecdna::DrawsArgs draws_args(const ecdna_ssa_ctx* c, const KeptStore& s, const ecdna_ssa_accept_draws_t& a,
+                            const ecdna::accept_draws::Plan& slices, const ecdna::thin::LdsPlan& lds,
+                            const void* d_cdf, const void* d_scalars) {
+    const ecdna_ssa_params_t& p = c->p;
+    const bool phases = &s == &c->kept_tp && c->n_passages;
+    ecdna::DrawsArgs k{};
+    k.headers = s.d_headers;
+    k.cells = s.d_cells;
+    // rule 1 as the sources 12 and 13 have it: the one summary, or on a passage context every participating phase's
+    k.summaries = phases ? c->d_pas_summ : c->d_summ;
+    k.err_stride = phases ? p.n_replicates : 0u;
+    k.target_cdf = static_cast<const double*>(d_cdf);
+    k.target_scalars = static_cast<const double*>(d_scalars);
+    k.slice_mask = slices.slice_mask;
+    k.rid0 = p.first_replicate;
+    k.rid_stride = rid_stride(p);
+    k.reps_per_set = p.reps_per_set;
+    k.n = (uint32_t)p.n_replicates;
+    k.m = s.m;
+    k.bins = p.hist_bins;
+    k.n_slices = slices.n_slices;
+    k.n_targets = a.n_targets;
+    k.n_sets = p.n_param_sets;
+    k.first_draw = a.first_draw;
+    k.n_draws = a.n_draws;
+    k.reps_per_block = pass_reps_per_block(c, k.n, lds.waves);
+    k.table_slots = lds.table_slots;
+    k.scratch_words = lds.scratch_words;
+    for (uint32_t t = 0; t < slices.n_slices; ++t) {
+        const SliceStream drawn = slice_stream(c, s, t);
+        k.slice_seed[t] = drawn.seed;
+        k.slice_tag[t] = ecdna::thin::stream_tag(drawn.field, 0u);
+    }
+    return k;
+}
+
+// A threshold row as the kernels' argument blocks carry it.
+void threshold_row(const ecdna_accept_threshold_t& t, double* row) {
+    row[0] = t.ks;
+    row[1] = t.mean_rel;
+    row[2] = t.entropy_rel;
+    row[3] = t.frequency_diff;
+}
 }  // namespace
 
 // library-internal entry points for ssa_comm.cpp (the RCCL reduction)
@@ -2093,86 +2170,40 @@ int ecdna_ssa_ctx_rescore_timepoints_sized(ecdna_ssa_ctx* c, const uint64_t* tar
 
 int ecdna_ssa_ctx_accept_draws(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a) {
     namespace ad = ecdna::accept_draws;
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!a) return fail(ECDNA_E_INVALID, "accept_draws: the block is NULL");
-    const ecdna_ssa_params_t& p = c->p;
-    const bool timepoints = a->timepoints == 1u;
-    KeptStore* s = timepoints ? &c->kept_tp : &c->kept;
-    const std::string bad = ad::invalid(p.hist_bins, s->m ? s->m : ecdna::kMaxSubsampleCells, c->kept_tp.T,
-                                        p.n_replicates, *a);
-    if (!bad.empty()) return fail(ECDNA_E_INVALID, bad);
-    if (!s->m)
-        return fail(ECDNA_E_STATE, timepoints ? std::string("accept_draws") + kNeedsTimepoints
-                                              : std::string("accept_draws: the kept samples need ecdna_ssa_ctx_create_keep"));
-    TRY(ctx_launched(c, "accept_draws before launch"));
+    const char* who = "ecdna_ssa_ctx_accept_draws";
+    KeptStore* s = nullptr;
+    TRY(draws_store(c, a, "accept_draws", [&](uint32_t keep_cells) {
+        return ad::invalid(c->p.hist_bins, keep_cells, c->kept_tp.T, c->p.n_replicates, *a);
+    }, &s));
 
+    const ecdna_ssa_params_t& p = c->p;
     const uint32_t bins = p.hist_bins, Q = a->n_thresholds, P = a->n_targets;
     const uint64_t n = p.n_replicates;
-    const bool phases = timepoints && c->n_passages;
     TRY(hipSetDevice(c->device));
     hipStream_t st = c->last_stream;
     // an earlier call may still read the targets this one replaces (and its upload their host copies)
     if (c->adr_pending) TRY(hipStreamSynchronize(c->adr_stream));
     c->adr_pending = false;
     c->adr_valid = false;
-    TRY(accept_reserve(&c->adr_cdf, ad::cdf_bytes(P, bins), "target CDFs", "ecdna_ssa_ctx_accept_draws"));
-    TRY(accept_reserve(&c->adr_scalars, ad::scalars_bytes(P), "target scalars", "ecdna_ssa_ctx_accept_draws"));
-    TRY(accept_reserve(&c->adr_sums, ad::sums_bytes(Q, p.n_param_sets), "sums", "ecdna_ssa_ctx_accept_draws"));
-    if (n) TRY(accept_reserve(&c->adr_passes, ad::passes_bytes(n, Q), "passes", "ecdna_ssa_ctx_accept_draws"));
+    TRY(accept_reserve(&c->adr_cdf, ad::cdf_bytes(P, bins), "target CDFs", who));
+    TRY(accept_reserve(&c->adr_scalars, ad::scalars_bytes(P), "target scalars", who));
+    TRY(accept_reserve(&c->adr_sums, ad::sums_bytes(Q, p.n_param_sets), "sums", who));
+    if (n) TRY(accept_reserve(&c->adr_passes, ad::passes_bytes(n, Q), "passes", who));
     TRY(hipMemsetAsync(c->adr_sums.ptr, 0, ad::sums_bytes(Q, p.n_param_sets), st));
     if (n) {
-        c->adr_host_cdf.resize((uint64_t)P * bins);
-        c->adr_host_scalars.resize((uint64_t)P * 3u);
-        summarize_targets(a->target_hists, P, bins, c->adr_host_cdf.data(), c->adr_host_scalars.data());
-        TRY(hipMemcpyAsync(c->adr_cdf.ptr, c->adr_host_cdf.data(), ad::cdf_bytes(P, bins), hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(c->adr_scalars.ptr, c->adr_host_scalars.data(), ad::scalars_bytes(P), hipMemcpyHostToDevice,
-                           st));
+        // (the call only enqueues: the uploads' host copies live in the context)
+        TRY(upload_targets(a->target_hists, P, bins, &c->adr_host_cdf, &c->adr_host_scalars, c->adr_cdf.ptr,
+                           c->adr_scalars.ptr, st));
         c->adr_pending = true;
         c->adr_stream = st;
-        const ad::Plan pl = ad::plan(bins, s->m, timepoints, P, a->sample_cells, a->timepoint_mask);
+        const ad::Plan pl = ad::plan(bins, s->m, a->timepoints == 1u, P, a->sample_cells, a->timepoint_mask);
         ecdna::AcceptDrawsArgs k{};
-        k.headers = s->d_headers;
-        k.cells = s->d_cells;
-        // rule 1 as the sources 12 and 13 have it: the one summary, or on a passage context every participating phase's
-        k.summaries = phases ? c->d_pas_summ : c->d_summ;
-        k.err_stride = phases ? n : 0u;
-        k.target_cdf = static_cast<const double*>(c->adr_cdf.ptr);
-        k.target_scalars = static_cast<const double*>(c->adr_scalars.ptr);
+        k.s = draws_args(c, *s, *a, pl, pl.lds, c->adr_cdf.ptr, c->adr_scalars.ptr);
+        k.g = pl.grouping();
         k.passes = static_cast<uint8_t*>(c->adr_passes.ptr);
         k.sums = static_cast<unsigned long long*>(c->adr_sums.ptr);
-        k.slice_mask = pl.slice_mask;
-        k.rid0 = p.first_replicate;
-        k.rid_stride = rid_stride(p);
-        k.reps_per_set = p.reps_per_set;
-        k.n = (uint32_t)n;
-        k.m = s->m;
-        k.bins = bins;
-        k.n_slices = pl.n_slices;
-        k.n_targets = P;
-        k.n_groups = pl.n_groups;
         k.Q = Q;
-        k.n_sets = p.n_param_sets;
-        k.first_draw = a->first_draw;
-        k.n_draws = a->n_draws;
-        k.reps_per_block = pass_reps_per_block(c, k.n, pl.lds.waves);
-        k.table_slots = pl.lds.table_slots;
-        k.scratch_words = pl.lds.scratch_words;
-        // the key and the stream each slice's own samples were drawn under (launch_thin_pass)
-        for (uint32_t t = 0; t < pl.n_slices; ++t) {
-            k.slice_seed[t] = phases ? passage_seed(p.seed, t) : p.seed;
-            k.slice_tag[t] = ecdna::thin::stream_tag((timepoints && !phases) ? t + 1u : 0u, 0u);
-        }
-        std::copy_n(pl.slice_group, ecdna::kMaxCohortTargets + 1u, k.slice_group);
-        std::copy_n(pl.group_m, ecdna::kMaxCohortTargets, k.group_m);
-        std::copy_n(pl.group_offset, ecdna::kMaxCohortTargets + 1u, k.group_offset);
-        std::copy_n(pl.group_targets, ecdna::kMaxCohortTargets, k.group_targets);
-        for (uint32_t q = 0; q < Q; ++q) {
-            const ecdna_accept_threshold_t& t = a->thresholds[q];
-            k.thr[q][0] = t.ks;
-            k.thr[q][1] = t.mean_rel;
-            k.thr[q][2] = t.entropy_rel;
-            k.thr[q][3] = t.frequency_diff;
-        }
+        for (uint32_t q = 0; q < Q; ++q) threshold_row(a->thresholds[q], k.thr[q]);
         TRY(ecdna::launch_accept_draws(k, st));
     }
     c->adr_rows = Q;
@@ -2200,28 +2231,21 @@ int ecdna_ssa_ctx_pool_draws(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a
                              uint64_t* out_thinned, uint64_t* out_kept) {
     namespace pd = ecdna::pool_draws;
     const char* who = "ecdna_ssa_ctx_pool_draws";
-    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
-    if (!a) return fail(ECDNA_E_INVALID, "pool_draws: the block is NULL");
-    const ecdna_ssa_params_t& p = c->p;
-    const bool timepoints = a->timepoints == 1u;
-    const KeptStore* s = timepoints ? &c->kept_tp : &c->kept;
-    const std::string bad = pd::invalid(p.hist_bins, s->m ? s->m : ecdna::kMaxSubsampleCells, c->kept_tp.T,
-                                        p.n_replicates, *a, threshold, out_thinned, out_kept);
-    if (!bad.empty()) return fail(ECDNA_E_INVALID, bad);
-    if (!s->m)
-        return fail(ECDNA_E_STATE, timepoints ? std::string("pool_draws") + kNeedsTimepoints
-                                              : std::string("pool_draws: the kept samples need ecdna_ssa_ctx_create_keep"));
-    TRY(ctx_launched(c, "pool_draws before launch"));
+    KeptStore* s = nullptr;
+    TRY(draws_store(c, a, "pool_draws", [&](uint32_t keep_cells) {
+        return pd::invalid(c->p.hist_bins, keep_cells, c->kept_tp.T, c->p.n_replicates, *a, threshold, out_thinned,
+                           out_kept);
+    }, &s));
 
+    const ecdna_ssa_params_t& p = c->p;
     const uint32_t bins = p.hist_bins, P = a->n_targets, sets = p.n_param_sets;
     const uint64_t n = p.n_replicates;
-    const pd::Plan pl = pd::plan(bins, s->m, timepoints, P, a->sample_cells, a->timepoint_mask);
+    const pd::Plan pl = pd::plan(bins, s->m, a->timepoints == 1u, P, a->sample_cells, a->timepoint_mask);
     const uint32_t S = pl.pool.n_slices;
     const uint64_t thinned_words = pd::thinned_words(P, sets, bins), kept_words = pd::kept_words(S, sets, bins);
     if (out_thinned) std::fill(out_thinned, out_thinned + thinned_words, 0ull);
     if (out_kept) std::fill(out_kept, out_kept + kept_words, 0ull);
     if (!n) return ECDNA_OK;
-    const bool phases = timepoints && c->n_passages;
     TRY(hipSetDevice(c->device));
     hipStream_t st = c->last_stream;
     TRY(accept_reserve(&c->pdr_cdf, pd::cdf_bytes(P, bins), "target CDFs", who));
@@ -2231,62 +2255,22 @@ int ecdna_ssa_ctx_pool_draws(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a
     unsigned long long* d_kept = d_thinned + thinned_words;
     TRY(hipMemsetAsync(c->pdr_pool.ptr, 0, pd::pooled_bytes(P, S, sets, bins), st));
     // (the call synchronises below, so the uploads' host copies live on its stack)
-    std::vector<double> host_cdf((uint64_t)P * bins), host_scalars((uint64_t)P * 3u);
-    summarize_targets(a->target_hists, P, bins, host_cdf.data(), host_scalars.data());
-    TRY(hipMemcpyAsync(c->pdr_cdf.ptr, host_cdf.data(), pd::cdf_bytes(P, bins), hipMemcpyHostToDevice, st));
-    const hipError_t up =
-        hipMemcpyAsync(c->pdr_scalars.ptr, host_scalars.data(), pd::scalars_bytes(P), hipMemcpyHostToDevice, st);
-    if (up != hipSuccess) {
-        (void)hipStreamSynchronize(st);  // (the first upload may still read host_cdf)
-        TRY(up);
+    std::vector<double> host_cdf, host_scalars;
+    if (const int rc = upload_targets(a->target_hists, P, bins, &host_cdf, &host_scalars, c->pdr_cdf.ptr,
+                                      c->pdr_scalars.ptr, st)) {
+        (void)hipStreamSynchronize(st);  // (an upload already enqueued may still read its host copy)
+        return rc;
     }
 
     ecdna::PoolDrawsArgs k{};
-    k.headers = s->d_headers;
-    k.cells = s->d_cells;
-    // rule 1 as ecdna_ssa_ctx_accept_draws has it: the one summary, or on a passage context every participating phase's
-    k.summaries = phases ? c->d_pas_summ : c->d_summ;
-    k.err_stride = phases ? n : 0u;
-    k.target_cdf = static_cast<const double*>(c->pdr_cdf.ptr);
-    k.target_scalars = static_cast<const double*>(c->pdr_scalars.ptr);
+    // (the slices and the mask are the verdict's: the pooling grouping walks every slice whatever the mask)
+    k.s = draws_args(c, *s, *a, pl.verdict, pl.lds, c->pdr_cdf.ptr, c->pdr_scalars.ptr);
+    k.verdict = pl.verdict.grouping();
+    k.pool = pl.pool.grouping();
     k.thinned = out_thinned ? d_thinned : nullptr;
     k.kept = out_kept ? d_kept : nullptr;
-    k.slice_mask = pl.verdict.slice_mask;
-    k.rid0 = p.first_replicate;
-    k.rid_stride = rid_stride(p);
-    k.reps_per_set = p.reps_per_set;
-    k.n = (uint32_t)n;
-    k.m = s->m;
-    k.bins = bins;
-    k.n_slices = S;
-    k.n_targets = P;
-    k.v_groups = pl.verdict.n_groups;
-    k.p_groups = pl.pool.n_groups;
-    k.n_sets = sets;
-    k.first_draw = a->first_draw;
-    k.n_draws = a->n_draws;
-    k.reps_per_block = pass_reps_per_block(c, k.n, pl.lds.waves);
-    k.table_slots = pl.lds.table_slots;
-    k.scratch_words = pl.lds.scratch_words;
     k.wave_words = ecdna::pool_draws_wave_words(bins, pl.lds.table_slots);
-    const ecdna_accept_threshold_t& t = a->thresholds[threshold];
-    k.thr[0] = t.ks;
-    k.thr[1] = t.mean_rel;
-    k.thr[2] = t.entropy_rel;
-    k.thr[3] = t.frequency_diff;
-    // the key and the stream each slice's own samples were drawn under (launch_thin_pass)
-    for (uint32_t i = 0; i < S; ++i) {
-        k.slice_seed[i] = phases ? passage_seed(p.seed, i) : p.seed;
-        k.slice_tag[i] = ecdna::thin::stream_tag((timepoints && !phases) ? i + 1u : 0u, 0u);
-    }
-    std::copy_n(pl.verdict.slice_group, ecdna::kMaxCohortTargets + 1u, k.v_slice_group);
-    std::copy_n(pl.verdict.group_m, ecdna::kMaxCohortTargets, k.v_group_m);
-    std::copy_n(pl.verdict.group_offset, ecdna::kMaxCohortTargets + 1u, k.v_group_offset);
-    std::copy_n(pl.verdict.group_targets, ecdna::kMaxCohortTargets, k.v_group_targets);
-    std::copy_n(pl.pool.slice_group, ecdna::kMaxCohortTargets + 1u, k.p_slice_group);
-    std::copy_n(pl.pool.group_m, ecdna::kMaxCohortTargets, k.p_group_m);
-    std::copy_n(pl.pool.group_offset, ecdna::kMaxCohortTargets + 1u, k.p_group_offset);
-    std::copy_n(pl.pool.group_targets, ecdna::kMaxCohortTargets, k.p_group_targets);
+    threshold_row(a->thresholds[threshold], k.thr);
     const hipError_t le = ecdna::launch_pool_draws(k, st);
     const hipError_t se = hipStreamSynchronize(st);  // (also when the launch was refused: the uploads read the stack)
     TRY(le);

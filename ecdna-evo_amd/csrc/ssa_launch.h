@@ -327,24 +327,47 @@ struct AcceptArgs {
     double thr[kMaxAcceptRows][4];        // per row: ks, mean_rel, entropy_rel, frequency_diff (+inf: off)
 };
 
-// The thinned acceptance pass over the whole run (ssa_accept_draws.hip; ecdna_ssa_ctx_accept_draws, thinned acceptance
-// mapping v1): per replicate and threshold row, the number of thinning draws first_draw .. first_draw + n_draws - 1 on
-// which acceptance mapping v1 accepts the records ssa_thin would write for that draw — the records stay in registers.
-// The store's slices 0 .. n_slices - 1 (headers [n_slices][n], cells [n_slices][n][m]) are walked per replicate; slice
-// s takes part when bit s of slice_mask is set, draws under slice_seed[s] on stream slice_tag[s] | (d << 10), and owns
-// the groups slice_group[s] .. slice_group[s + 1) of the flat group tables, which are ThinArgs' (group_targets index
-// target_cdf / target_scalars). The keep store is one slice with the participating targets' groups; the timepoint store
-// a slice per timepoint with one group of one target. The error words lie as AcceptArgs' (err_stride 0: one summary per
-// replicate; else slice s's is summaries[i + s * err_stride], over the slices of slice_mask). Tables and thresholds
-// travel in the argument block: wave-uniform, read with scalar loads (below the 4 KiB a launch takes).
-struct AcceptDrawsArgs {
+// The flat group tables of the passes over thinning draws: slice s of a store owns the groups slice_group[s] ..
+// slice_group[s + 1), and group g draws one sample of group_m[g] cells per draw and scores or pools it for the targets
+// group_targets[group_offset[g] .. group_offset[g + 1]) (indices into target_cdf / target_scalars), as ThinArgs' groups.
+// accept_draws::plan (ssa_accept_draws.hpp) makes them; they travel in the argument block: wave-uniform, read with
+// scalar loads.
+struct Grouping {
+    uint32_t n_groups;                    // over all slices, 1 .. n_targets
+    uint32_t slice_group[kMaxCohortTargets + 1];
+    uint32_t group_m[kMaxCohortTargets];  // 1 .. m each
+    uint32_t group_offset[kMaxCohortTargets + 1];
+    uint32_t group_targets[kMaxCohortTargets];
+};
+// Whether a kernel may index by g's tables on a store of n_slices slices of m kept cells and n_targets targets: every
+// index it forms from them stays inside them, target_cdf and a kept row.
+inline bool grouping_ok(const Grouping& g, uint32_t n_slices, uint32_t n_targets, uint32_t m) {
+    if (n_slices < 1u || n_slices > kMaxCohortTargets || n_targets < 1u || n_targets > kMaxCohortTargets ||
+        g.n_groups < 1u || g.n_groups > n_targets || g.slice_group[0] != 0u || g.slice_group[n_slices] != g.n_groups ||
+        g.group_offset[0] != 0u || g.group_offset[g.n_groups] > n_targets)
+        return false;
+    for (uint32_t s = 0; s < n_slices; ++s)
+        if (g.slice_group[s] > g.slice_group[s + 1u]) return false;
+    for (uint32_t j = 0; j < g.n_groups; ++j)
+        if (g.group_offset[j] > g.group_offset[j + 1u] || g.group_m[j] < 1u || g.group_m[j] > m) return false;
+    for (uint32_t j = 0; j < g.group_offset[g.n_groups]; ++j)
+        if (g.group_targets[j] >= n_targets) return false;
+    return true;
+}
+
+// What the two passes over thinning draws share (ssa_accept_draws.hip, ssa_pool_draws.hip): the store, the targets and
+// the range of draws. The store's slices 0 .. n_slices - 1 (headers [n_slices][n], cells [n_slices][n][m]) are walked
+// per replicate; slice s takes part in the verdict when bit s of slice_mask is set and draws under slice_seed[s] on
+// stream slice_tag[s] with the draw index set (thin::draw_tag). The keep store is one slice; the timepoint store a slice
+// per timepoint. The error words lie as AcceptArgs' (err_stride 0: one summary per replicate; else slice s's is
+// summaries[i + s * err_stride], over the slices of slice_mask).
+constexpr uint32_t kThinDraws = 64;      // thinning draws of one kept sample: the draw index takes 6 bits
+struct DrawsArgs {
     const uint2* headers;                 // [n_slices][n]
     const uint16_t* cells;                // [n_slices][n][m]
     const ecdna_rep_summary_t* summaries;
     const double* target_cdf;             // [targets][bins]
     const double* target_scalars;         // [targets][3]
-    uint8_t* passes;                      // [n][Q]
-    unsigned long long* sums;             // [Q][n_sets], zeroed before the launch
     uint64_t err_stride;
     uint64_t slice_mask;                  // participating slices (bits below n_slices, never 0)
     uint64_t rid0, rid_stride, reps_per_set;
@@ -353,64 +376,44 @@ struct AcceptDrawsArgs {
     uint32_t bins;
     uint32_t n_slices;                    // 1 .. 64
     uint32_t n_targets;                   // rows of target_cdf, 1 .. kMaxCohortTargets
-    uint32_t n_groups;                    // over all slices, 1 .. n_targets
-    uint32_t Q;                           // threshold rows, 1 .. kMaxAcceptRows
     uint32_t n_sets;
-    uint32_t first_draw, n_draws;         // first_draw + n_draws <= 64, n_draws >= 1
+    uint32_t first_draw, n_draws;         // first_draw + n_draws <= kThinDraws, n_draws >= 1
     uint32_t reps_per_block;
-    uint32_t table_slots;                 // as ThinArgs'
+    uint32_t table_slots;                 // as ThinArgs', for the largest m' of any group
     uint32_t scratch_words;
     uint64_t slice_seed[kMaxCohortTargets];
-    uint32_t slice_tag[kMaxCohortTargets];        // thin::stream_tag(field, 0)
-    uint32_t slice_group[kMaxCohortTargets + 1];
-    uint32_t group_m[kMaxCohortTargets];
-    uint32_t group_offset[kMaxCohortTargets + 1];
-    uint32_t group_targets[kMaxCohortTargets];
+    uint32_t slice_tag[kMaxCohortTargets];  // thin::stream_tag(field, 0)
+};
+
+// The thinned acceptance pass over the whole run (ssa_accept_draws.hip; ecdna_ssa_ctx_accept_draws, thinned acceptance
+// mapping v1): per replicate and threshold row, the number of thinning draws first_draw .. first_draw + n_draws - 1 on
+// which acceptance mapping v1 accepts the records ssa_thin would write for that draw — the records stay in registers.
+// The keep store's one slice has the participating targets' groups; a slice of the timepoint store one group of one
+// target. Tables and thresholds travel in the argument block: wave-uniform, read with scalar loads (below the 4 KiB a
+// launch takes).
+struct AcceptDrawsArgs {
+    DrawsArgs s;
+    Grouping g;
+    uint8_t* passes;                      // [n][Q]
+    unsigned long long* sums;             // [Q][n_sets], zeroed before the launch
+    uint32_t Q;                           // threshold rows, 1 .. kMaxAcceptRows
     double thr[kMaxAcceptRows][4];        // per row: ks, mean_rel, entropy_rel, frequency_diff (+inf: off)
 };
 static_assert(sizeof(AcceptDrawsArgs) <= 4096, "the argument block of a launch");
 
 // The pooling pass over thinning draws (ssa_pool_draws.hip; ecdna_ssa_ctx_pool_draws, thinned pooling mapping v1): per
 // replicate the 64-bit set of the draws it passes under the one threshold row thr — AcceptDrawsArgs' verdict for that
-// row, over the groups v_* of the participating slices — and then, for a replicate that passes any, the pools over
-// every slice of the store: kept[s] takes popcount(set) times the slice's full histogram, thinned[target] the thinned
-// histograms of the passing draws of the target's group among p_* (the pooling grouping: every slot, whatever the
-// mask). Store, error words, seeds, tags and tables lie as AcceptDrawsArgs'. Either output may be null: it is then
-// neither computed nor written.
+// row, over the groups of `verdict` on the participating slices — and then, for a replicate that passes any, the pools
+// over every slice of the store: kept[s] takes popcount(set) times the slice's full histogram, thinned[target] the
+// thinned histograms of the passing draws of the target's group in `pool` (the pooling grouping: every slot, whatever
+// the mask). Either output may be null: it is then neither computed nor written.
 struct PoolDrawsArgs {
-    const uint2* headers;                 // [n_slices][n]
-    const uint16_t* cells;                // [n_slices][n][m]
-    const ecdna_rep_summary_t* summaries;
-    const double* target_cdf;             // [targets][bins]
-    const double* target_scalars;         // [targets][3]
+    DrawsArgs s;                          // table_slots: for the largest m' of either grouping
+    Grouping verdict, pool;
     unsigned long long* thinned;          // [n_targets][n_sets][bins] or null, zeroed before the launch
     unsigned long long* kept;             // [n_slices][n_sets][bins] or null, zeroed before the launch
-    uint64_t err_stride;
-    uint64_t slice_mask;                  // the verdict's participating slices (bits below n_slices, never 0)
-    uint64_t rid0, rid_stride, reps_per_set;
-    uint32_t n;                           // replicates of the run
-    uint32_t m;                           // the store's kept cells per sample
-    uint32_t bins;
-    uint32_t n_slices;                    // 1 .. 64
-    uint32_t n_targets;                   // rows of target_cdf, 1 .. kMaxCohortTargets
-    uint32_t v_groups, p_groups;          // over all slices, 1 .. n_targets each
-    uint32_t n_sets;
-    uint32_t first_draw, n_draws;         // first_draw + n_draws <= 64, n_draws >= 1
-    uint32_t reps_per_block;
-    uint32_t table_slots;                 // as ThinArgs', for the largest m' of either grouping
-    uint32_t scratch_words;
     uint32_t wave_words;                  // per-wave u32 words of LDS: pool_draws_wave_words(bins, table_slots)
     double thr[4];                        // the row: ks, mean_rel, entropy_rel, frequency_diff (+inf: off)
-    uint64_t slice_seed[kMaxCohortTargets];
-    uint32_t slice_tag[kMaxCohortTargets];        // thin::stream_tag(field, 0)
-    uint32_t v_slice_group[kMaxCohortTargets + 1];
-    uint32_t v_group_m[kMaxCohortTargets];
-    uint32_t v_group_offset[kMaxCohortTargets + 1];
-    uint32_t v_group_targets[kMaxCohortTargets];
-    uint32_t p_slice_group[kMaxCohortTargets + 1];
-    uint32_t p_group_m[kMaxCohortTargets];
-    uint32_t p_group_offset[kMaxCohortTargets + 1];
-    uint32_t p_group_targets[kMaxCohortTargets];
 };
 static_assert(sizeof(PoolDrawsArgs) <= 4096, "the argument block of a launch");
 
@@ -560,6 +563,16 @@ inline uint32_t pool_draws_wave_words(uint32_t bins, uint32_t table_slots) {
 inline uint32_t pool_draws_waves(uint32_t bins, uint32_t table_slots, size_t* lds_bytes) {
     return pass_waves(0, (size_t)pool_draws_wave_words(bins, table_slots) * 4u, lds_bytes);
 }
+// Whether a kernel may index its LDS, the store, the targets and its outputs by s (the group tables: grouping_ok): what
+// launch_accept_draws and launch_pool_draws refuse of the part they share.
+inline bool draws_ok(const DrawsArgs& s) {
+    return s.scratch_words == cohort_scratch_words(s.bins, s.table_slots) && s.n_slices >= 1u &&
+           s.n_slices <= kMaxCohortTargets && s.n_targets >= 1u && s.n_targets <= kMaxCohortTargets && s.n_draws >= 1u &&
+           s.first_draw < kThinDraws && s.n_draws <= kThinDraws - s.first_draw && s.n && s.reps_per_block &&
+           s.bins >= 2u && s.rid_stride && s.reps_per_set && s.n_sets && s.m && s.slice_mask &&
+           !(s.n_slices < 64u && (s.slice_mask >> s.n_slices)) && s.headers && s.cells && s.summaries && s.target_cdf &&
+           s.target_scalars;
+}
 // ssa_pool_accepted: the workgroup's u64 sum of the accepted samples' histograms (one parameter set at a time), 16 KiB
 // at 2,048 bins; its waves keep nothing of their own
 inline uint32_t pool_accepted_waves(uint32_t bins, size_t* lds_bytes) {
@@ -588,10 +601,10 @@ hipError_t launch_passage(const PassageArgs& a, uint32_t blocks, hipStream_t str
 // ever waits for another. a.n > 0.
 hipError_t launch_accept_mask(const AcceptArgs& a, hipStream_t stream);
 hipError_t launch_accept_list(const AcceptArgs& a, hipStream_t stream);
-// The thinned acceptance pass (ssa_accept_draws.hip): ssa_thin's LDS plan (thin_waves) for a.table_slots; a.sums zeroed
+// The thinned acceptance pass (ssa_accept_draws.hip): ssa_thin's LDS plan (thin_waves) for a.s.table_slots; a.sums zeroed
 // on the stream before it. A block that disagrees with the plan is refused: hipErrorInvalidValue.
 hipError_t launch_accept_draws(const AcceptDrawsArgs& a, hipStream_t stream);
-// The pooling pass over thinning draws (ssa_pool_draws.hip): pool_draws_waves' LDS plan for a.table_slots; a.thinned
+// The pooling pass over thinning draws (ssa_pool_draws.hip): pool_draws_waves' LDS plan for a.s.table_slots; a.thinned
 // and a.kept zeroed on the stream before it. A block that disagrees with the plan is refused: hipErrorInvalidValue.
 hipError_t launch_pool_draws(const PoolDrawsArgs& a, hipStream_t stream);
 // The select passes (ssa_select.hip): the keys of every replicate (a.n > 0), and one digit pass over them (a.hist zeroed

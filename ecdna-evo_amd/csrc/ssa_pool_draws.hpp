@@ -33,22 +33,14 @@ inline std::string invalid(uint32_t hist_bins, uint32_t keep_cells, uint32_t sto
     return "";
 }
 
-// The pass's LDS plan: ssa_thin's per-wave layout — the full histogram, a thinned sample's, the scratch the table and
-// the CDF share — and the wave's accumulator, [bins] u32 rounded up to an even number of words, behind the table: inside
-// the scratch where it has room, past it where not (ssa_launch.h pool_draws_wave_words). lds_bytes / waves is the
-// per-wave size.
-inline thin::LdsPlan lds_plan(uint32_t bins, uint32_t max_mp) {
-    thin::LdsPlan l{};
-    l.table_slots = max_mp ? subsample_table_slots(max_mp) : 0u;
-    l.scratch_words = cohort_scratch_words(bins, l.table_slots);
-    l.waves = pool_draws_waves(bins, l.table_slots, &l.lds_bytes);
-    return l;
-}
+// The pass's LDS plan: thin::lds_plan under this pass's waves rule (the wave's accumulator behind the table).
+inline thin::LdsPlan lds_plan(uint32_t bins, uint32_t max_mp) { return thin::lds_plan(bins, max_mp, pool_draws_waves); }
 
 // The call's tables, as PoolDrawsArgs carries them. verdict: the grouping ecdna_ssa_ctx_accept_draws makes of the same
 // block, so the verdict is that call's. pool: the same grouping with mask 0 — every slot takes part: on the keep store
 // the targets grouped by m1 whatever the mask, on the timepoint store one group of one target per slice. lds: for the
-// largest number of positions any group of either picks (the pooling's, which holds every group of the verdict's).
+// largest number of positions any group of either picks (the pooling's, which holds every group of the verdict's):
+// ssa_thin's per-wave layout and the wave's accumulator behind the table (ssa_launch.h pool_draws_wave_words).
 struct Plan {
     accept_draws::Plan verdict, pool;
     thin::LdsPlan lds{};

@@ -10,8 +10,9 @@
 // whole kept sample, and its record is ssa_rescore's byte for byte: the histogram and the sums are integers, and the
 // f64 operations on them are wave_cohort_stats' (ssa_wave.hpp) in its lane and scan order (fp contract off).
 //
-// One wave per replicate, as ssa_rescore. The row is read once, with u16 loads (a row of m cells is not 16-byte aligned
-// when m is odd), into the full histogram fh, which stays in LDS. The targets are grouped by (m1, draw index)
+// One wave per replicate, as ssa_rescore. The scan, the thinned draw and the record of a group are ssa_thinwave.hpp's,
+// shared with ssa_accept_draws and ssa_pool_draws; this kernel stores the records. The row is read once
+// into the full histogram fh, which stays in LDS. The targets are grouped by (m1, draw index)
 // (ssa_thin.hpp): a group's sample is drawn once — into wh, which starts from zero or, for a complement, from a copy of
 // fh — and scored against every target of the group. Whether a group takes the whole kept sample depends on the
 // replicate's a + b: the branch is wave-uniform. The CDF shares its LDS with the table of drawn positions, as in
@@ -24,6 +25,7 @@
 #include "ssa_launch.h"
 #include "ssa_sampledraw.hpp"
 #include "ssa_thin.hpp"
+#include "ssa_thinwave.hpp"
 #include "ssa_wave.hpp"
 
 #pragma clang fp contract(off)
@@ -41,70 +43,39 @@ __global__ void __launch_bounds__(256) ssa_thin(const ThinArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long lds[];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t nw = blockDim.x >> 6;
-    const uint32_t bins = a.bins, last = bins - 1u;
-    // (every term is even, so each wave's scratch is 8-byte aligned for the CDF)
-    const uint32_t wave_words = 2u * bins + a.scratch_words;
-    uint32_t* fh = reinterpret_cast<uint32_t*>(lds) + (size_t)wave * wave_words;  // [bins] the kept sample's histogram
-    uint32_t* wh = fh + bins;                                                     // [bins] a thinned sample's
-    uint32_t* tab = wh + bins;                                                    // [scratch_words]: the table, or
-    double* F = reinterpret_cast<double*>(tab);                                   // [bins] the scored sample's CDF
+    const uint32_t bins = a.bins;
+    const ThinLds L = thin_lds(lds, wave, 2u * bins + a.scratch_words, bins);
     const uint32_t r_begin = blockIdx.x * a.reps_per_block;
     if (r_begin >= a.n) return;
     const uint32_t r_end = min(a.n, r_begin + a.reps_per_block);
-    const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
 
     for (uint32_t q = r_begin + wave; q < r_end; q += nw) {
-        const uint2 h = a.headers[q];
-        if (h.x == kKeptGuard && h.y == kKeptGuard) {  // the guard: all-zero statistics, as ssa_rescore
+        const KeptSample k = kept_sample(a.headers, a.cells, q, a.m);
+        if (k.guard) {  // the guard: all-zero statistics, as ssa_rescore
             if (lane < a.n_targets) a.out[q + (uint64_t)lane * a.n] = ecdna_rep_stats_t{};
             continue;
         }
-        const uint32_t np = min(h.y, a.m);  // (a row holds m cells)
-        const uint64_t cells_all = (uint64_t)h.x + np;
         const uint64_t rid = a.rid0 + (uint64_t)q * a.rid_stride;
-        const uint16_t* row = a.cells + (uint64_t)q * a.m;
 
         // 1. the one scan: the kept sample's full histogram and its sum of k, as ssa_rescore makes them
-        for (uint32_t b = lane; b < bins; b += 64u) fh[b] = 0u;
-        wave_sync_lds();
-        uint64_t ksum = 0;
-        for (uint32_t j = lane; j < np; j += 64u) {
-            const uint32_t kk = row[j];
-            atomicAdd(&fh[kk < last ? kk : last], 1u);
-            ksum += kk;
-        }
-        if (lane == 0) atomicAdd(&fh[0], h.x);
-        wave_sync_lds();
-        ksum = wave_sum(ksum);
-        // the kept sample as a population: h.x N- cells, then the row (no bin counters)
-        const SamplePop pop{(uint64_t)h.x, nullptr, 0u, 0u, row, np};
+        const uint64_t ksum = wave_kept_hist(L.fh, bins, k, lane);
 
         // 2. each (m1, draw index): the whole kept sample, or one thinned sample, scored against the group's targets
         for (uint32_t g = 0; g < a.n_groups; ++g) {
             const uint32_t m1 = a.group_m[g];
             const uint32_t* list = a.group_targets + a.group_offset[g];
             const uint32_t count = a.group_offset[g + 1u] - a.group_offset[g];
-            const SamplePlan plan = sample_plan(m1, cells_all);
+            const SamplePlan plan = sample_plan(m1, k.cells_all);
             bool bad = plan.bad;
             uint64_t psum = 0;  // sum of k over the picked positions
-            if (!plan.whole && !bad) {
-                // the picks are counted into zeros, or taken out of a copy of the full histogram (complement)
-                for (uint32_t b = lane; b < bins; b += 64u) wh[b] = plan.comp ? fh[b] : 0u;
-                wave_sync_lds();
-                bad = wave_sample_picks<0>(wh, tab, a.table_slots, pop, plan.N, plan.mp, plan.comp, last,
-                                           a.group_tag[g], rid, k0, k1, lane, psum);
-                wave_sync_lds();
-            }
-            psum = wave_sum(psum);
+            if (!plan.whole && !bad)
+                bad = wave_thin_draw(L, a.table_slots, bins, k, plan, a.group_tag[g], a.seed, rid, lane, psum);
             if (bad) {  // the guard: all-zero statistics, as wave_sample_stats
                 if (lane < count) a.out[q + (uint64_t)list[lane] * a.n] = ecdna_rep_stats_t{};
             } else {
-                const uint32_t* hh = plan.whole ? fh : wh;
-                const uint64_t cells = plan.whole ? cells_all : (uint64_t)m1;
-                const uint64_t ks_sum = plan.whole ? ksum : (plan.comp ? ksum - psum : psum);
-                const uint64_t nplus_s = plan.whole ? (uint64_t)np : cells - (uint64_t)wh[0];
-                wave_cohort_stats(hh, F, bins, cells, ks_sum, nplus_s, a.target_cdf, a.target_scalars, list, count, lane,
-                                  a.out + q, a.n);
+                const ecdna_rep_stats_t rec = wave_thin_record(L, bins, k, plan.whole, plan.comp, m1, ksum, psum,
+                                                               a.target_cdf, a.target_scalars, list, count, lane);
+                if (lane < count) a.out[q + (uint64_t)list[lane] * a.n] = rec;
             }
             wave_sync_lds();  // wh and the scratch are written again for the next group or replicate
         }

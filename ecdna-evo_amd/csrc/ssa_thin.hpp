@@ -16,7 +16,7 @@
 namespace ecdna {
 namespace thin {
 
-constexpr uint32_t kMaxDraw = 63;            // the draw index d takes 6 bits
+constexpr uint32_t kMaxDraw = kThinDraws - 1u;  // 63: the draw index d takes 6 bits
 constexpr uint32_t kSampleTag = 0xC0000000u; // the sampling passes' tag (ssa_sampledraw.hpp kSubTag)
 constexpr uint32_t kThinFlag = 0x20000000u;  // bit 29: the sampling passes keep it clear
 
@@ -24,8 +24,10 @@ constexpr uint32_t kThinFlag = 0x20000000u;  // bit 29: the sampling passes keep
 // was drawn on (snapshot_plus_one = 0 for the end of the run and for a passage phase, s + 1 for snapshot s < 64), the
 // thinning flag, and the draw index d <= kMaxDraw in bits 10-15. t takes bits 0-9, d bits 10-15, the snapshot field bits
 // 16-22, the flag bit 29, the tag bits 30-31: the fields never meet.
+// draw_tag: a slice's tag stream_tag(field, 0) with the draw index set, as the passes over a range of draws form it.
+constexpr uint32_t draw_tag(uint32_t slice_tag, uint32_t d) { return slice_tag | (d << 10); }
 constexpr uint32_t stream_tag(uint32_t snapshot_plus_one, uint32_t d) {
-    return kSampleTag | (snapshot_plus_one << 16) | kThinFlag | (d << 10);
+    return draw_tag(kSampleTag | (snapshot_plus_one << 16) | kThinFlag, d);
 }
 
 inline bool empty_row(const uint64_t* h, uint32_t bins) {
@@ -110,16 +112,19 @@ inline Groups group_by_size_and_draw(const uint32_t* sample_cells, const uint32_
 }
 
 // The thinning pass's LDS plan for `bins` histogram bins when a group picks at most max_mp positions (0: every target
-// takes the whole kept sample): waves per workgroup, the table's slots and the dynamic LDS (ssa_launch.h).
+// takes the whole kept sample): waves per workgroup, the table's slots and the dynamic LDS (ssa_launch.h). waves: the
+// pass's rule for its waves and bytes — thin_waves, or pool_draws_waves for the pass that keeps an accumulator behind
+// the table; lds_bytes / waves is the per-wave size.
 struct LdsPlan {
     uint32_t waves, table_slots, scratch_words;
     size_t lds_bytes;
 };
-inline LdsPlan lds_plan(uint32_t bins, uint32_t max_mp) {
+inline LdsPlan lds_plan(uint32_t bins, uint32_t max_mp,
+                        uint32_t (*waves)(uint32_t, uint32_t, size_t*) = thin_waves) {
     LdsPlan l{};
     l.table_slots = max_mp ? subsample_table_slots(max_mp) : 0u;
     l.scratch_words = cohort_scratch_words(bins, l.table_slots);
-    l.waves = thin_waves(bins, l.table_slots, &l.lds_bytes);
+    l.waves = waves(bins, l.table_slots, &l.lds_bytes);
     return l;
 }
 

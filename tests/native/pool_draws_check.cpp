@@ -1,7 +1,7 @@
 // pool_draws_check.cpp — the host side of the pooling over thinning draws (ecdna-evo_amd/csrc/ssa_pool_draws.hpp) on
 // the CPU, for tests/test_pool_draws_native.py: every branch of the call's validation, the verdict's and the pooling's
-// grouping of the targets, the LDS plan at the limits and the byte counts. Built for the host alone, with the address
-// and undefined-behaviour sanitizers.
+// grouping of the targets, the LDS plan at the limits, the byte counts and the launch-time check of the group tables the
+// kernels index by. Built for the host alone, with the address and undefined-behaviour sanitizers.
 //
 //   pool_draws_check plan K S MASK m0 m1 ...  prints both groupings at keep_cells = K for store S (0 keep, 1 timepoints)
 //                                             and timepoint mask MASK (hex): per grouping "verdict|pool slices N mask M
@@ -11,6 +11,9 @@
 //                                             at bins 2 and 2048 with keep_cells 1 and 4096
 //   pool_draws_check bytes                    prints the byte counts of two shapes
 //   pool_draws_check validate                 checks every validation branch; prints "validate ok"
+//   pool_draws_check grouping                 grouping_ok (ssa_launch.h), the launches' check of the group tables: prints
+//                                             "accepted N" for the N groupings the two plans make over the sweep of
+//                                             `lds` and three masks, then "refused <what>" per hand-broken table
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -27,7 +30,8 @@ namespace pd = ecdna::pool_draws;
 static void print_grouping(const char* name, const ad::Plan& p) {
     std::printf("%s slices %u mask %llx groups %u max_mp %u\n", name, p.n_slices, (unsigned long long)p.slice_mask,
                 p.n_groups, p.max_mp);
-    for (uint32_t s = 0; s < p.n_slices; ++s) std::printf("slice %u groups %u %u\n", s, p.slice_group[s], p.slice_group[s + 1]);
+    for (uint32_t s = 0; s < p.n_slices; ++s)
+        std::printf("slice %u groups %u %u\n", s, p.slice_group[s], p.slice_group[s + 1]);
     for (uint32_t g = 0; g < p.n_groups; ++g) {
         std::printf("m %u targets", p.group_m[g]);
         for (uint32_t i = p.group_offset[g]; i < p.group_offset[g + 1]; ++i) std::printf(" %u", p.group_targets[i]);
@@ -245,11 +249,96 @@ static int check_validate() {
     return 0;
 }
 
+// grouping_ok takes what accept_draws::plan and pool_draws::plan make and refuses a table broken in any one way: one
+// refusal per clause of the check, each on a grouping that is in order otherwise.
+static int check_grouping() {
+    const uint32_t bins_list[] = {2, 9, 64, 65, 130, 1024, 2047, 2048};
+    const uint32_t keep_list[] = {1, 2, 64, 199, 200, 2048, 4095, 4096};
+    unsigned accepted = 0;
+    for (uint32_t bins : bins_list)
+        for (uint32_t keep : keep_list)
+            for (int timepoints = 0; timepoints < 2; ++timepoints) {
+                std::vector<uint32_t> sizes(std::min(keep, 64u));
+                for (uint32_t i = 0; i < sizes.size(); ++i) sizes[i] = keep / 2u > i ? keep / 2u - i : 1u;
+                const uint32_t P = (uint32_t)sizes.size();
+                const uint64_t all = P >= 64u ? ~0ull : (1ull << P) - 1ull;
+                for (uint64_t mask : {0ull, P > 1u ? 2ull : 0ull, 0x5555555555555555ull & all}) {
+                    const pd::Plan p = pd::plan(bins, keep, timepoints != 0, P, sizes.data(), mask);
+                    const ad::Plan v = ad::plan(bins, keep, timepoints != 0, P, sizes.data(), mask);
+                    if (std::memcmp(&v.grouping(), &p.verdict.grouping(), sizeof(ecdna::Grouping)) != 0)
+                        return std::fprintf(stderr, "the verdict's grouping is not accept_draws'\n"), 1;
+                    for (const ad::Plan* q : {&p.verdict, &p.pool, &v}) {
+                        if (!ecdna::grouping_ok(*q, q->n_slices, P, keep))
+                            return std::fprintf(stderr, "a plan's grouping refused at bins = %u, keep = %u, store %d, "
+                                                        "mask %llx\n", bins, keep, timepoints, (unsigned long long)mask), 1;
+                        ++accepted;
+                    }
+                }
+            }
+    std::printf("accepted %u\n", accepted);
+
+    // the keep store, four targets of two sizes: groups (100: 0 2) (80: 1 3); the timepoint store, three slices
+    const uint32_t keep_sizes[] = {100, 80, 100, 80}, tp_sizes[] = {20, 50, 35};
+    const ecdna::Grouping keep = ad::plan(9u, 200u, false, 4u, keep_sizes, 0);
+    const ecdna::Grouping tp = ad::plan(9u, 50u, true, 3u, tp_sizes, 0);
+    if (!ecdna::grouping_ok(keep, 1u, 4u, 200u) || !ecdna::grouping_ok(tp, 3u, 3u, 50u) || keep.n_groups != 2u ||
+        tp.n_groups != 3u)
+        return std::fprintf(stderr, "the groupings to break are not in order\n"), 1;
+    int bad = 0;
+    auto refused = [&](const ecdna::Grouping& g, uint32_t n_slices, uint32_t n_targets, uint32_t m, const char* what) {
+        if (ecdna::grouping_ok(g, n_slices, n_targets, m))
+            bad += std::fprintf(stderr, "taken: %s\n", what), 1;
+        else
+            std::printf("refused %s\n", what);
+    };
+    ecdna::Grouping g = keep;
+    g.group_offset[1] = 5;  // 0 5 4
+    refused(g, 1, 4, 200, "a decreasing group_offset");
+    g = tp;
+    g.slice_group[1] = 3;  // 0 3 2 3
+    refused(g, 3, 3, 50, "a decreasing slice_group");
+    g = keep;
+    g.slice_group[1] = 1;
+    refused(g, 1, 4, 200, "slice_group[n_slices] != n_groups");
+    g = keep;
+    g.group_targets[3] = 4;
+    refused(g, 1, 4, 200, "a target index >= n_targets");
+    g = keep;
+    g.group_m[1] = 0;
+    refused(g, 1, 4, 200, "group_m of 0");
+    g = keep;
+    g.group_m[1] = 201;
+    refused(g, 1, 4, 200, "group_m of m + 1");
+    g = keep;
+    g.n_groups = 0;
+    g.slice_group[1] = 0;
+    refused(g, 1, 4, 200, "n_groups of 0");
+    g = keep;
+    g.n_groups = 5;  // five groups over four targets: the last three empty, every table in order otherwise
+    g.slice_group[1] = 5;
+    for (uint32_t j = 2; j < 5; ++j) g.group_m[j] = 1, g.group_offset[j + 1] = 4;
+    refused(g, 1, 4, 200, "n_groups of n_targets + 1");
+    g = keep;
+    g.slice_group[0] = 1;
+    refused(g, 1, 4, 200, "slice_group[0] != 0");
+    g = keep;
+    g.group_offset[0] = 1;
+    refused(g, 1, 4, 200, "group_offset[0] != 0");
+    g = keep;
+    g.group_offset[2] = 5;
+    refused(g, 1, 4, 200, "group_offset[n_groups] > n_targets");
+    refused(keep, 0, 4, 200, "no slice");
+    refused(keep, 65, 4, 200, "65 slices");
+    refused(keep, 1, 65, 200, "65 targets");
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && std::strcmp(argv[1], "plan") == 0) return print_plan(argc, argv);
     if (argc > 1 && std::strcmp(argv[1], "lds") == 0) return check_lds();
     if (argc > 1 && std::strcmp(argv[1], "bytes") == 0) return print_bytes();
     if (argc > 1 && std::strcmp(argv[1], "validate") == 0) return check_validate();
-    std::fprintf(stderr, "usage: pool_draws_check plan K S MASK m0 m1 ... | lds | bytes | validate\n");
+    if (argc > 1 && std::strcmp(argv[1], "grouping") == 0) return check_grouping();
+    std::fprintf(stderr, "usage: pool_draws_check plan K S MASK m0 m1 ... | lds | bytes | validate | grouping\n");
     return 2;
 }

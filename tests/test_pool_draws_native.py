@@ -1,6 +1,6 @@
 """The host side of the pooling over thinning draws on the CPU (ecdna-evo_amd/csrc/ssa_pool_draws.hpp; thinned pooling
 mapping v1): every branch of the call's validation, the verdict's and the pooling's grouping of the targets, the LDS
-plan at its limits and the byte counts.
+plan at its limits, the byte counts, and the launches' check of the group tables (ssa_launch.h grouping_ok).
 
 tests/native/pool_draws_check.cpp is a stand-alone program, built for the host alone with the address and
 undefined-behaviour sanitizers (any report ends it with an error); it is never loaded into Python."""
@@ -149,3 +149,15 @@ def test_byte_counts(check):
 
 def test_every_validation_branch(check):
     assert _run(check, "validate") == ["validate ok"]
+
+
+def test_the_launch_check_takes_every_planned_grouping_and_refuses_each_broken_table(check):
+    lines = _run(check, "grouping")
+    # 8 bins x 8 keep sizes x 2 stores x 3 masks, and per case the verdict's, the pooling's and accept_draws' own plan
+    assert lines[0] == "accepted %d" % (8 * 8 * 2 * 3 * 3)
+    # one refusal per clause of the conditions launch_accept_draws and launch_pool_draws had spelled out
+    assert lines[1:] == ["refused " + what for what in (
+        "a decreasing group_offset", "a decreasing slice_group", "slice_group[n_slices] != n_groups",
+        "a target index >= n_targets", "group_m of 0", "group_m of m + 1", "n_groups of 0", "n_groups of n_targets + 1",
+        "slice_group[0] != 0", "group_offset[0] != 0", "group_offset[n_groups] > n_targets",
+        "no slice", "65 slices", "65 targets")]
