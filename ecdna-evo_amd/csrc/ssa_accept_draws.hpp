@@ -24,8 +24,10 @@ constexpr uint32_t kMaxDraws = kThinDraws;  // 64: the draw index takes 6 bits
 // ECDNA_E_INVALID, which names the field; "" for a block the engine takes. keep_cells: the kept cells of the store the
 // block names (a context without it: the largest any store keeps). store_T: the timepoints of the timepoint keep block,
 // 0 for a context without it (the block is then refused for its state, not for n_targets). Reads host memory only.
+// finds_thresholds: the call is ecdna_ssa_ctx_select_draws, whose block carries no threshold rows (ssa_select_draws.hpp):
+// in the place of the threshold rules it must have none; every other rule and message is this call's.
 inline std::string invalid(uint32_t hist_bins, uint32_t keep_cells, uint32_t store_T, uint64_t n_replicates,
-                           const ecdna_ssa_accept_draws_t& a) {
+                           const ecdna_ssa_accept_draws_t& a, bool finds_thresholds = false) {
     if (a.struct_size != sizeof(ecdna_ssa_accept_draws_t))
         return "accept_draws.struct_size must be sizeof(ecdna_ssa_accept_draws_t)";
     if (a.reserved) return "accept_draws.reserved must be 0";
@@ -45,8 +47,14 @@ inline std::string invalid(uint32_t hist_bins, uint32_t keep_cells, uint32_t sto
                    std::to_string(keep_cells) + "]: a target with more measured cells than were kept cannot be served";
     if (a.n_draws < 1u || a.n_draws > kMaxDraws) return "accept_draws.n_draws must be in [1, 64]";
     if (a.first_draw > kMaxDraws - a.n_draws) return "accept_draws.first_draw + n_draws must be <= 64";
-    if (a.n_thresholds < 1u || a.n_thresholds > kMaxAcceptRows) return "accept_draws.n_thresholds must be in [1, 32]";
-    if (!a.thresholds) return "accept_draws.thresholds is NULL";
+    if (finds_thresholds) {
+        if (a.n_thresholds) return "select_draws.n_thresholds must be 0: the call finds the thresholds";
+        if (a.thresholds) return "select_draws.thresholds must be NULL: the call finds the thresholds";
+    } else {
+        if (a.n_thresholds < 1u || a.n_thresholds > kMaxAcceptRows)
+            return "accept_draws.n_thresholds must be in [1, 32]";
+        if (!a.thresholds) return "accept_draws.thresholds is NULL";
+    }
     for (uint32_t q = 0; q < a.n_thresholds; ++q) {
         const ecdna_accept_threshold_t& t = a.thresholds[q];
         const double v[4] = {t.ks, t.mean_rel, t.entropy_rel, t.frequency_diff};

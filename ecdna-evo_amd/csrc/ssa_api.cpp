@@ -2,7 +2,7 @@
 // device-resident run contexts, chunking by HBM capacity, and launches of the
 // stepper and end-of-run kernels (ssa_kernels.hip, ssa_hist.hip, ssa_subsample.hip, ssa_snapstats.hip,
 // ssa_passage.hip, ssa_cohort.hip), of the post-launch acceptance pass (ssa_accept.hip) and of the passes over the kept
-// samples (ssa_rescore.hip, ssa_thin.hip, ssa_accept_draws.hip, ssa_pool_draws.hip). The kept samples of the keep block and of the timepoint keep block lie in one kind of store
+// samples (ssa_rescore.hip, ssa_thin.hip, ssa_accept_draws.hip, ssa_pool_draws.hip, ssa_select_draws.hip). The kept samples of the keep block and of the timepoint keep block lie in one kind of store
 // (KeptStore), and every pass over them has one implementation, which the two blocks' entry points call.
 //
 // This file replaces, for one GPU, the per-replicate driver loop of the
@@ -24,6 +24,7 @@
 #include "../../include/ecdna_ssa.h"
 #include "ssa_accept_draws.hpp"
 #include "ssa_pool_draws.hpp"
+#include "ssa_select_draws.hpp"
 #include "ssa_cohort.hpp"
 #include "ssa_keep.hpp"
 #include "ssa_launch.h"
@@ -399,6 +400,12 @@ struct ecdna_ssa_ctx {
     // the pooling over thinning draws (ecdna_ssa_ctx_pool_draws): the call's own target CDFs and scalars, and its pooled
     // arrays, thinned [targets][sets][bins] then kept [slices][sets][bins] u64. The call is synchronous and holds no result.
     AcceptBuf pdr_cdf, pdr_scalars, pdr_pool;
+    // the select over thinning draws (ecdna_ssa_ctx_select_draws / _select_draws_digits): the call's own target CDFs and
+    // scalars, its keys [4][n x n_draws] u64 and one pass's histogram; the block the keys were made for, kept between
+    // the passes of _select_draws_digits until a launch replaces the kept samples they were made from
+    AcceptBuf sdr_cdf, sdr_scalars, sdr_keys, sdr_hist;
+    bool sdr_keys_valid = false;
+    ecdna::select_draws::Block sdr_block;
 };
 
 namespace {
@@ -432,7 +439,7 @@ void free_ctx(ecdna_ssa_ctx* c) {
                          &c->sel_hist, &c->pool_hist, &c->gat_index, &c->gat_headers, &c->gat_cells, &c->kept.stats,
                          &c->kept.cdf, &c->kept.scalars, &c->kept_tp.stats, &c->kept_tp.cdf, &c->kept_tp.scalars,
                          &c->adr_cdf, &c->adr_scalars, &c->adr_passes, &c->adr_sums, &c->pdr_cdf, &c->pdr_scalars,
-                         &c->pdr_pool})
+                         &c->pdr_pool, &c->sdr_cdf, &c->sdr_scalars, &c->sdr_keys, &c->sdr_hist})
         if (b->ptr) (void)hipFree(b->ptr);
     delete c;
 }
@@ -1252,8 +1259,39 @@ int select_source(const ecdna_ssa_ctx* c, uint32_t source, uint64_t timepoint_ma
 // to the global histogram is shared by 2,048 keys (the C4 sweep: 2,048 workgroups per distance).
 constexpr uint32_t kSelectRepsPerBlock = 8u * ecdna::kSelectBlock;
 
-// One digit pass: out_hist[x][j][d], j < K, for the prefixes[x * stride + j]. Makes the keys first unless the context
-// holds those of this source and mask. Synchronises.
+// One pass's histogram on the device: [4][kMaxSelectGroups][256] u64.
+constexpr uint64_t kSelectHistWords = (uint64_t)ecdna::select::kDistances * ecdna::kMaxSelectGroups * ecdna::select::kDigits;
+
+// One digit pass over keys [4][n] on stream st: out_hist[x][j][d], j < K, for the prefixes[x * stride + j]. d_hist: the
+// device histogram, kSelectHistWords. Synchronises.
+int digit_pass(const uint64_t* keys, uint32_t n, void* d_hist, uint32_t pass, uint32_t K, const uint64_t* prefixes,
+               uint32_t stride, uint64_t* out_hist, hipStream_t st) {
+    namespace sel = ecdna::select;
+    ecdna::SelectArgs a{};
+    a.keys = keys;
+    a.hist = static_cast<unsigned long long*>(d_hist);
+    a.n = n;
+    a.pass = pass;
+    a.reps_per_block = kSelectRepsPerBlock;
+    uint32_t group[sel::kDistances][sel::kMaxRanks];
+    for (uint32_t x = 0; x < sel::kDistances; ++x) {
+        uint64_t top[sel::kMaxRanks];
+        for (uint32_t j = 0; j < K; ++j) top[j] = sel::key_top(prefixes[(uint64_t)x * stride + j], pass);
+        a.n_groups[x] = sel::dedup(top, K, a.prefix[x], group[x]);
+    }
+    TRY(hipMemsetAsync(d_hist, 0, kSelectHistWords * sizeof(uint64_t), st));
+    TRY(ecdna::launch_select_digits(a, st));
+    TRY(hipStreamSynchronize(st));
+    std::vector<uint64_t> dev(kSelectHistWords);
+    TRY(to_host(dev.data(), static_cast<const uint64_t*>(d_hist), kSelectHistWords));
+    for (uint32_t x = 0; x < sel::kDistances; ++x)
+        for (uint32_t j = 0; j < K; ++j)
+            std::copy_n(dev.data() + ((uint64_t)x * ecdna::kMaxSelectGroups + group[x][j]) * sel::kDigits, sel::kDigits,
+                        out_hist + ((uint64_t)x * K + j) * sel::kDigits);
+    return ECDNA_OK;
+}
+
+// One digit pass over the source's keys: makes them first unless the context holds those of this source and mask.
 int select_pass(ecdna_ssa_ctx* c, uint32_t source, const SelectSource& s, uint32_t pass, uint32_t K,
                 const uint64_t* prefixes, uint32_t stride, uint64_t* out_hist, const char* who) {
     namespace sel = ecdna::select;
@@ -1267,8 +1305,7 @@ int select_pass(ecdna_ssa_ctx* c, uint32_t source, const SelectSource& s, uint32
         c->sel_keys_valid = false;
         TRY(accept_reserve(&c->sel_keys, sel::kDistances * n * sizeof(uint64_t), "keys", who));
     }
-    constexpr uint64_t hist_words = (uint64_t)sel::kDistances * ecdna::kMaxSelectGroups * sel::kDigits;
-    TRY(accept_reserve(&c->sel_hist, hist_words * sizeof(uint64_t), "histogram", who));
+    TRY(accept_reserve(&c->sel_hist, kSelectHistWords * sizeof(uint64_t), "histogram", who));
     if (!cached) {
         ecdna::SelectKeyArgs k{};
         k.stats = s.src.stats;
@@ -1285,28 +1322,8 @@ int select_pass(ecdna_ssa_ctx* c, uint32_t source, const SelectSource& s, uint32
         c->sel_tmask = s.tmask;
         c->sel_keys_valid = true;
     }
-    ecdna::SelectArgs a{};
-    a.keys = static_cast<const uint64_t*>(c->sel_keys.ptr);
-    a.hist = static_cast<unsigned long long*>(c->sel_hist.ptr);
-    a.n = (uint32_t)n;
-    a.pass = pass;
-    a.reps_per_block = kSelectRepsPerBlock;
-    uint32_t group[sel::kDistances][sel::kMaxRanks];
-    for (uint32_t x = 0; x < sel::kDistances; ++x) {
-        uint64_t top[sel::kMaxRanks];
-        for (uint32_t j = 0; j < K; ++j) top[j] = sel::key_top(prefixes[(uint64_t)x * stride + j], pass);
-        a.n_groups[x] = sel::dedup(top, K, a.prefix[x], group[x]);
-    }
-    TRY(hipMemsetAsync(c->sel_hist.ptr, 0, hist_words * sizeof(uint64_t), st));
-    TRY(ecdna::launch_select_digits(a, st));
-    TRY(hipStreamSynchronize(st));
-    std::vector<uint64_t> dev(hist_words);
-    TRY(to_host(dev.data(), static_cast<const uint64_t*>(c->sel_hist.ptr), hist_words));
-    for (uint32_t x = 0; x < sel::kDistances; ++x)
-        for (uint32_t j = 0; j < K; ++j)
-            std::copy_n(dev.data() + ((uint64_t)x * ecdna::kMaxSelectGroups + group[x][j]) * sel::kDigits, sel::kDigits,
-                        out_hist + ((uint64_t)x * K + j) * sel::kDigits);
-    return ECDNA_OK;
+    return digit_pass(static_cast<const uint64_t*>(c->sel_keys.ptr), (uint32_t)n, c->sel_hist.ptr, pass, K, prefixes,
+                      stride, out_hist, st);
 }
 
 // ---- the passes over a store of kept samples: what a call of the keep block (one slice) and its twin of the timepoint
@@ -1584,6 +1601,55 @@ void threshold_row(const ecdna_accept_threshold_t& t, double* row) {
     row[2] = t.entropy_rel;
     row[3] = t.frequency_diff;
 }
+
+// ---- ecdna_ssa_ctx_select_draws / _select_draws_digits: what both do after their own argument checks ----
+
+// The store of the block and the state checks, as draws_store makes them under select_draws::invalid.
+int select_draws_store(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a, KeptStore** out) {
+    return draws_store(c, a, "select_draws", [&](uint32_t keep_cells) {
+        return ecdna::select_draws::invalid(c->p.hist_bins, keep_cells, c->kept_tp.T, c->p.n_replicates, *a);
+    }, out);
+}
+
+// The keys of every (replicate, draw) of the block, into the context's buffer, which it then holds for that block.
+// n > 0. Synchronises: the uploads read host copies on this stack.
+int select_draws_keys(ecdna_ssa_ctx* c, const KeptStore& s, const ecdna_ssa_accept_draws_t& a, const char* who) {
+    namespace sd = ecdna::select_draws;
+    const uint32_t bins = c->p.hist_bins, P = a.n_targets;
+    hipStream_t st = c->last_stream;
+    c->sdr_keys_valid = false;
+    TRY(accept_reserve(&c->sdr_cdf, sd::cdf_bytes(P, bins), "target CDFs", who));
+    TRY(accept_reserve(&c->sdr_scalars, sd::scalars_bytes(P), "target scalars", who));
+    TRY(accept_reserve(&c->sdr_keys, sd::keys_bytes(c->p.n_replicates, a.n_draws), "keys", who));
+    std::vector<double> host_cdf, host_scalars;
+    if (const int rc = upload_targets(a.target_hists, P, bins, &host_cdf, &host_scalars, c->sdr_cdf.ptr,
+                                      c->sdr_scalars.ptr, st)) {
+        (void)hipStreamSynchronize(st);  // (an upload already enqueued may still read its host copy)
+        return rc;
+    }
+    const ecdna::accept_draws::Plan pl =
+        ecdna::accept_draws::plan(bins, s.m, a.timepoints == 1u, P, a.sample_cells, a.timepoint_mask);
+    ecdna::SelectDrawsArgs k{};
+    k.s = draws_args(c, s, a, pl, pl.lds, c->sdr_cdf.ptr, c->sdr_scalars.ptr);
+    k.g = pl.grouping();
+    k.keys = static_cast<uint64_t*>(c->sdr_keys.ptr);
+    const hipError_t le = ecdna::launch_select_draws_keys(k, st);
+    const hipError_t se = hipStreamSynchronize(st);  // (also when the launch was refused: the uploads read the stack)
+    TRY(le);
+    TRY(se);
+    c->sdr_block = sd::remember(a, bins);
+    c->sdr_keys_valid = true;
+    return ECDNA_OK;
+}
+
+// One digit pass over the keys select_draws_keys made.
+int select_draws_pass(ecdna_ssa_ctx* c, uint32_t n_draws, uint32_t pass, uint32_t K, const uint64_t* prefixes,
+                      uint32_t stride, uint64_t* out_hist, const char* who) {
+    TRY(accept_reserve(&c->sdr_hist, ecdna::select_draws::hist_bytes(), "histogram", who));
+    return digit_pass(static_cast<const uint64_t*>(c->sdr_keys.ptr),
+                      (uint32_t)ecdna::select_draws::n_keys(c->p.n_replicates, n_draws), c->sdr_hist.ptr, pass, K,
+                      prefixes, stride, out_hist, c->last_stream);
+}
 }  // namespace
 
 // library-internal entry points for ssa_comm.cpp (the RCCL reduction)
@@ -1769,6 +1835,7 @@ int ecdna_ssa_ctx_launch(ecdna_ssa_ctx* c, void* stream) {
     c->sel_keys_valid = false;  // (and the select passes' keys were made from its records)
     c->kept.valid = c->kept_tp.valid = false;  // (and the rescored records from its kept samples)
     c->adr_valid = false;  // (and the thinned acceptance's counts)
+    c->sdr_keys_valid = false;  // (and the select over thinning draws' keys)
     return ECDNA_OK;
 }
 
@@ -2383,6 +2450,67 @@ int ecdna_ssa_ctx_select(ecdna_ssa_ctx* c, const ecdna_ssa_select_t* s, uint64_t
     std::vector<uint64_t> hist((uint64_t)sel::kDistances * K * sel::kDigits);
     for (uint32_t pass = 0; pass < sel::kPasses; ++pass) {
         TRY(select_pass(c, s->source, src, pass, K, walk.prefixes(), sel::kMaxRanks, hist.data(), "ecdna_ssa_ctx_select"));
+        walk.feed(hist.data());
+    }
+    if (out_population) *out_population = walk.M;
+    for (uint32_t j = 0; j < K; ++j) {
+        if (out_ranks) out_ranks[j] = walk.rank[j];
+        for (uint32_t x = 0; x < sel::kDistances; ++x) {
+            if (out_values) out_values[(uint64_t)x * K + j] = walk.value(x, j);
+            if (out_counts_le) out_counts_le[(uint64_t)x * K + j] = walk.counts_le(x, j);
+        }
+    }
+    return ECDNA_OK;
+}
+
+// ---- the select over thinning draws (thinned select mapping v1): the keys of every (replicate, draw) of the block's
+// range, made by the thinning core on buffers of its own, and ecdna_ssa_ctx_select's digit passes and walk over them ----
+
+int ecdna_ssa_ctx_select_draws_digits(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a, uint32_t pass,
+                                      uint32_t n_prefixes, const uint64_t* prefixes, uint64_t* out_hist) {
+    namespace sd = ecdna::select_draws;
+    namespace sel = ecdna::select;
+    const char* who = "ecdna_ssa_ctx_select_draws_digits";
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    const std::string bad = sd::invalid_pass(pass, n_prefixes, prefixes, out_hist);
+    if (!bad.empty()) return fail(ECDNA_E_INVALID, bad);
+    KeptStore* s = nullptr;
+    TRY(select_draws_store(c, a, &s));
+    std::fill(out_hist, out_hist + (uint64_t)sel::kDistances * n_prefixes * sel::kDigits, 0ull);
+    if (!c->p.n_replicates) return ECDNA_OK;
+    TRY(hipSetDevice(c->device));
+    if (pass == 0u) {
+        TRY(select_draws_keys(c, *s, *a, who));
+    } else if (!c->sdr_keys_valid || !sd::same(c->sdr_block, *a, c->p.hist_bins)) {
+        return fail(ECDNA_E_STATE, "select_draws_digits: pass " + std::to_string(pass) +
+                                       " has no keys to read: pass 0 of the same block must come first (a launch "
+                                       "drops the keys)");
+    }
+    return select_draws_pass(c, a->n_draws, pass, n_prefixes, prefixes, n_prefixes, out_hist, who);
+}
+
+int ecdna_ssa_ctx_select_draws(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a, uint32_t n_ranks,
+                               const uint64_t* ranks, const double* fractions, uint64_t* out_population,
+                               uint64_t* out_ranks, double* out_values, uint64_t* out_counts_le) {
+    namespace sd = ecdna::select_draws;
+    namespace sel = ecdna::select;
+    const char* who = "ecdna_ssa_ctx_select_draws";
+    if (!c) return fail(ECDNA_E_INVALID, "ctx is NULL");
+    const std::string bad = sd::invalid_ranks(n_ranks, ranks, fractions);
+    if (!bad.empty()) return fail(ECDNA_E_INVALID, bad);
+    KeptStore* s = nullptr;
+    TRY(select_draws_store(c, a, &s));
+    const uint32_t K = n_ranks;
+    const bool any = c->p.n_replicates != 0u;
+    if (any) {
+        TRY(hipSetDevice(c->device));
+        TRY(select_draws_keys(c, *s, *a, who));
+    }
+    sel::Walk walk;
+    walk.start(K, ranks, fractions);
+    std::vector<uint64_t> hist((uint64_t)sel::kDistances * K * sel::kDigits, 0ull);
+    for (uint32_t pass = 0; pass < sel::kPasses; ++pass) {
+        if (any) TRY(select_draws_pass(c, a->n_draws, pass, K, walk.prefixes(), sel::kMaxRanks, hist.data(), who));
         walk.feed(hist.data());
     }
     if (out_population) *out_population = walk.M;

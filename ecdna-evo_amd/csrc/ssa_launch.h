@@ -443,6 +443,17 @@ struct SelectArgs {
     uint64_t prefix[4][kMaxSelectGroups]; // their top 8 * pass bits, shifted down (pass 0: 0); wave-uniform reads
 };
 
+// The keys of the select over thinning draws (ssa_select_draws.hip; ecdna_ssa_ctx_select_draws, thinned select mapping
+// v1): per replicate, draw of the range and distance, the maximum over the participating groups' targets of the key of
+// the record AcceptDrawsArgs' pass scores on that draw. Entry i * n_draws + (d - first_draw) of each distance's array;
+// ssa_select_digits then walks them as SelectArgs' keys with n = s.n * s.n_draws, which is below 2^32.
+struct SelectDrawsArgs {
+    DrawsArgs s;
+    Grouping g;
+    uint64_t* keys;                       // [4][n * n_draws]; select::kExcluded for a replicate with an error
+};
+static_assert(sizeof(SelectDrawsArgs) <= 4096, "the argument block of a launch");
+
 constexpr uint32_t kMaxSubsampleCells = 4096;  // LDS: 8 B of table per sampled cell and wave (<= 32 KiB)
 constexpr int kStepperBlock = 256;
 constexpr int kBinWideBlock = 64;  // bin store with 256 bins
@@ -607,6 +618,10 @@ hipError_t launch_accept_draws(const AcceptDrawsArgs& a, hipStream_t stream);
 // The pooling pass over thinning draws (ssa_pool_draws.hip): pool_draws_waves' LDS plan for a.s.table_slots; a.thinned
 // and a.kept zeroed on the stream before it. A block that disagrees with the plan is refused: hipErrorInvalidValue.
 hipError_t launch_pool_draws(const PoolDrawsArgs& a, hipStream_t stream);
+// The keys of the select over thinning draws (ssa_select_draws.hip): ssa_thin's LDS plan (thin_waves) for
+// a.s.table_slots. A block that disagrees with the plan, or whose keys 32 bits do not index, is refused:
+// hipErrorInvalidValue.
+hipError_t launch_select_draws_keys(const SelectDrawsArgs& a, hipStream_t stream);
 // The select passes (ssa_select.hip): the keys of every replicate (a.n > 0), and one digit pass over them (a.hist zeroed
 // on the stream before it; the dynamic LDS table is 1 KiB per group of the distance with most, 32 KiB at most).
 hipError_t launch_select_keys(const SelectKeyArgs& a, hipStream_t stream);

@@ -1,6 +1,6 @@
 // ssa_thinwave.hpp — a wave's work on one kept sample, shared by the thinning passes over the kept samples: ssa_thin.hip,
-// ssa_accept_draws.hip and ssa_pool_draws.hip (thinning mapping v1 and the two mappings over its draws,
-// include/ecdna_ssa.h). ssa_rescore.hip keeps its own copy of the scan: through wave_kept_hist it measured
+// ssa_accept_draws.hip, ssa_pool_draws.hip and ssa_select_draws.hip (thinning mapping v1 and the three mappings over
+// its draws, include/ecdna_ssa.h). ssa_rescore.hip keeps its own copy of the scan: through wave_kept_hist it measured
 // half a percent slower (docs/PERF_LOG.md). The wave's LDS, the kept sample as its header gives it, the one scan
 // into the full histogram, one thinned draw, the record of a group on the whole or the thinned sample, and the
 // acceptance rule on such a record. The passes perform the same operations in the same order through these, which is

@@ -37,6 +37,15 @@ __device__ __forceinline__ double wave_max(double x) {
     return x;
 }
 
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint64_t y = __shfl_xor((unsigned long long)x, o, 64);
+        x = y > x ? y : x;
+    }
+    return x;
+}
+
 // The lane's inclusive prefix sum over the wave (lanes 0 .. lane); lane 63 holds the wave's total.
 template <typename T>
 __device__ __forceinline__ T wave_inclusive_scan(T x, uint32_t lane) {

@@ -247,6 +247,12 @@ ACCEPT_DRAWS_MAX = 64  # thinning draws of one kept sample: the draw index takes
 # uint64_t* out_kept) (added within ABI v13; thinned pooling mapping v1): the block of accept_draws, one row of it, and
 # the host arrays [n_targets][n_param_sets][hist_bins] and [n_slices][n_param_sets][hist_bins] (either may be NULL)
 POOL_DRAWS_ARGTYPES = [C.c_void_p, C.POINTER(AcceptDraws), C.c_uint32, C.c_void_p, C.c_void_p]
+# ecdna_ssa_ctx_select_draws(c, a, n_ranks, ranks, fractions, out_population, out_ranks, out_values, out_counts_le) and
+# ecdna_ssa_ctx_select_draws_digits(c, a, pass, n_prefixes, prefixes, out_hist): the select over thinning draws (added
+# within ABI v13; thinned select mapping v1). Their block is AcceptDraws without threshold rows.
+SELECT_DRAWS_ARGTYPES = [C.c_void_p, C.POINTER(AcceptDraws), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                         C.c_void_p, C.c_void_p, C.c_void_p]
+SELECT_DRAWS_DIGITS_ARGTYPES = [C.c_void_p, C.POINTER(AcceptDraws), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
 
 
 class Select(C.Structure):

@@ -61,6 +61,8 @@ EXPORTS = [
     "ecdna_ssa_ctx_pool_draws",
     "ecdna_ssa_ctx_select",
     "ecdna_ssa_ctx_select_digits",
+    "ecdna_ssa_ctx_select_draws",
+    "ecdna_ssa_ctx_select_draws_digits",
     "ecdna_ssa_ctx_download_rng_words",
     "ecdna_ssa_ctx_row_stride",
     "ecdna_ssa_ctx_geometry",
@@ -225,6 +227,12 @@ def lib():
     if hasattr(L, "ecdna_ssa_ctx_pool_draws"):
         L.ecdna_ssa_ctx_pool_draws.argtypes = list(abi.POOL_DRAWS_ARGTYPES)
         L.ecdna_ssa_ctx_pool_draws.restype = C.c_int
+    # (likewise added within v13: ABC thresholds over thinning draws)
+    if hasattr(L, "ecdna_ssa_ctx_select_draws"):
+        L.ecdna_ssa_ctx_select_draws.argtypes = list(abi.SELECT_DRAWS_ARGTYPES)
+        L.ecdna_ssa_ctx_select_draws.restype = C.c_int
+        L.ecdna_ssa_ctx_select_draws_digits.argtypes = list(abi.SELECT_DRAWS_DIGITS_ARGTYPES)
+        L.ecdna_ssa_ctx_select_draws_digits.restype = C.c_int
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -599,13 +607,14 @@ class Context:
         self._accept_draws_shape = (int(a.n_thresholds), int(n_draws))
 
     def _accept_draws_block(self, targets, sample_cells, thresholds, n_draws, first_draw, timepoints, store):
-        """The block ecdna_ssa_accept_draws_t of accept_draws' arguments, and the arrays it points into."""
+        """The block ecdna_ssa_accept_draws_t of accept_draws' arguments, and the arrays it points into. thresholds
+        None: a block without threshold rows, as select_draws takes it."""
         if store not in ("keep", "timepoints"):
             raise ValueError('store must be "keep" or "timepoints"')
         tgt = np.ascontiguousarray(targets, dtype=np.uint64)
         if tgt.ndim != 2 or tgt.shape[1] != self.params.hist_bins:
             raise ValueError("targets must be [P][hist_bins]: one histogram of hist_bins entries per target")
-        thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+        thr = np.ascontiguousarray(thresholds if thresholds is not None else np.zeros((0, 4)), dtype=np.float64)
         if thr.ndim != 2 or thr.shape[1] != 4:
             raise ValueError("thresholds must be [Q][4]: ks, mean_rel, entropy_rel, frequency_diff per row")
         for name, v in (("n_targets", tgt.shape[0]), ("n_thresholds", thr.shape[0]), ("n_draws", n_draws),
@@ -617,7 +626,8 @@ class Context:
                             n_thresholds=thr.shape[0], timepoint_mask=timepoint_mask(timepoints))
         a.target_hists = tgt.ctypes.data_as(C.POINTER(C.c_uint64))
         a.sample_cells = cells.ctypes.data_as(C.POINTER(C.c_uint32))
-        a.thresholds = thr.ctypes.data_as(C.POINTER(abi.AcceptThreshold))
+        if thresholds is not None:
+            a.thresholds = thr.ctypes.data_as(C.POINTER(abi.AcceptThreshold))
         return a, (tgt, cells, thr)
 
     def download_accept_draws(self) -> AcceptDrawsResult:
@@ -706,6 +716,45 @@ class Context:
         _check(lib().ecdna_ssa_ctx_select_digits(self.h, int(source), timepoint_mask(timepoints), int(pass_),
                                                  pre.shape[1], pre.ctypes.data, hist.ctypes.data),
                "ecdna_ssa_ctx_select_digits")
+        return hist
+
+    def select_draws(self, targets, sample_cells, n_draws: int = 64, first_draw: int = 0, timepoints=None,
+                     store: str = "keep", ranks=None, fractions=None) -> SelectResult:
+        """ABC thresholds over thinning draws (ecdna_ssa_ctx_select_draws, thinned select mapping v1): select()'s order
+        statistics over the pairs (error-free replicate, thinning draw) of accept_draws()' arguments without thresholds —
+        the population is (error-free replicates) x n_draws, and a pair's key the maximum over the participating slots of
+        the distance accept_draws scores on that draw. accept_draws() with a finite value as its one threshold has
+        sums[0].sum() == counts_le. Synchronous; stores no record, needs no rescore and leaves the rescored records and
+        the results of accept, accept_draws and select as they are."""
+        L = _lib_with("ecdna_ssa_ctx_select_draws", "ABC thresholds over thinning draws")
+        rk, fr = select_ranks(ranks, fractions)
+        K = len(rk) if rk is not None else len(fr)
+        a, _alive = self._accept_draws_block(targets, sample_cells, None, n_draws, first_draw, timepoints, store)
+        population = C.c_uint64()
+        out_ranks = np.zeros(K, dtype=np.uint64)
+        values = np.zeros((4, K), dtype=np.float64)
+        counts_le = np.zeros((4, K), dtype=np.uint64)
+        _check(L.ecdna_ssa_ctx_select_draws(self.h, C.byref(a), K, rk.ctypes.data if rk is not None else None,
+                                            fr.ctypes.data if fr is not None else None, C.byref(population),
+                                            out_ranks.ctypes.data, values.ctypes.data, counts_le.ctypes.data),
+               "ecdna_ssa_ctx_select_draws")
+        return SelectResult(int(population.value), out_ranks, values, counts_le)
+
+    def select_draws_digits(self, targets, sample_cells, pass_: int, prefixes, n_draws: int = 64, first_draw: int = 0,
+                            timepoints=None, store: str = "keep") -> np.ndarray:
+        """One pass of select_draws on this context's replicates (ecdna_ssa_ctx_select_draws_digits), the shard
+        primitive: select_digits() over the keys of every (replicate, draw). Pass 0 makes the keys; the later passes
+        read them and must name the same block. Shards' arrays sum."""
+        L = _lib_with("ecdna_ssa_ctx_select_draws_digits", "ABC thresholds over thinning draws")
+        pre = np.ascontiguousarray(prefixes, dtype=np.uint64)
+        if pre.ndim != 2 or pre.shape[0] != 4 or not (1 <= pre.shape[1] <= abi.SELECT_MAX_RANKS):
+            raise ValueError(f"prefixes must be [4][K], K in 1 .. {abi.SELECT_MAX_RANKS}")
+        if not (0 <= int(pass_) < abi.SELECT_PASSES):
+            raise ValueError(f"pass_ = {pass_} must be in 0 .. {abi.SELECT_PASSES - 1}")
+        a, _alive = self._accept_draws_block(targets, sample_cells, None, n_draws, first_draw, timepoints, store)
+        hist = np.zeros((4, pre.shape[1], 256), dtype=np.uint64)
+        _check(L.ecdna_ssa_ctx_select_draws_digits(self.h, C.byref(a), int(pass_), pre.shape[1], pre.ctypes.data,
+                                                   hist.ctypes.data), "ecdna_ssa_ctx_select_draws_digits")
         return hist
 
     def download_cohort(self) -> CohortResult:

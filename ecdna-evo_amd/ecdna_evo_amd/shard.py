@@ -241,6 +241,28 @@ def select(ctx, source: int, ranks=None, fractions=None, timepoints=None, group=
     return walk.result()
 
 
+def select_draws(ctx, targets, sample_cells, n_draws: int = 64, first_draw: int = 0, timepoints=None,
+                 store: str = "keep", ranks=None, fractions=None, group=None, device=None):
+    """Context.select_draws over every rank's shard: the exact order statistics of the distances over the whole run's
+    pairs (replicate, thinning draw), the same engine.SelectResult on every rank. It is select() with
+    Context.select_draws_digits in the loop: pass 0 makes each shard's keys, and eight all-reduces (int64, sum) of the
+    [4][K][256] arrays join the shards. `device` as for select()."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    K = len(ranks) if ranks is not None else len(fractions if fractions is not None else ())
+    walk = SelectWalk(K, ranks=ranks, fractions=fractions)
+    for p in range(SelectWalk.PASSES):
+        hist = ctx.select_draws_digits(targets, sample_cells, p, walk.prefixes, n_draws, first_draw, timepoints, store)
+        t = torch.from_numpy(hist.view(np.int64))  # (counts stay far below 2^63)
+        if device is not None:
+            t = t.to(device)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        walk.feed(t.cpu().numpy().view(np.uint64))
+    return walk.result()
+
+
 def pool_accepted(ctx, threshold: int, group=None, device=None):
     """Context.pool_accepted over every rank's shard: the whole run's posterior predictive histogram
     [n_param_sets][hist_bins] u64, the same on every rank. Each rank pools its own accepted replicates' kept samples

@@ -43,7 +43,12 @@
 extern "C" {
 #endif
 
-/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): the accepted
+/* Added within v13 (additive: no layout and no existing function changes, the version stays 13): ABC thresholds over
+ * thinning draws — ecdna_ssa_ctx_select_draws and its shard primitive ecdna_ssa_ctx_select_draws_digits (below; thinned
+ * select mapping v1): exact order statistics of the four distances over the pairs (replicate, thinning draw) of a block
+ * ecdna_ssa_accept_draws_t without threshold rows, found by the radix select of ecdna_ssa_ctx_select over keys that no
+ * stored record stands behind. A context that never calls them allocates and launches nothing new.
+ * Added within v13 (additive: no layout and no existing function changes, the version stays 13): the accepted
  * thinnings pooled — ecdna_ssa_ctx_pool_draws (below; thinned pooling mapping v1): per global parameter set, the
  * histograms of the thinned samples on the draws that pass one threshold row of ecdna_ssa_accept_draws_t, and the whole
  * kept samples weighted by the number of passing draws, in one synchronous pass. A context that never calls it allocates
@@ -1003,6 +1008,64 @@ int ecdna_ssa_ctx_select(ecdna_ssa_ctx* c, const ecdna_ssa_select_t* s, uint64_t
  * small all-reduces instead of a gather of every record. Synchronous. */
 int ecdna_ssa_ctx_select_digits(ecdna_ssa_ctx* c, uint32_t source, uint64_t timepoint_mask, uint32_t pass,
                                 uint32_t n_prefixes, const uint64_t* prefixes, uint64_t* out_hist);
+/* ABC thresholds over thinning draws (added within ABI v13). ecdna_ssa_ctx_accept_draws and ecdna_ssa_ctx_pool_draws
+ * take threshold rows; ecdna_ssa_ctx_select finds thresholds, but over stored records, the records of one draw. In ABC
+ * with measurement noise the population a quantile cuts is the pseudo-datasets, the pairs (replicate, draw): "keep the
+ * closest 1 %" is the rank ceil(0.01 x M) order statistic over all of them, and with it sum(passes) / M is the
+ * acceptance rate that was asked for. The calls below find it in one pass of the thinning core and the eight digit
+ * passes of ecdna_ssa_ctx_select, without storing a record.
+ *
+ * Thinned select mapping v1.
+ *  - Block. ecdna_ssa_accept_draws_t means what it means for ecdna_ssa_ctx_accept_draws — the store, the slots,
+ *    sample_cells, the draw range, timepoint_mask — except that it carries no threshold rows: n_thresholds must be 0 and
+ *    thresholds NULL. n_replicates x n_draws must be below 2^32: the digit pass indexes its keys with 32 bits.
+ *  - Population. The pairs (i, d): replicate i error-free under rule 1 of thinned acceptance mapping v1 (the one-summary
+ *    rule on the keep store and on a snapshot context; on a passage context the rule per participating phase), draw d in
+ *    first_draw .. first_draw + n_draws - 1. Its size is M = (error-free replicates) x n_draws.
+ *  - Key. key_x(i, d) is the maximum, over the participating slots, of select mapping v1's key of distance x of the
+ *    record thinned acceptance mapping v1 scores for that slot on draw d: the same key per slice, stream tag and
+ *    grouping, the same f64 operations in the same order, the same whole-sample rule when m1 >= a + b (one record,
+ *    counted on every draw). A guard record (the header's, the size's, the 2^16 draws') has four zero distances and so
+ *    the key of 0.0. Nothing of thinning mapping v1 or of thinned acceptance mapping v1 changes.
+ *  - Order statistics, ranks from fractions, over-rank (value +inf, counts_le = M) and the reporting of NaN are exactly
+ *    select mapping v1's, over these M keys. Ranks are u64; M can reach 2^32.
+ *  - Contracts, all equalities of integers or of bits.
+ *    S1. ecdna_ssa_ctx_select_draws_digits(block, pass, prefixes) equals the sum, over the draws d of the range, of
+ *        ecdna_ssa_ctx_select_digits(source 12 or 13, timepoint_mask, pass, prefixes) taken after the sized rescore at
+ *        draw d (ecdna_ssa_ctx_rescore_sized or _rescore_timepoints_sized with the same targets and sizes). So
+ *        ecdna_ssa_ctx_select_draws equals select mapping v1's walk over the union of those keys.
+ *    S2. For a finite value_x(k), ecdna_ssa_ctx_accept_draws with the same block and one row — that value on x, +inf on
+ *        the other three — gives sums[0] that, summed over the sets, equal counts_le_x(k); no smaller threshold reaches k.
+ *    S3. With n_draws = 1 the four outputs are bit for bit those of ecdna_ssa_ctx_select on source 12 or 13 after the
+ *        sized rescore at that draw.
+ *    S4. Shards' digit arrays sum to the whole run's. Nothing depends on chunk, shard, grid or device.
+ *
+ * The calls own their buffers: the keys, [4][n_replicates x n_draws] u64 (32 x n x n_draws bytes: 2.1 GB at n = 2^20 and
+ * 64 draws), one pass's histogram, the target CDFs and scalars; allocated at the first call, grown by later ones, freed at
+ * destroy. ecdna_ssa_ctx_select_draws makes the keys once and its eight passes over them.
+ * ecdna_ssa_ctx_select_draws_digits makes them in pass 0, and the context remembers the block they were made for (its
+ * fields, and copies of target_hists and sample_cells): a pass above 0 whose block differs, or that follows a relaunch,
+ * returns ECDNA_E_STATE — pass 0 of the same block must come first. The calls leave untouched the keys and validity of
+ * ecdna_ssa_ctx_select, the rescored records of both stores, and the results of ecdna_ssa_ctx_accept,
+ * ecdna_ssa_ctx_accept_draws and ecdna_ssa_ctx_pool_draws. They need no earlier rescore.
+ *
+ * Both are synchronous, as ecdna_ssa_ctx_select and _select_digits are, and run on the stream of the last launch.
+ * ranks, fractions and n_ranks (K) follow the rules of ecdna_ssa_select_t; pass, n_prefixes, prefixes and out_hist those
+ * of ecdna_ssa_ctx_select_digits. Any output of ecdna_ssa_ctx_select_draws may be NULL.
+ * ECDNA_E_INVALID (the message names the field): everything ecdna_ssa_ctx_accept_draws refuses, with the same messages,
+ * but for its threshold rules; select_draws.n_thresholds != 0 or select_draws.thresholds != NULL; n_replicates x n_draws
+ * >= 2^32; n_ranks outside 1 .. 32, both or neither of ranks and fractions, a rank of 0, a fraction outside (0, 1] or
+ * NaN; pass > 7, n_prefixes outside 1 .. 32, NULL prefixes or out_hist.
+ * ECDNA_E_STATE: before a launch; a context without the named block; a pass above 0 without pass 0 of the same block.
+ * ECDNA_E_NOMEM: a buffer does not fit (the message carries its bytes; a narrower draw range needs fewer); the context
+ * stays usable and its other outputs intact. */
+int ecdna_ssa_ctx_select_draws(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a,
+                               uint32_t n_ranks, const uint64_t* ranks, const double* fractions,
+                               uint64_t* out_population, uint64_t* out_ranks,
+                               double* out_values /* [4][K] */, uint64_t* out_counts_le /* [4][K] */);
+int ecdna_ssa_ctx_select_draws_digits(ecdna_ssa_ctx* c, const ecdna_ssa_accept_draws_t* a, uint32_t pass,
+                                      uint32_t n_prefixes, const uint64_t* prefixes /* [4][K] */,
+                                      uint64_t* out_hist /* [4][K][256] */);
 /* Reference draws (ECDNA_FLAG_REFERENCE_DRAWS, ABI v7): per replicate, the number of 32-bit words its ChaCha8
  * stream (seed_from_u64(seed), stream seed*10 + r) had handed out when it stopped — where the reference's
  * end-of-run subsampling continues the same rng (into_subsampled(nb, &mut rng), src/main.rs:110-123, 184-197;
