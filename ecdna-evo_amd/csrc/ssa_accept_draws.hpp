@@ -20,6 +20,30 @@ namespace accept_draws {
 
 constexpr uint32_t kMaxDraws = kThinDraws;  // 64: the draw index takes 6 bits
 
+#pragma GCC visibility push(hidden)  // (shared by the library's own units: not for its symbol table)
+// Two rules every acceptance call has (ecdna_ssa_ctx_accept, _select, _select_digits, and the calls over this block),
+// as the message of ECDNA_E_INVALID or "". who: the prefix the call's fields are named under.
+// The timepoint mask: no bit at or above T; mask 0 stands for all T (all_timepoints).
+inline uint64_t all_timepoints(uint32_t T) { return T >= 64u ? ~0ull : (1ull << T) - 1ull; }
+inline std::string invalid_timepoint_mask(const std::string& who, uint64_t mask, uint32_t T) {
+    if (mask & ~all_timepoints(T)) return who + ".timepoint_mask has bits at or above T = " + std::to_string(T);
+    return "";
+}
+// The threshold rows: every threshold >= 0 and not NaN.
+inline std::string invalid_threshold_rows(const std::string& who, uint32_t n, const ecdna_accept_threshold_t* rows) {
+    for (uint32_t q = 0; q < n; ++q) {
+        const ecdna_accept_threshold_t& t = rows[q];
+        const double v[4] = {t.ks, t.mean_rel, t.entropy_rel, t.frequency_diff};
+        const char* names[4] = {"ks", "mean_rel", "entropy_rel", "frequency_diff"};
+        for (int k = 0; k < 4; ++k)
+            if (!(v[k] >= 0.0))
+                return who + ".thresholds[" + std::to_string(q) + "]." + names[k] +
+                       " must be >= 0 (+inf switches it off) and not NaN";
+    }
+    return "";
+}
+#pragma GCC visibility pop
+
 // What is wrong with the block on a context of hist_bins bins and n_replicates replicates, as the message of
 // ECDNA_E_INVALID, which names the field; "" for a block the engine takes. keep_cells: the kept cells of the store the
 // block names (a context without it: the largest any store keeps). store_T: the timepoints of the timepoint keep block,
@@ -55,19 +79,10 @@ inline std::string invalid(uint32_t hist_bins, uint32_t keep_cells, uint32_t sto
             return "accept_draws.n_thresholds must be in [1, 32]";
         if (!a.thresholds) return "accept_draws.thresholds is NULL";
     }
-    for (uint32_t q = 0; q < a.n_thresholds; ++q) {
-        const ecdna_accept_threshold_t& t = a.thresholds[q];
-        const double v[4] = {t.ks, t.mean_rel, t.entropy_rel, t.frequency_diff};
-        const char* names[4] = {"ks", "mean_rel", "entropy_rel", "frequency_diff"};
-        for (int k = 0; k < 4; ++k)
-            if (!(v[k] >= 0.0))
-                return "accept_draws.thresholds[" + std::to_string(q) + "]." + names[k] +
-                       " must be >= 0 (+inf switches it off) and not NaN";
-    }
+    std::string bad = invalid_threshold_rows("accept_draws", a.n_thresholds, a.thresholds);
     // the acceptance's timepoints: the targets of the keep store, the slices of the timepoint store (== n_targets)
-    const uint32_t T = a.n_targets;
-    if (T < 64u && (a.timepoint_mask >> T))
-        return "accept_draws.timepoint_mask has bits at or above T = " + std::to_string(T);
+    if (bad.empty()) bad = invalid_timepoint_mask("accept_draws", a.timepoint_mask, a.n_targets);
+    if (!bad.empty()) return bad;
     if (n_replicates >= (1ull << 32)) return "accept_draws: n_replicates must be < 2^32";
     return "";
 }
@@ -89,7 +104,7 @@ inline Plan plan(uint32_t bins, uint32_t keep_cells, bool timepoints, uint32_t n
                  uint64_t timepoint_mask) {
     Plan p;
     const uint32_t P = std::min(n_targets, kMaxCohortTargets);
-    const uint64_t all = P >= 64u ? ~0ull : (1ull << P) - 1ull;
+    const uint64_t all = all_timepoints(P);
     const uint64_t mask = timepoint_mask ? (timepoint_mask & all) : all;
     uint32_t at = 0;
     auto add = [&](const thin::Groups& g, uint32_t first_target, uint64_t take) {

@@ -20,11 +20,9 @@
 #include <type_traits>
 
 #include "../../include/ecdna_ssa.h"
+#include "ssa_ctx.hpp"
 
-// from ssa_api.cpp (library-internal)
-__attribute__((visibility("hidden"))) int ecdna_ssa_internal_fail(int code, const std::string& msg);
-__attribute__((visibility("hidden"))) int ecdna_ssa_internal_ctx_outputs(ecdna_ssa_ctx* c, uint64_t** d_hist, ecdna_totals_t** d_tot, uint32_t* n_sets,
-                                   uint32_t* bins, int* device, void** stream);
+using namespace ecdna::api;
 
 namespace {
 
@@ -77,11 +75,11 @@ Rccl& rccl() {
 
 int need_rccl() {
     Rccl& r = rccl();
-    return r.ok ? ECDNA_OK : ecdna_ssa_internal_fail(ECDNA_E_COMM, r.why);
+    return r.ok ? ECDNA_OK : fail(ECDNA_E_COMM, r.why);
 }
 
 int nccl_fail(ncclResult_t e, const char* what) {
-    return ecdna_ssa_internal_fail(ECDNA_E_COMM, std::string(what) + ": " + rccl().error_string(e));
+    return fail(ECDNA_E_COMM, std::string(what) + ": " + rccl().error_string(e));
 }
 
 }  // namespace
@@ -89,7 +87,7 @@ int nccl_fail(ncclResult_t e, const char* what) {
 extern "C" {
 
 int ecdna_ssa_comm_unique_id(uint8_t out_id[ECDNA_COMM_ID_BYTES]) {
-    if (!out_id) return ecdna_ssa_internal_fail(ECDNA_E_INVALID, "out_id is NULL");
+    if (!out_id) return fail(ECDNA_E_INVALID, "out_id is NULL");
     if (int rc = need_rccl()) return rc;
     static_assert(sizeof(ncclUniqueId) == ECDNA_COMM_ID_BYTES, "ncclUniqueId size");
     ncclUniqueId id;
@@ -101,10 +99,10 @@ int ecdna_ssa_comm_unique_id(uint8_t out_id[ECDNA_COMM_ID_BYTES]) {
 int ecdna_ssa_comm_init_rank(const uint8_t id[ECDNA_COMM_ID_BYTES], int n_ranks, int rank, int device,
                              void** out_comm) {
     if (!id || !out_comm || n_ranks < 1 || rank < 0 || rank >= n_ranks)
-        return ecdna_ssa_internal_fail(ECDNA_E_INVALID, "comm_init_rank: bad arguments");
+        return fail(ECDNA_E_INVALID, "comm_init_rank: bad arguments");
     *out_comm = nullptr;
     if (int rc = need_rccl()) return rc;
-    if (hipSetDevice(device) != hipSuccess) return ecdna_ssa_internal_fail(ECDNA_E_NODEVICE, "hipSetDevice failed");
+    if (hipSetDevice(device) != hipSuccess) return fail(ECDNA_E_NODEVICE, "hipSetDevice failed");
     ncclUniqueId uid;
     std::memcpy(&uid, id, sizeof(uid));
     ncclComm_t comm = nullptr;
@@ -115,7 +113,7 @@ int ecdna_ssa_comm_init_rank(const uint8_t id[ECDNA_COMM_ID_BYTES], int n_ranks,
 
 int ecdna_ssa_comm_init_all(int n_devices, const int* devices, void** out_comms) {
     if (n_devices < 1 || !devices || !out_comms)
-        return ecdna_ssa_internal_fail(ECDNA_E_INVALID, "comm_init_all: bad arguments");
+        return fail(ECDNA_E_INVALID, "comm_init_all: bad arguments");
     if (int rc = need_rccl()) return rc;
     ncclComm_t* comms = reinterpret_cast<ncclComm_t*>(out_comms);
     if (ncclResult_t e = rccl().init_all(comms, n_devices, devices)) return nccl_fail(e, "ncclCommInitAll");
@@ -132,7 +130,7 @@ int ecdna_ssa_comm_destroy(void* comm) {
 int ecdna_ssa_reduce_hist(void* comm, uint64_t* d_hist, ecdna_totals_t* d_totals, uint32_t n_param_sets,
                           uint32_t hist_bins, void* stream) {
     if (!comm || !d_hist || !d_totals || n_param_sets == 0 || hist_bins == 0)
-        return ecdna_ssa_internal_fail(ECDNA_E_INVALID, "reduce_hist: bad arguments");
+        return fail(ECDNA_E_INVALID, "reduce_hist: bad arguments");
     if (int rc = need_rccl()) return rc;
     Rccl& r = rccl();
     ncclComm_t cm = reinterpret_cast<ncclComm_t>(comm);
@@ -149,14 +147,9 @@ int ecdna_ssa_reduce_hist(void* comm, uint64_t* d_hist, ecdna_totals_t* d_totals
 }
 
 int ecdna_ssa_ctx_reduce(ecdna_ssa_ctx* c, void* comm) {
-    uint64_t* h = nullptr;
-    ecdna_totals_t* t = nullptr;
-    uint32_t sets = 0, bins = 0;
-    int device = 0;
-    void* stream = nullptr;
-    if (int rc = ecdna_ssa_internal_ctx_outputs(c, &h, &t, &sets, &bins, &device, &stream)) return rc;
-    if (hipSetDevice(device) != hipSuccess) return ecdna_ssa_internal_fail(ECDNA_E_HIP, "hipSetDevice failed");
-    return ecdna_ssa_reduce_hist(comm, h, t, sets, bins, stream);
+    TRY(ctx_launched(c, "reduce before launch"));
+    if (hipSetDevice(c->device) != hipSuccess) return fail(ECDNA_E_HIP, "hipSetDevice failed");
+    return ecdna_ssa_reduce_hist(comm, c->d_hist, c->d_tot, c->p.n_param_sets, c->p.hist_bins, c->last_stream);
 }
 
 }  // extern "C"

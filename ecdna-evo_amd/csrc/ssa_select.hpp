@@ -1,12 +1,17 @@
 // ssa_select.hpp — the host side of ecdna_ssa_ctx_select / ecdna_ssa_ctx_select_digits (select mapping v1,
-// include/ecdna_ssa.h): the order-preserving key of a distance and its inverse, and the rank walk of the 8-bit radix
-// select over the per-pass digit histograms. No HIP runtime call and nothing of the API: the key functions are the ones
-// the kernels of ssa_select.hip call, and the walk is pure, so both are checked on a machine without a GPU
+// include/ecdna_ssa.h): the order-preserving key of a distance and its inverse, the rank walk of the 8-bit radix
+// select over the per-pass digit histograms, the driver that runs the passes and writes the outputs (select::run, which
+// ecdna_ssa_ctx_select and ecdna_ssa_ctx_select_draws call in ssa_api_passes.cpp), and the rank and digit-pass rules of
+// both calls. No HIP runtime call and nothing of the API: the key functions are the ones the kernels of ssa_select.hip
+// call, and the walk and the driver are pure, so all are checked on a machine without a GPU
 // (tests/native/select_check.cpp, tests/test_select_native.py).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <string>
+#include <vector>
 
 namespace ecdna {
 namespace select {
@@ -138,6 +143,60 @@ inline uint32_t dedup(const uint64_t* top, uint32_t K, uint64_t* unique, uint32_
     }
     return G;
 }
+
+#pragma GCC visibility push(hidden)  // (host-side helpers of the library's own units: not for its symbol table)
+
+// The rank rules of ecdna_ssa_select_t, as the message of ECDNA_E_INVALID ("" for ranks the engine takes). who: the
+// prefix the call's arguments are named under, "select" or "select_draws".
+inline std::string invalid_ranks(const std::string& who, uint32_t n_ranks, const uint64_t* ranks,
+                                 const double* fractions) {
+    if (n_ranks < 1u || n_ranks > kMaxRanks) return who + ".n_ranks must be in [1, 32]";
+    if ((ranks != nullptr) == (fractions != nullptr))
+        return "exactly one of " + who + ".ranks and " + who + ".fractions must be given";
+    for (uint32_t j = 0; j < n_ranks; ++j) {
+        if (ranks && ranks[j] == 0u) return who + ".ranks[" + std::to_string(j) + "] must be >= 1";
+        if (fractions && !(fractions[j] > 0.0 && fractions[j] <= 1.0))
+            return who + ".fractions[" + std::to_string(j) + "] must be in (0, 1] and not NaN";
+    }
+    return "";
+}
+
+// The rules of one digit pass, likewise. who: "select_digits" or "select_draws_digits".
+inline std::string invalid_pass(const std::string& who, uint32_t pass, uint32_t n_prefixes, const void* prefixes,
+                                const void* out_hist) {
+    if (pass >= kPasses) return who + ".pass must be in [0, 7]";
+    if (n_prefixes < 1u || n_prefixes > kMaxRanks) return who + ".n_prefixes must be in [1, 32]";
+    if (!prefixes) return who + ".prefixes is NULL";
+    if (!out_hist) return who + ".out_hist is NULL";
+    return "";
+}
+
+// The whole select of K ranks (or fractions): the eight digit passes, each fed to the walk, then the four outputs
+// (any may be NULL): the population, the ranks [K], and the values and counts_le [4][K]. pass(pass_index, prefixes,
+// hist_out) -> int fills hist_out [4][K][256] for the prefixes [4][kMaxRanks] (a pass that writes nothing leaves
+// zeros: an empty population); the first non-zero code it returns ends the select and is returned.
+template <class Pass>
+int run(uint32_t K, const uint64_t* ranks, const double* fractions, Pass pass, uint64_t* out_population,
+        uint64_t* out_ranks, double* out_values, uint64_t* out_counts_le) {
+    Walk walk;
+    walk.start(K, ranks, fractions);
+    std::vector<uint64_t> hist((uint64_t)kDistances * K * kDigits, 0ull);
+    while (!walk.done()) {
+        if (const int rc = pass(walk.pass, walk.prefixes(), hist.data())) return rc;
+        walk.feed(hist.data());
+    }
+    if (out_population) *out_population = walk.M;
+    for (uint32_t j = 0; j < K; ++j) {
+        if (out_ranks) out_ranks[j] = walk.rank[j];
+        for (uint32_t x = 0; x < kDistances; ++x) {
+            if (out_values) out_values[(uint64_t)x * K + j] = walk.value(x, j);
+            if (out_counts_le) out_counts_le[(uint64_t)x * K + j] = walk.counts_le(x, j);
+        }
+    }
+    return 0;
+}
+
+#pragma GCC visibility pop
 
 }  // namespace select
 }  // namespace ecdna

@@ -35,26 +35,13 @@ inline std::string invalid(uint32_t hist_bins, uint32_t keep_cells, uint32_t sto
     return "";
 }
 
-// The rank rules of ecdna_ssa_select_t, under the names of this call's arguments.
+// The rank rules of ecdna_ssa_select_t and the rules of ecdna_ssa_ctx_select_digits for one pass (ssa_select.hpp), under
+// the names of this call's arguments.
 inline std::string invalid_ranks(uint32_t n_ranks, const uint64_t* ranks, const double* fractions) {
-    if (n_ranks < 1u || n_ranks > select::kMaxRanks) return "select_draws.n_ranks must be in [1, 32]";
-    if ((ranks != nullptr) == (fractions != nullptr))
-        return "exactly one of select_draws.ranks and select_draws.fractions must be given";
-    for (uint32_t j = 0; j < n_ranks; ++j) {
-        if (ranks && ranks[j] == 0u) return "select_draws.ranks[" + std::to_string(j) + "] must be >= 1";
-        if (fractions && !(fractions[j] > 0.0 && fractions[j] <= 1.0))
-            return "select_draws.fractions[" + std::to_string(j) + "] must be in (0, 1] and not NaN";
-    }
-    return "";
+    return select::invalid_ranks("select_draws", n_ranks, ranks, fractions);
 }
-
-// The rules of ecdna_ssa_ctx_select_digits for one pass, under the names of this call's arguments.
 inline std::string invalid_pass(uint32_t pass, uint32_t n_prefixes, const void* prefixes, const void* out_hist) {
-    if (pass >= select::kPasses) return "select_draws_digits.pass must be in [0, 7]";
-    if (n_prefixes < 1u || n_prefixes > select::kMaxRanks) return "select_draws_digits.n_prefixes must be in [1, 32]";
-    if (!prefixes) return "select_draws_digits.prefixes is NULL";
-    if (!out_hist) return "select_draws_digits.out_hist is NULL";
-    return "";
+    return select::invalid_pass("select_draws_digits", pass, n_prefixes, prefixes, out_hist);
 }
 
 // The bytes of the call's own buffers: the keys [4][n x n_draws] u64 (2.1 GB at n = 2^20 and 64 draws) and one pass's

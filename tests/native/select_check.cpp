@@ -1,6 +1,6 @@
 // select_check.cpp — the host side of ecdna_ssa_ctx_select (ecdna-evo_amd/csrc/ssa_select.hpp) on the CPU, for
-// tests/test_select_native.py: the key map the kernels call and the rank walk ssa_api.cpp makes. Built for the host
-// alone, with the address and undefined-behaviour sanitizers.
+// tests/test_select_native.py: the key map the kernels call and the select driver ssa_api_passes.cpp calls. Built for
+// the host alone, with the address and undefined-behaviour sanitizers.
 //
 //   select_check edges    checks on a list of edge doubles (0, the smallest denormal, 1 - ulp, 1, the largest finite,
 //                         +inf, NaN, and their negatives) that the key is monotone, that key(value(key)) is the key and
@@ -9,8 +9,9 @@
 //                           ranks k1 k2 ...          or          fractions f1 f2 ...
 //                           bits b b b ...     four lines, one per distance: the population's values as the hex bit
 //                                              patterns of their doubles (all four lines equally long)
-//                         It makes the keys with key_of, per pass builds the histograms [4][K][256] of the walk's
-//                         prefixes as the engine does (dedup, key_top, key_digit), and feeds them to select::Walk.
+//                         It makes the keys with key_of and runs the engine's driver (select::run) with a pass that
+//                         builds the histograms [4][K][256] of the walk's prefixes as the engine does (dedup, key_top,
+//                         key_digit); what it prints is what the driver wrote to its four outputs.
 //                         Output: "population M", "ranks ...", and per distance "values <hex bits> ..." and
 //                         "counts ...".
 #include <cinttypes>
@@ -94,34 +95,37 @@ int main(int argc, char** argv) {
     for (const auto& k : keys)
         if (k.size() != keys[0].size()) return std::fprintf(stderr, "select_check: bits lines differ in length\n"), 2;
 
-    sel::Walk walk;
-    walk.start(K, ranks.empty() ? nullptr : ranks.data(), fractions.empty() ? nullptr : fractions.data());
-    std::vector<uint64_t> hist((size_t)sel::kDistances * K * sel::kDigits);
-    while (!walk.done()) {
-        std::fill(hist.begin(), hist.end(), 0ull);
+    // one pass's histograms [4][K][256] of the walk's prefixes [4][kMaxRanks], from the host's keys
+    auto host_pass = [&](uint32_t pass, const uint64_t* prefixes, uint64_t* hist) {
         for (uint32_t x = 0; x < sel::kDistances; ++x) {
             uint64_t top[sel::kMaxRanks], unique[sel::kMaxRanks];
             uint32_t group[sel::kMaxRanks];
-            for (uint32_t j = 0; j < K; ++j) top[j] = sel::key_top(walk.prefixes()[x * sel::kMaxRanks + j], walk.pass);
+            for (uint32_t j = 0; j < K; ++j) top[j] = sel::key_top(prefixes[x * sel::kMaxRanks + j], pass);
             const uint32_t G = sel::dedup(top, K, unique, group);
             std::vector<uint64_t> table((size_t)G * sel::kDigits, 0ull);  // the device's table of distinct prefixes
             for (const uint64_t key : keys[x])
                 for (uint32_t g = 0; g < G; ++g)
-                    if (sel::key_top(key, walk.pass) == unique[g]) ++table[g * sel::kDigits + sel::key_digit(key, walk.pass)];
+                    if (sel::key_top(key, pass) == unique[g]) ++table[g * sel::kDigits + sel::key_digit(key, pass)];
             for (uint32_t j = 0; j < K; ++j)
                 for (uint32_t d = 0; d < sel::kDigits; ++d)
                     hist[((size_t)x * K + j) * sel::kDigits + d] = table[group[j] * sel::kDigits + d];
         }
-        walk.feed(hist.data());
-    }
-    std::printf("population %" PRIu64 "\nranks", walk.M);
-    for (uint32_t j = 0; j < K; ++j) std::printf(" %" PRIu64, walk.rank[j]);
+        return 0;
+    };
+    uint64_t population = 0;
+    std::vector<uint64_t> out_ranks(K), counts((size_t)sel::kDistances * K);
+    std::vector<double> values((size_t)sel::kDistances * K);
+    if (sel::run(K, ranks.empty() ? nullptr : ranks.data(), fractions.empty() ? nullptr : fractions.data(), host_pass,
+                 &population, out_ranks.data(), values.data(), counts.data()))
+        return std::fprintf(stderr, "select_check: the driver returned an error\n"), 1;
+    std::printf("population %" PRIu64 "\nranks", population);
+    for (uint32_t j = 0; j < K; ++j) std::printf(" %" PRIu64, out_ranks[j]);
     std::printf("\n");
     for (uint32_t x = 0; x < sel::kDistances; ++x) {
         std::printf("values");
-        for (uint32_t j = 0; j < K; ++j) std::printf(" %016" PRIx64, bits_of(walk.value(x, j)));
+        for (uint32_t j = 0; j < K; ++j) std::printf(" %016" PRIx64, bits_of(values[(size_t)x * K + j]));
         std::printf("\ncounts");
-        for (uint32_t j = 0; j < K; ++j) std::printf(" %" PRIu64, walk.counts_le(x, j));
+        for (uint32_t j = 0; j < K; ++j) std::printf(" %" PRIu64, counts[(size_t)x * K + j]);
         std::printf("\n");
     }
     return 0;

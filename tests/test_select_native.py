@@ -1,6 +1,7 @@
 """The host side of ecdna_ssa_ctx_select on the CPU (ecdna-evo_amd/csrc/ssa_select.hpp): the key map — the function the
-kernels of ssa_select.hip call, NaN branch included, which no run reaches — and the rank walk ssa_api.cpp makes over the
-passes' histograms, against the numpy restatement (tests/select_law.py), bit for bit.
+kernels of ssa_select.hip call, NaN branch included, which no run reaches — and the driver ssa_api_passes.cpp calls
+(select::run: the rank walk over the passes' histograms and the four outputs), against the numpy restatement
+(tests/select_law.py), bit for bit.
 
 tests/native/select_check.cpp is a stand-alone program, built for the host alone with the address and
 undefined-behaviour sanitizers (any report ends it with an error); it is never loaded into Python."""
