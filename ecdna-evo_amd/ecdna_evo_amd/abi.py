@@ -243,16 +243,6 @@ class AcceptDraws(C.Structure):
 
 
 ACCEPT_DRAWS_MAX = 64  # thinning draws of one kept sample: the draw index takes 6 bits
-# int ecdna_ssa_ctx_pool_draws(c, const ecdna_ssa_accept_draws_t* a, uint32_t threshold, uint64_t* out_thinned,
-# uint64_t* out_kept) (added within ABI v13; thinned pooling mapping v1): the block of accept_draws, one row of it, and
-# the host arrays [n_targets][n_param_sets][hist_bins] and [n_slices][n_param_sets][hist_bins] (either may be NULL)
-POOL_DRAWS_ARGTYPES = [C.c_void_p, C.POINTER(AcceptDraws), C.c_uint32, C.c_void_p, C.c_void_p]
-# ecdna_ssa_ctx_select_draws(c, a, n_ranks, ranks, fractions, out_population, out_ranks, out_values, out_counts_le) and
-# ecdna_ssa_ctx_select_draws_digits(c, a, pass, n_prefixes, prefixes, out_hist): the select over thinning draws (added
-# within ABI v13; thinned select mapping v1). Their block is AcceptDraws without threshold rows.
-SELECT_DRAWS_ARGTYPES = [C.c_void_p, C.POINTER(AcceptDraws), C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
-                         C.c_void_p, C.c_void_p, C.c_void_p]
-SELECT_DRAWS_DIGITS_ARGTYPES = [C.c_void_p, C.POINTER(AcceptDraws), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
 
 
 class Select(C.Structure):
@@ -328,6 +318,60 @@ class Instance(C.Structure):
         d["kernel_name"] = KERNEL_KINDS.get(d["kernel"], "?")
         d["schedule_name"] = SCHEDULE_NAMES.get(d["schedule"], "?")
         return d
+
+
+def _signatures():
+    """Every function include/ecdna_ssa.h declares, in its order of introduction: (name, restype, argtypes, added).
+    `added`: None for the calls every library of this ABI version has; for those added within v13, what they brought —
+    a same-box A/B may load a v13 library built before them, which runs everything else (engine._lib_with)."""
+    P, V, I, U32, U64 = C.POINTER, C.c_void_p, C.c_int, C.c_uint32, C.c_uint64
+    create = [P(Params), P(Ext), P(Passages), P(Cohort), P(Keep), P(KeepTimepoints)]  # the create chain's blocks
+    base = [
+        ("abi_version", I, []), ("strerror", C.c_char_p, [I]), ("last_error_message", C.c_char_p, []),
+        ("device_count", I, []), ("run", I, [P(Params), V, V, V, V]), ("ctx_create", I, create[:1] + [P(V)]),
+        ("ctx_set_outputs", I, [V, V, V]), ("ctx_launch", I, [V, V]), ("ctx_sync", I, [V, P(C.c_float), P(C.c_float)]),
+        ("ctx_device_outputs", I, [V, P(V), P(V)]), ("ctx_download", I, [V, V, V, V, V]),
+        ("ctx_download_snapshots", I, [V, V, V]), ("ctx_download_stats", I, [V, V]),
+        ("ctx_download_sample", I, [V, V, V]), ("ctx_download_rng_words", I, [V, V]),
+        ("ctx_row_stride", C.c_int64, [V]), ("ctx_geometry", I, [V, P(U64), P(U64)]),
+        ("ctx_instance", I, [V, P(Instance)]), ("ctx_destroy", I, [V]), ("comm_unique_id", I, [V]),
+        ("comm_init_rank", I, [V, I, I, I, P(V)]), ("comm_init_all", I, [I, P(I), P(V)]), ("comm_destroy", I, [V]),
+        ("reduce_hist", I, [V, V, V, U32, U32, V]), ("ctx_reduce", I, [V, V]),
+    ]
+    within_v13 = {
+        "per-snapshot statistics": [("ctx_create_ext", create[:2] + [P(V)]), ("ctx_download_snapshot_stats", [V] * 5)],
+        "serial passaging": [("ctx_create_passages", create[:3] + [P(V)]), ("ctx_download_passages", [V] * 7)],
+        "ABC rejection on the GPU": [("ctx_accept", [V, P(Accept)]),
+                                     ("ctx_download_accept", [V, V, V, P(U64), V, V])],
+        "ABC thresholds on the GPU": [("ctx_select", [V, P(Select), P(U64), V, V, V]),
+                                      ("ctx_select_digits", [V, U32, U64, U32, U32, V, V])],
+        "a cohort of targets": [("ctx_create_cohort", create[:4] + [P(V)]), ("ctx_download_cohort", [V, V, V])],
+        "kept samples": [("ctx_create_keep", create[:5] + [P(V)]), ("ctx_rescore", [V, U32, V]),
+                         ("ctx_download_rescored", [V, V]), ("ctx_pool_accepted", [V, U32, V]),
+                         ("ctx_download_kept", [V, U64, V, V, V])],
+        "kept timepoint samples": [("ctx_create_keep_timepoints", create + [P(V)]), ("ctx_rescore_timepoints", [V, V]),
+                                   ("ctx_download_rescored_timepoints", [V, V]),
+                                   ("ctx_pool_accepted_timepoints", [V, U32, V]),
+                                   ("ctx_download_kept_timepoints", [V, U64, V, V, V])],
+        "sized rescoring": [("ctx_rescore_sized", [V, P(Rescore)]), ("ctx_rescore_timepoints_sized", [V, V, V, U32])],
+        "acceptance over repeated thinnings": [("ctx_accept_draws", [V, P(AcceptDraws)]),
+                                               ("ctx_download_accept_draws", [V, V, V])],
+        # (c, block, threshold, out_thinned [n_targets][n_param_sets][hist_bins], out_kept [n_slices][..][..])
+        "pooling over thinning draws": [("ctx_pool_draws", [V, P(AcceptDraws), U32, V, V])],
+        # (c, block without threshold rows, n_ranks, ranks, fractions, out_population, out_ranks, out_values,
+        # out_counts_le) and (c, block, pass, n_prefixes, prefixes, out_hist)
+        "ABC thresholds over thinning draws": [("ctx_select_draws", [V, P(AcceptDraws), U32, V, V, P(U64), V, V, V]),
+                                               ("ctx_select_draws_digits", [V, P(AcceptDraws), U32, U32, V, V])],
+    }
+    rows = [("ecdna_ssa_" + n, r, a, None) for n, r, a in base]
+    return rows + [("ecdna_ssa_" + n, I, a, what) for what, calls in within_v13.items() for n, a in calls]
+
+
+SIGNATURES = _signatures()
+_ARGTYPES = {name: argtypes for name, _, argtypes, _ in SIGNATURES}
+POOL_DRAWS_ARGTYPES = _ARGTYPES["ecdna_ssa_ctx_pool_draws"]
+SELECT_DRAWS_ARGTYPES = _ARGTYPES["ecdna_ssa_ctx_select_draws"]
+SELECT_DRAWS_DIGITS_ARGTYPES = _ARGTYPES["ecdna_ssa_ctx_select_draws_digits"]
 
 
 SNAPSHOT_DTYPE = np.dtype([("time", "<f8"), ("nminus", "<u8"), ("nplus", "<u8"), ("taken", "<u4"),

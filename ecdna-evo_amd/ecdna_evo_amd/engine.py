@@ -21,60 +21,7 @@ PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # .../ec
 # ECDNA_SSA_LIB: development override (same-box A/B of two builds, tools/ab_build.sh)
 LIB_PATH = os.environ.get("ECDNA_SSA_LIB") or os.path.join(PKG_ROOT, "lib", "libecdna_ssa.so")
 
-EXPORTS = [
-    "ecdna_ssa_abi_version",
-    "ecdna_ssa_strerror",
-    "ecdna_ssa_last_error_message",
-    "ecdna_ssa_device_count",
-    "ecdna_ssa_run",
-    "ecdna_ssa_ctx_create",
-    "ecdna_ssa_ctx_create_ext",
-    "ecdna_ssa_ctx_create_passages",
-    "ecdna_ssa_ctx_create_cohort",
-    "ecdna_ssa_ctx_create_keep",
-    "ecdna_ssa_ctx_create_keep_timepoints",
-    "ecdna_ssa_ctx_set_outputs",
-    "ecdna_ssa_ctx_launch",
-    "ecdna_ssa_ctx_sync",
-    "ecdna_ssa_ctx_device_outputs",
-    "ecdna_ssa_ctx_download",
-    "ecdna_ssa_ctx_download_snapshots",
-    "ecdna_ssa_ctx_download_stats",
-    "ecdna_ssa_ctx_download_sample",
-    "ecdna_ssa_ctx_download_snapshot_stats",
-    "ecdna_ssa_ctx_download_passages",
-    "ecdna_ssa_ctx_download_cohort",
-    "ecdna_ssa_ctx_rescore",
-    "ecdna_ssa_ctx_download_rescored",
-    "ecdna_ssa_ctx_pool_accepted",
-    "ecdna_ssa_ctx_download_kept",
-    "ecdna_ssa_ctx_rescore_timepoints",
-    "ecdna_ssa_ctx_download_rescored_timepoints",
-    "ecdna_ssa_ctx_pool_accepted_timepoints",
-    "ecdna_ssa_ctx_download_kept_timepoints",
-    "ecdna_ssa_ctx_rescore_sized",
-    "ecdna_ssa_ctx_rescore_timepoints_sized",
-    "ecdna_ssa_ctx_accept",
-    "ecdna_ssa_ctx_download_accept",
-    "ecdna_ssa_ctx_accept_draws",
-    "ecdna_ssa_ctx_download_accept_draws",
-    "ecdna_ssa_ctx_pool_draws",
-    "ecdna_ssa_ctx_select",
-    "ecdna_ssa_ctx_select_digits",
-    "ecdna_ssa_ctx_select_draws",
-    "ecdna_ssa_ctx_select_draws_digits",
-    "ecdna_ssa_ctx_download_rng_words",
-    "ecdna_ssa_ctx_row_stride",
-    "ecdna_ssa_ctx_geometry",
-    "ecdna_ssa_ctx_instance",
-    "ecdna_ssa_ctx_destroy",
-    "ecdna_ssa_comm_unique_id",
-    "ecdna_ssa_comm_init_rank",
-    "ecdna_ssa_comm_init_all",
-    "ecdna_ssa_comm_destroy",
-    "ecdna_ssa_reduce_hist",
-    "ecdna_ssa_ctx_reduce",
-]
+EXPORTS = [name for name, _, _, _ in abi.SIGNATURES]
 
 
 class EngineError(RuntimeError):
@@ -103,136 +50,13 @@ def lib():
         raise EngineError(f"{LIB_PATH} is missing: build it with `make -C ecdna-evo_amd` (or __graft_entry__.build())")
     _ensure_single_hip_runtime()
     L = C.CDLL(LIB_PATH)
-    P = C.POINTER
-    L.ecdna_ssa_abi_version.restype = C.c_int
-    L.ecdna_ssa_strerror.argtypes = [C.c_int]
-    L.ecdna_ssa_strerror.restype = C.c_char_p
-    L.ecdna_ssa_last_error_message.restype = C.c_char_p
-    L.ecdna_ssa_device_count.restype = C.c_int
-    L.ecdna_ssa_run.argtypes = [P(abi.Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.ecdna_ssa_run.restype = C.c_int
-    L.ecdna_ssa_ctx_create.argtypes = [P(abi.Params), P(C.c_void_p)]
-    L.ecdna_ssa_ctx_create.restype = C.c_int
-    L.ecdna_ssa_ctx_set_outputs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.ecdna_ssa_ctx_set_outputs.restype = C.c_int
-    L.ecdna_ssa_ctx_launch.argtypes = [C.c_void_p, C.c_void_p]
-    L.ecdna_ssa_ctx_launch.restype = C.c_int
-    L.ecdna_ssa_ctx_sync.argtypes = [C.c_void_p, P(C.c_float), P(C.c_float)]
-    L.ecdna_ssa_ctx_sync.restype = C.c_int
-    L.ecdna_ssa_ctx_device_outputs.argtypes = [C.c_void_p, P(C.c_void_p), P(C.c_void_p)]
-    L.ecdna_ssa_ctx_device_outputs.restype = C.c_int
-    L.ecdna_ssa_ctx_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.ecdna_ssa_ctx_download.restype = C.c_int
-    L.ecdna_ssa_ctx_download_snapshots.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.ecdna_ssa_ctx_download_snapshots.restype = C.c_int
-    L.ecdna_ssa_ctx_download_stats.argtypes = [C.c_void_p, C.c_void_p]
-    L.ecdna_ssa_ctx_download_stats.restype = C.c_int
-    L.ecdna_ssa_ctx_download_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.ecdna_ssa_ctx_download_sample.restype = C.c_int
-    L.ecdna_ssa_ctx_download_rng_words.argtypes = [C.c_void_p, C.c_void_p]
-    L.ecdna_ssa_ctx_download_rng_words.restype = C.c_int
-    L.ecdna_ssa_ctx_row_stride.argtypes = [C.c_void_p]
-    L.ecdna_ssa_ctx_row_stride.restype = C.c_int64
-    L.ecdna_ssa_ctx_geometry.argtypes = [C.c_void_p, P(C.c_uint64), P(C.c_uint64)]
-    L.ecdna_ssa_ctx_geometry.restype = C.c_int
-    L.ecdna_ssa_ctx_instance.argtypes = [C.c_void_p, P(abi.Instance)]
-    L.ecdna_ssa_ctx_instance.restype = C.c_int
-    L.ecdna_ssa_ctx_destroy.argtypes = [C.c_void_p]
-    L.ecdna_ssa_ctx_destroy.restype = C.c_int
-    L.ecdna_ssa_comm_unique_id.argtypes = [C.c_void_p]
-    L.ecdna_ssa_comm_unique_id.restype = C.c_int
-    L.ecdna_ssa_comm_init_rank.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, P(C.c_void_p)]
-    L.ecdna_ssa_comm_init_rank.restype = C.c_int
-    L.ecdna_ssa_comm_init_all.argtypes = [C.c_int, P(C.c_int), P(C.c_void_p)]
-    L.ecdna_ssa_comm_init_all.restype = C.c_int
-    L.ecdna_ssa_comm_destroy.argtypes = [C.c_void_p]
-    L.ecdna_ssa_comm_destroy.restype = C.c_int
-    L.ecdna_ssa_reduce_hist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
-    L.ecdna_ssa_reduce_hist.restype = C.c_int
-    L.ecdna_ssa_ctx_reduce.argtypes = [C.c_void_p, C.c_void_p]
-    L.ecdna_ssa_ctx_reduce.restype = C.c_int
-    # (added within v13: a same-box A/B may load a v13 library built before them, which runs everything but the
-    # per-snapshot statistics; Context raises when a spec asks such a library for them)
-    if hasattr(L, "ecdna_ssa_ctx_create_ext"):
-        L.ecdna_ssa_ctx_create_ext.argtypes = [P(abi.Params), P(abi.Ext), P(C.c_void_p)]
-        L.ecdna_ssa_ctx_create_ext.restype = C.c_int
-        L.ecdna_ssa_ctx_download_snapshot_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ecdna_ssa_ctx_download_snapshot_stats.restype = C.c_int
-    # (likewise added within v13: serial passaging; Context raises when a spec asks an earlier library for it)
-    if hasattr(L, "ecdna_ssa_ctx_create_passages"):
-        L.ecdna_ssa_ctx_create_passages.argtypes = [P(abi.Params), P(abi.Ext), P(abi.Passages), P(C.c_void_p)]
-        L.ecdna_ssa_ctx_create_passages.restype = C.c_int
-        L.ecdna_ssa_ctx_download_passages.argtypes = [C.c_void_p] * 7
-        L.ecdna_ssa_ctx_download_passages.restype = C.c_int
-    # (likewise added within v13: ABC rejection on the GPU; Context.accept raises on an earlier library)
-    if hasattr(L, "ecdna_ssa_ctx_accept"):
-        L.ecdna_ssa_ctx_accept.argtypes = [C.c_void_p, P(abi.Accept)]
-        L.ecdna_ssa_ctx_accept.restype = C.c_int
-        L.ecdna_ssa_ctx_download_accept.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint64), C.c_void_p,
-                                                    C.c_void_p]
-        L.ecdna_ssa_ctx_download_accept.restype = C.c_int
-    # (likewise added within v13: ABC thresholds on the GPU; Context.select raises on an earlier library)
-    if hasattr(L, "ecdna_ssa_ctx_select"):
-        L.ecdna_ssa_ctx_select.argtypes = [C.c_void_p, P(abi.Select), P(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ecdna_ssa_ctx_select.restype = C.c_int
-        L.ecdna_ssa_ctx_select_digits.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
-                                                  C.c_void_p, C.c_void_p]
-        L.ecdna_ssa_ctx_select_digits.restype = C.c_int
-    # (likewise added within v13: a cohort of targets; Context raises when a spec asks an earlier library for it)
-    if hasattr(L, "ecdna_ssa_ctx_create_cohort"):
-        L.ecdna_ssa_ctx_create_cohort.argtypes = [P(abi.Params), P(abi.Ext), P(abi.Passages), P(abi.Cohort),
-                                                  P(C.c_void_p)]
-        L.ecdna_ssa_ctx_create_cohort.restype = C.c_int
-        L.ecdna_ssa_ctx_download_cohort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ecdna_ssa_ctx_download_cohort.restype = C.c_int
-    # (likewise added within v13: the kept samples; Context raises when a spec asks an earlier library for them)
-    if hasattr(L, "ecdna_ssa_ctx_create_keep"):
-        L.ecdna_ssa_ctx_create_keep.argtypes = [P(abi.Params), P(abi.Ext), P(abi.Passages), P(abi.Cohort), P(abi.Keep),
-                                                P(C.c_void_p)]
-        L.ecdna_ssa_ctx_create_keep.restype = C.c_int
-        L.ecdna_ssa_ctx_rescore.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-        L.ecdna_ssa_ctx_rescore.restype = C.c_int
-        L.ecdna_ssa_ctx_download_rescored.argtypes = [C.c_void_p, C.c_void_p]
-        L.ecdna_ssa_ctx_download_rescored.restype = C.c_int
-        L.ecdna_ssa_ctx_pool_accepted.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-        L.ecdna_ssa_ctx_pool_accepted.restype = C.c_int
-        L.ecdna_ssa_ctx_download_kept.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ecdna_ssa_ctx_download_kept.restype = C.c_int
-    # (likewise added within v13: the kept samples of every timepoint)
-    if hasattr(L, "ecdna_ssa_ctx_create_keep_timepoints"):
-        L.ecdna_ssa_ctx_create_keep_timepoints.argtypes = [P(abi.Params), P(abi.Ext), P(abi.Passages), P(abi.Cohort),
-                                                           P(abi.Keep), P(abi.KeepTimepoints), P(C.c_void_p)]
-        L.ecdna_ssa_ctx_create_keep_timepoints.restype = C.c_int
-        L.ecdna_ssa_ctx_rescore_timepoints.argtypes = [C.c_void_p, C.c_void_p]
-        L.ecdna_ssa_ctx_rescore_timepoints.restype = C.c_int
-        L.ecdna_ssa_ctx_download_rescored_timepoints.argtypes = [C.c_void_p, C.c_void_p]
-        L.ecdna_ssa_ctx_download_rescored_timepoints.restype = C.c_int
-        L.ecdna_ssa_ctx_pool_accepted_timepoints.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
-        L.ecdna_ssa_ctx_pool_accepted_timepoints.restype = C.c_int
-        L.ecdna_ssa_ctx_download_kept_timepoints.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ecdna_ssa_ctx_download_kept_timepoints.restype = C.c_int
-    # (likewise added within v13: the kept samples at each target's own number of measured cells)
-    if hasattr(L, "ecdna_ssa_ctx_rescore_sized"):
-        L.ecdna_ssa_ctx_rescore_sized.argtypes = [C.c_void_p, P(abi.Rescore)]
-        L.ecdna_ssa_ctx_rescore_sized.restype = C.c_int
-        L.ecdna_ssa_ctx_rescore_timepoints_sized.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
-        L.ecdna_ssa_ctx_rescore_timepoints_sized.restype = C.c_int
-    # (likewise added within v13: acceptance over repeated thinnings of the kept samples)
-    if hasattr(L, "ecdna_ssa_ctx_accept_draws"):
-        L.ecdna_ssa_ctx_accept_draws.argtypes = [C.c_void_p, P(abi.AcceptDraws)]
-        L.ecdna_ssa_ctx_accept_draws.restype = C.c_int
-        L.ecdna_ssa_ctx_download_accept_draws.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ecdna_ssa_ctx_download_accept_draws.restype = C.c_int
-    # (likewise added within v13: the accepted thinnings pooled)
-    if hasattr(L, "ecdna_ssa_ctx_pool_draws"):
-        L.ecdna_ssa_ctx_pool_draws.argtypes = list(abi.POOL_DRAWS_ARGTYPES)
-        L.ecdna_ssa_ctx_pool_draws.restype = C.c_int
-    # (likewise added within v13: ABC thresholds over thinning draws)
-    if hasattr(L, "ecdna_ssa_ctx_select_draws"):
-        L.ecdna_ssa_ctx_select_draws.argtypes = list(abi.SELECT_DRAWS_ARGTYPES)
-        L.ecdna_ssa_ctx_select_draws.restype = C.c_int
-        L.ecdna_ssa_ctx_select_draws_digits.argtypes = list(abi.SELECT_DRAWS_DIGITS_ARGTYPES)
-        L.ecdna_ssa_ctx_select_draws_digits.restype = C.c_int
+    for name, restype, argtypes, added in abi.SIGNATURES:
+        # (added within v13: a same-box A/B may load a v13 library built before the call, which runs everything else;
+        # _lib_with raises when such a library is asked for it. A call of the version's baseline must be there.)
+        if added is None or hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype = restype
+            fn.argtypes = argtypes
     ver = L.ecdna_ssa_abi_version()
     # (a same-box A/B, tools/ab_build.sh, may load a library of an earlier ABI version whose Params layout is this
     # one's: ECDNA_SSA_ABI_ANY=1 accepts versions ABI_SAME_LAYOUT_SINCE .. ABI_VERSION, never a newer one;
@@ -251,10 +75,14 @@ def _check(rc: int, what: str):
                           f"{L.ecdna_ssa_last_error_message().decode()}")
 
 
-def _lib_with(symbol: str, what: str):
-    """The library, which must export `symbol`: an entry point added within an ABI version, with `what` it brought."""
+_ADDED = {name: added for name, _, _, added in abi.SIGNATURES}
+
+
+def _lib_with(symbol: str, what: Optional[str] = None):
+    """The library, which must export `symbol`: an entry point added within an ABI version, with `what` it brought
+    (default: what abi.SIGNATURES says)."""
     if not hasattr(lib(), symbol):
-        raise EngineError(f"{LIB_PATH} predates {symbol} ({what})")
+        raise EngineError(f"{LIB_PATH} predates {symbol} ({what or _ADDED[symbol]})")
     return lib()
 
 
@@ -443,6 +271,43 @@ def select_ranks(ranks=None, fractions=None):
     return None, fr
 
 
+def _target_hists(targets, hist_bins: int) -> np.ndarray:
+    """`targets` as the ABI's [P][hist_bins] u64 histograms."""
+    tgt = np.ascontiguousarray(targets, dtype=np.uint64)
+    if tgt.ndim != 2 or tgt.shape[1] != hist_bins:
+        raise ValueError("targets must be [P][hist_bins]: one histogram of hist_bins entries per target")
+    return tgt
+
+
+def _threshold_rows(thresholds) -> np.ndarray:
+    """`thresholds` as the ABI's [Q][4] f64 rows."""
+    thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+    if thr.ndim != 2 or thr.shape[1] != 4:
+        raise ValueError("thresholds must be [Q][4]: ks, mean_rel, entropy_rel, frequency_diff per row")
+    return thr
+
+
+def _digit_arrays(pass_: int, prefixes):
+    """The checked `prefixes` [4][K] u64 of one pass of a select, and the [4][K][256] u64 array the pass fills."""
+    pre = np.ascontiguousarray(prefixes, dtype=np.uint64)
+    if pre.ndim != 2 or pre.shape[0] != 4 or not (1 <= pre.shape[1] <= abi.SELECT_MAX_RANKS):
+        raise ValueError(f"prefixes must be [4][K], K in 1 .. {abi.SELECT_MAX_RANKS}")
+    if not (0 <= int(pass_) < abi.SELECT_PASSES):
+        raise ValueError(f"pass_ = {pass_} must be in 0 .. {abi.SELECT_PASSES - 1}")
+    return pre, np.zeros((4, pre.shape[1], 256), dtype=np.uint64)
+
+
+def _select_result(K: int, name: str, call) -> SelectResult:
+    """A select's outputs, filled by call(out_population, out_ranks, out_values, out_counts_le): the last four
+    arguments of both select calls."""
+    population = C.c_uint64()
+    out_ranks = np.zeros(K, dtype=np.uint64)
+    values = np.zeros((4, K), dtype=np.float64)
+    counts_le = np.zeros((4, K), dtype=np.uint64)
+    _check(call(C.byref(population), out_ranks.ctypes.data, values.ctypes.data, counts_le.ctypes.data), name)
+    return SelectResult(int(population.value), out_ranks, values, counts_le)
+
+
 class Context:
     """A device-resident run (ecdna_ssa_ctx): create once, launch many times."""
 
@@ -475,15 +340,15 @@ class Context:
                 C.byref(self.params), ref(self.ext), ref(self.passages), ref(self.cohort), C.byref(self.keep),
                 C.byref(h)), "ecdna_ssa_ctx_create_keep")
         elif self.cohort is not None:  # (only a spec that asks for a cohort goes through _cohort)
-            _check(_lib_with("ecdna_ssa_ctx_create_cohort", "a cohort of targets").ecdna_ssa_ctx_create_cohort(
+            _check(_lib_with("ecdna_ssa_ctx_create_cohort").ecdna_ssa_ctx_create_cohort(
                 C.byref(self.params), ref(self.ext), ref(self.passages), C.byref(self.cohort), C.byref(h)),
                 "ecdna_ssa_ctx_create_cohort")
         elif self.passages is not None:  # (only a spec that asks for passages goes through _passages)
-            _check(_lib_with("ecdna_ssa_ctx_create_passages", "serial passaging").ecdna_ssa_ctx_create_passages(
+            _check(_lib_with("ecdna_ssa_ctx_create_passages").ecdna_ssa_ctx_create_passages(
                 C.byref(self.params), ref(self.ext), C.byref(self.passages), C.byref(h)),
                 "ecdna_ssa_ctx_create_passages")
         elif self.ext is not None:  # (only a spec that asks for the extension goes through _ext)
-            _check(_lib_with("ecdna_ssa_ctx_create_ext", "per-snapshot statistics").ecdna_ssa_ctx_create_ext(
+            _check(_lib_with("ecdna_ssa_ctx_create_ext").ecdna_ssa_ctx_create_ext(
                 C.byref(self.params), C.byref(self.ext), C.byref(h)), "ecdna_ssa_ctx_create_ext")
         else:
             _check(lib().ecdna_ssa_ctx_create(C.byref(self.params), C.byref(h)), "ecdna_ssa_ctx_create")
@@ -551,10 +416,8 @@ class Context:
                        list_capacity: int = 0):
         """Enqueue the acceptance pass on the stream of the last launch (ecdna_ssa_ctx_accept); download_accept
         returns its results. Arguments as accept()."""
-        _lib_with("ecdna_ssa_ctx_accept", "ABC rejection on the GPU")
-        thr = np.ascontiguousarray(thresholds, dtype=np.float64)
-        if thr.ndim != 2 or thr.shape[1] != 4:
-            raise ValueError("thresholds must be [Q][4]: ks, mean_rel, entropy_rel, frequency_diff per row")
+        _lib_with("ecdna_ssa_ctx_accept")
+        thr = _threshold_rows(thresholds)
         mask = timepoint_mask(timepoints)
         for name, v, bits in (("list_threshold", list_threshold, 32), ("list_capacity", list_capacity, 64),
                               ("source", source, 32), ("n_thresholds", thr.shape[0], 32)):
@@ -600,7 +463,7 @@ class Context:
                              timepoints=None, store: str = "keep"):
         """Enqueue the acceptance over thinning draws first_draw .. first_draw + n_draws - 1 on the stream of the last
         launch (ecdna_ssa_ctx_accept_draws); download_accept_draws returns its results. Arguments as accept_draws()."""
-        L = _lib_with("ecdna_ssa_ctx_accept_draws", "acceptance over repeated thinnings")
+        L = _lib_with("ecdna_ssa_ctx_accept_draws")
         a, _alive = self._accept_draws_block(targets, sample_cells, thresholds, n_draws, first_draw, timepoints, store)
         self._accept_draws_shape = None
         _check(L.ecdna_ssa_ctx_accept_draws(self.h, C.byref(a)), "ecdna_ssa_ctx_accept_draws")
@@ -611,12 +474,8 @@ class Context:
         None: a block without threshold rows, as select_draws takes it."""
         if store not in ("keep", "timepoints"):
             raise ValueError('store must be "keep" or "timepoints"')
-        tgt = np.ascontiguousarray(targets, dtype=np.uint64)
-        if tgt.ndim != 2 or tgt.shape[1] != self.params.hist_bins:
-            raise ValueError("targets must be [P][hist_bins]: one histogram of hist_bins entries per target")
-        thr = np.ascontiguousarray(thresholds if thresholds is not None else np.zeros((0, 4)), dtype=np.float64)
-        if thr.ndim != 2 or thr.shape[1] != 4:
-            raise ValueError("thresholds must be [Q][4]: ks, mean_rel, entropy_rel, frequency_diff per row")
+        tgt = _target_hists(targets, self.params.hist_bins)
+        thr = _threshold_rows(thresholds if thresholds is not None else np.zeros((0, 4)))
         for name, v in (("n_targets", tgt.shape[0]), ("n_thresholds", thr.shape[0]), ("n_draws", n_draws),
                         ("first_draw", first_draw)):
             _check_u32(name, v)
@@ -665,7 +524,7 @@ class Context:
         row — every slot, those `timepoints` leaves out of the verdict included — and .kept[slice] the whole kept
         samples times the number of passing draws (one slice on store "keep", T on "timepoints"). Synchronous; needs
         neither an earlier accept_draws nor a rescore and leaves their results as they are."""
-        L = _lib_with("ecdna_ssa_ctx_pool_draws", "pooling over thinning draws")
+        L = _lib_with("ecdna_ssa_ctx_pool_draws")
         a, _alive = self._accept_draws_block(targets, sample_cells, thresholds, n_draws, first_draw, timepoints, store)
         _check_u32("threshold", threshold)
         if int(threshold) >= int(a.n_thresholds):
@@ -683,7 +542,7 @@ class Context:
         (ranks >= 1), or those at `fractions` in (0, 1] of the population, of each of the four distances among the
         error-free replicates of `source` (an abi.ACCEPT_* constant), the maximum over `timepoints` (None: all) standing
         for a replicate. accept() with a finite value as the one threshold accepts exactly its counts_le replicates."""
-        _lib_with("ecdna_ssa_ctx_select", "ABC thresholds on the GPU")
+        _lib_with("ecdna_ssa_ctx_select")
         rk, fr = select_ranks(ranks, fractions)
         _check_u32("source", source)
         K = len(rk) if rk is not None else len(fr)
@@ -693,26 +552,16 @@ class Context:
             s.ranks = rk.ctypes.data_as(C.POINTER(C.c_uint64))
         else:
             s.fractions = fr.ctypes.data_as(C.POINTER(C.c_double))
-        population = C.c_uint64()
-        out_ranks = np.zeros(K, dtype=np.uint64)
-        values = np.zeros((4, K), dtype=np.float64)
-        counts_le = np.zeros((4, K), dtype=np.uint64)
-        _check(lib().ecdna_ssa_ctx_select(self.h, C.byref(s), C.byref(population), out_ranks.ctypes.data,
-                                          values.ctypes.data, counts_le.ctypes.data), "ecdna_ssa_ctx_select")
-        return SelectResult(int(population.value), out_ranks, values, counts_le)
+        return _select_result(K, "ecdna_ssa_ctx_select",
+                              lambda *out: lib().ecdna_ssa_ctx_select(self.h, C.byref(s), *out))
 
     def select_digits(self, source: int, pass_: int, prefixes, timepoints=None) -> np.ndarray:
         """One pass of the select on this context's replicates (ecdna_ssa_ctx_select_digits), the shard primitive:
         `prefixes` [4][K] u64 keys (shard.SelectWalk.prefixes), the result [4][K][256] u64: per distance and prefix, the
         population's keys that share the prefix's top 8 * pass_ bits, counted by their next 8 bits. Shards' arrays sum."""
-        _lib_with("ecdna_ssa_ctx_select_digits", "ABC thresholds on the GPU")
-        pre = np.ascontiguousarray(prefixes, dtype=np.uint64)
-        if pre.ndim != 2 or pre.shape[0] != 4 or not (1 <= pre.shape[1] <= abi.SELECT_MAX_RANKS):
-            raise ValueError(f"prefixes must be [4][K], K in 1 .. {abi.SELECT_MAX_RANKS}")
-        if not (0 <= int(pass_) < abi.SELECT_PASSES):
-            raise ValueError(f"pass_ = {pass_} must be in 0 .. {abi.SELECT_PASSES - 1}")
+        _lib_with("ecdna_ssa_ctx_select_digits")
+        pre, hist = _digit_arrays(pass_, prefixes)
         _check_u32("source", source)
-        hist = np.zeros((4, pre.shape[1], 256), dtype=np.uint64)
         _check(lib().ecdna_ssa_ctx_select_digits(self.h, int(source), timepoint_mask(timepoints), int(pass_),
                                                  pre.shape[1], pre.ctypes.data, hist.ctypes.data),
                "ecdna_ssa_ctx_select_digits")
@@ -726,40 +575,29 @@ class Context:
         the distance accept_draws scores on that draw. accept_draws() with a finite value as its one threshold has
         sums[0].sum() == counts_le. Synchronous; stores no record, needs no rescore and leaves the rescored records and
         the results of accept, accept_draws and select as they are."""
-        L = _lib_with("ecdna_ssa_ctx_select_draws", "ABC thresholds over thinning draws")
+        L = _lib_with("ecdna_ssa_ctx_select_draws")
         rk, fr = select_ranks(ranks, fractions)
         K = len(rk) if rk is not None else len(fr)
         a, _alive = self._accept_draws_block(targets, sample_cells, None, n_draws, first_draw, timepoints, store)
-        population = C.c_uint64()
-        out_ranks = np.zeros(K, dtype=np.uint64)
-        values = np.zeros((4, K), dtype=np.float64)
-        counts_le = np.zeros((4, K), dtype=np.uint64)
-        _check(L.ecdna_ssa_ctx_select_draws(self.h, C.byref(a), K, rk.ctypes.data if rk is not None else None,
-                                            fr.ctypes.data if fr is not None else None, C.byref(population),
-                                            out_ranks.ctypes.data, values.ctypes.data, counts_le.ctypes.data),
-               "ecdna_ssa_ctx_select_draws")
-        return SelectResult(int(population.value), out_ranks, values, counts_le)
+        return _select_result(K, "ecdna_ssa_ctx_select_draws", lambda *out: L.ecdna_ssa_ctx_select_draws(
+            self.h, C.byref(a), K, rk.ctypes.data if rk is not None else None,
+            fr.ctypes.data if fr is not None else None, *out))
 
     def select_draws_digits(self, targets, sample_cells, pass_: int, prefixes, n_draws: int = 64, first_draw: int = 0,
                             timepoints=None, store: str = "keep") -> np.ndarray:
         """One pass of select_draws on this context's replicates (ecdna_ssa_ctx_select_draws_digits), the shard
         primitive: select_digits() over the keys of every (replicate, draw). Pass 0 makes the keys; the later passes
         read them and must name the same block. Shards' arrays sum."""
-        L = _lib_with("ecdna_ssa_ctx_select_draws_digits", "ABC thresholds over thinning draws")
-        pre = np.ascontiguousarray(prefixes, dtype=np.uint64)
-        if pre.ndim != 2 or pre.shape[0] != 4 or not (1 <= pre.shape[1] <= abi.SELECT_MAX_RANKS):
-            raise ValueError(f"prefixes must be [4][K], K in 1 .. {abi.SELECT_MAX_RANKS}")
-        if not (0 <= int(pass_) < abi.SELECT_PASSES):
-            raise ValueError(f"pass_ = {pass_} must be in 0 .. {abi.SELECT_PASSES - 1}")
+        L = _lib_with("ecdna_ssa_ctx_select_draws_digits")
+        pre, hist = _digit_arrays(pass_, prefixes)
         a, _alive = self._accept_draws_block(targets, sample_cells, None, n_draws, first_draw, timepoints, store)
-        hist = np.zeros((4, pre.shape[1], 256), dtype=np.uint64)
         _check(L.ecdna_ssa_ctx_select_draws_digits(self.h, C.byref(a), int(pass_), pre.shape[1], pre.ctypes.data,
                                                    hist.ctypes.data), "ecdna_ssa_ctx_select_draws_digits")
         return hist
 
     def download_cohort(self) -> CohortResult:
         """The cohort records of the last launch (ecdna_ssa_ctx_download_cohort): stats and sample_stats [P][n]."""
-        _lib_with("ecdna_ssa_ctx_download_cohort", "a cohort of targets")
+        _lib_with("ecdna_ssa_ctx_download_cohort")
         if self.cohort is None:  # (the library refuses: ECDNA_E_STATE)
             _check(lib().ecdna_ssa_ctx_download_cohort(self.h, None, None), "ecdna_ssa_ctx_download_cohort")
             raise EngineError("ecdna_ssa_ctx_download_cohort: the context has no cohort block")
@@ -775,11 +613,11 @@ class Context:
     # axes `lead` (none, or T).
     @staticmethod
     def _keep_lib():
-        return _lib_with("ecdna_ssa_ctx_create_keep", "kept samples")
+        return _lib_with("ecdna_ssa_ctx_create_keep")
 
     @staticmethod
     def _keep_timepoints_lib():
-        return _lib_with("ecdna_ssa_ctx_create_keep_timepoints", "kept timepoint samples")
+        return _lib_with("ecdna_ssa_ctx_create_keep_timepoints")
 
     def _pool_accepted(self, get_lib, name: str, T: int, threshold: int) -> np.ndarray:
         _check_u32("threshold", threshold)
@@ -808,7 +646,7 @@ class Context:
 
     @staticmethod
     def _sized_lib():
-        return _lib_with("ecdna_ssa_ctx_rescore_sized", "sized rescoring")
+        return _lib_with("ecdna_ssa_ctx_rescore_sized")
 
     @staticmethod
     def _u32_list(name: str, values, count: int) -> np.ndarray:
@@ -826,9 +664,7 @@ class Context:
         """Enqueue the late scoring of the kept samples against `targets` [P][hist_bins] on the stream of the last
         launch (ecdna_ssa_ctx_rescore; with sample_cells or draws, ecdna_ssa_ctx_rescore_sized); download_rescored
         returns the records."""
-        tgt = np.ascontiguousarray(targets, dtype=np.uint64)
-        if tgt.ndim != 2 or tgt.shape[1] != self.params.hist_bins:
-            raise ValueError("targets must be [P][hist_bins]: one histogram of hist_bins entries per target")
+        tgt = _target_hists(targets, self.params.hist_bins)
         if not (0 <= tgt.shape[0] < (1 << 32)):
             raise ValueError(f"{tgt.shape[0]} targets do not fit the ABI's u32 field")
         self._rescore_targets = 0

@@ -220,25 +220,38 @@ class SelectWalk:
         return SelectResult(M, np.array(self.ranks, dtype=np.uint64), values, counts_le)
 
 
+def _sum_over_ranks(arr, group=None, device=None):
+    """The sum of a u64 numpy array over the ranks, as u64: one all-reduce of its int64 view (the counts stay far below
+    2^63) — integer sums, exact in any order. `device`: where the exchange buffer lives ("cuda" under RCCL, None = CPU
+    for gloo)."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    t = torch.from_numpy(np.ascontiguousarray(arr).view(np.int64))
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.cpu().numpy().view(np.uint64)
+
+
+def _select_walk(digits, ranks, fractions, group, device):
+    """The eight passes of a sharded select: digits(pass_, prefixes) counts this rank's keys, [4][K][256] u64, and one
+    all-reduce per pass joins the shards' arrays for the SelectWalk."""
+    K = len(ranks) if ranks is not None else len(fractions if fractions is not None else ())
+    walk = SelectWalk(K, ranks=ranks, fractions=fractions)
+    for p in range(SelectWalk.PASSES):
+        walk.feed(_sum_over_ranks(digits(p, walk.prefixes), group, device))
+    return walk.result()
+
+
 def select(ctx, source: int, ranks=None, fractions=None, timepoints=None, group=None, device=None):
     """Context.select over every rank's shard: the exact order statistics of the whole run's distances, the same
     engine.SelectResult on every rank. Per pass each rank counts its own replicates (Context.select_digits) and one
     all-reduce (int64, sum) of the [4][K][256] array joins them: integer sums, exact in any order. Nothing else is
     exchanged. `device`: where the exchange buffer lives ("cuda" under RCCL, None = CPU for gloo)."""
-    import numpy as np
-    import torch
-    import torch.distributed as dist
-
-    K = len(ranks) if ranks is not None else len(fractions if fractions is not None else ())
-    walk = SelectWalk(K, ranks=ranks, fractions=fractions)
-    for p in range(SelectWalk.PASSES):
-        hist = ctx.select_digits(source, p, walk.prefixes, timepoints)
-        t = torch.from_numpy(hist.view(np.int64))  # (counts stay far below 2^63)
-        if device is not None:
-            t = t.to(device)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-        walk.feed(t.cpu().numpy().view(np.uint64))
-    return walk.result()
+    return _select_walk(lambda p, prefixes: ctx.select_digits(source, p, prefixes, timepoints), ranks, fractions,
+                        group, device)
 
 
 def select_draws(ctx, targets, sample_cells, n_draws: int = 64, first_draw: int = 0, timepoints=None,
@@ -247,36 +260,16 @@ def select_draws(ctx, targets, sample_cells, n_draws: int = 64, first_draw: int 
     pairs (replicate, thinning draw), the same engine.SelectResult on every rank. It is select() with
     Context.select_draws_digits in the loop: pass 0 makes each shard's keys, and eight all-reduces (int64, sum) of the
     [4][K][256] arrays join the shards. `device` as for select()."""
-    import numpy as np
-    import torch
-    import torch.distributed as dist
-
-    K = len(ranks) if ranks is not None else len(fractions if fractions is not None else ())
-    walk = SelectWalk(K, ranks=ranks, fractions=fractions)
-    for p in range(SelectWalk.PASSES):
-        hist = ctx.select_draws_digits(targets, sample_cells, p, walk.prefixes, n_draws, first_draw, timepoints, store)
-        t = torch.from_numpy(hist.view(np.int64))  # (counts stay far below 2^63)
-        if device is not None:
-            t = t.to(device)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-        walk.feed(t.cpu().numpy().view(np.uint64))
-    return walk.result()
+    return _select_walk(lambda p, prefixes: ctx.select_draws_digits(targets, sample_cells, p, prefixes, n_draws,
+                                                                    first_draw, timepoints, store),
+                        ranks, fractions, group, device)
 
 
 def pool_accepted(ctx, threshold: int, group=None, device=None):
     """Context.pool_accepted over every rank's shard: the whole run's posterior predictive histogram
     [n_param_sets][hist_bins] u64, the same on every rank. Each rank pools its own accepted replicates' kept samples
     and one all-reduce (int64, sum) joins the arrays: integer sums, exact in any order. `device` as for select()."""
-    import numpy as np
-    import torch
-    import torch.distributed as dist
-
-    hist = ctx.pool_accepted(threshold)
-    t = torch.from_numpy(hist.view(np.int64))  # (counts stay far below 2^63)
-    if device is not None:
-        t = t.to(device)
-    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-    return t.cpu().numpy().view(np.uint64)
+    return _sum_over_ranks(ctx.pool_accepted(threshold), group, device)
 
 
 def accept_draws(ctx, targets, sample_cells, thresholds, n_draws: int = 64, first_draw: int = 0, timepoints=None,
@@ -284,16 +277,8 @@ def accept_draws(ctx, targets, sample_cells, thresholds, n_draws: int = 64, firs
     """Context.accept_draws over every rank's shard: the result's passes are the rank's own replicates', its sums
     [Q][n_param_sets] u64 the whole run's, the same on every rank. One all-reduce (int64, sum) joins the shards' arrays:
     integer sums, exact in any order. `device` as for select()."""
-    import numpy as np
-    import torch
-    import torch.distributed as dist
-
     res = ctx.accept_draws(targets, sample_cells, thresholds, n_draws, first_draw, timepoints, store)
-    t = torch.from_numpy(res.sums.view(np.int64))  # (sums stay far below 2^63)
-    if device is not None:
-        t = t.to(device)
-    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-    res.sums = t.cpu().numpy().view(np.uint64)
+    res.sums = _sum_over_ranks(res.sums, group, device)
     return res
 
 
@@ -303,17 +288,9 @@ def pool_draws(ctx, targets, sample_cells, thresholds, threshold: int = 0, n_dra
     [n_targets][n_param_sets][hist_bins] and kept [n_slices][n_param_sets][hist_bins] u64, the same on every rank. Each
     rank pools its own replicates and one all-reduce (int64, sum) per array joins them: integer sums, exact in any
     order. `device` as for select()."""
-    import numpy as np
-    import torch
-    import torch.distributed as dist
-
     res = ctx.pool_draws(targets, sample_cells, thresholds, threshold, n_draws, first_draw, timepoints, store)
-    for name in ("thinned", "kept"):
-        t = torch.from_numpy(getattr(res, name).view(np.int64))  # (counts stay far below 2^63)
-        if device is not None:
-            t = t.to(device)
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-        setattr(res, name, t.cpu().numpy().view(np.uint64))
+    res.thinned = _sum_over_ranks(res.thinned, group, device)
+    res.kept = _sum_over_ranks(res.kept, group, device)
     return res
 
 
@@ -322,13 +299,4 @@ def pool_accepted_timepoints(ctx, threshold: int, group=None, device=None):
     timepoint, [T][n_param_sets][hist_bins] u64, the same on every rank. Each rank pools its own accepted replicates'
     kept timepoint samples and one all-reduce (int64, sum) joins the arrays: integer sums, exact in any order. `device`
     as for select()."""
-    import numpy as np
-    import torch
-    import torch.distributed as dist
-
-    hist = np.ascontiguousarray(ctx.pool_accepted_timepoints(threshold))
-    t = torch.from_numpy(hist.view(np.int64))  # (counts stay far below 2^63)
-    if device is not None:
-        t = t.to(device)
-    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-    return t.cpu().numpy().view(np.uint64)
+    return _sum_over_ranks(ctx.pool_accepted_timepoints(threshold), group, device)

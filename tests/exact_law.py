@@ -717,3 +717,10 @@ def check_yule(res) -> Dict[str, float]:
     # one event more than the cells say would be an off-by-one of the stop test: the events are cells - 1
     ok = ok and (s["iters"].astype(np.int64) == cells - 1).all()
     return {"time_stop": 1.0 if ok else 0.0, "cells": yule_stop_pvalue(cells, YULE_T)}
+
+
+def assert_laws(ps, label):
+    worst = min(ps, key=ps.get)
+    print(f"LAW {label} | {worst} | {ps[worst]:.3g}")
+    bad = {k: v for k, v in ps.items() if not v > P_MIN}
+    assert not bad, f"{label}: {bad}"

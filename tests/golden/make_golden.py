@@ -82,7 +82,7 @@ def make_parity():
 def make_refdraws():
     """The compat oracle (the reference's draw structure) on every row-store parity case: the engine's
     ECDNA_FLAG_REFERENCE_DRAWS mode must reproduce it (tests/test_gpu_refdraws.py)."""
-    from test_gpu_refdraws import refdraws_cases
+    from support.gpu import refdraws_cases
 
     out = {}
     for name, spec in sorted(refdraws_cases().items()):

@@ -13,6 +13,8 @@ import math
 
 import numpy as np
 
+from accept_law import timepoints_of
+
 FIELDS = ("ks", "mean_rel", "entropy_rel", "frequency_diff")
 SIGN = np.uint64(0x8000000000000000)
 QUIET_NAN = np.uint64(0x7FF8000000000000)
@@ -41,14 +43,6 @@ def values_of(keys):
     """The numbers the keys stand for (f64)."""
     k = np.ascontiguousarray(keys, dtype=np.uint64)
     return np.where(k & SIGN != 0, k ^ SIGN, ~k).view(np.float64)
-
-
-def timepoints_of(timepoint_mask, T):
-    """The participating timepoints: the set bits of the mask, or all T when it is 0."""
-    if timepoint_mask == 0:
-        return list(range(T))
-    assert timepoint_mask >> T == 0, "timepoint_mask has bits at or above T"
-    return [t for t in range(T) if (timepoint_mask >> t) & 1]
 
 
 def population_keys(records, summaries, timepoint_mask=0):

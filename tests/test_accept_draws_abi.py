@@ -4,47 +4,29 @@ declares the block and the two calls, the library exports them, the ctypes mirro
 still 13 and the older blocks kept their sizes, the header states the mapping, and without a context the calls answer as
 ecdna_ssa_ctx_accept does."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
-import pytest
 
 from ecdna_evo_amd import abi
+from support.abi import HEADER, declared, header_text, layout, product_lib  # noqa: F401 (fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
 BINS = 9
 NEW_CALLS = ("ecdna_ssa_ctx_accept_draws", "ecdna_ssa_ctx_download_accept_draws")
 FIELDS = ["struct_size", "timepoints", "n_targets", "target_hists", "sample_cells", "first_draw", "n_draws",
           "n_thresholds", "thresholds", "timepoint_mask", "reserved"]
 
 
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
-
-
-def _declared(text, name):
-    m = re.search(r"int\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, f"include/ecdna_ssa.h does not declare {name}"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
-
-
 def test_header_declares_and_library_exports_the_calls(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert _declared(text, "ecdna_ssa_ctx_accept_draws") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_accept_draws_t* a"]
-    assert _declared(text, "ecdna_ssa_ctx_download_accept_draws") == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_accept_draws") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_accept_draws_t* a"]
+    assert declared("ecdna_ssa_ctx_download_accept_draws") == [
         "ecdna_ssa_ctx* c", "uint64_t* out_sums", "uint8_t* out_passes"]
     # the calls it stands beside did not change
-    assert _declared(text, "ecdna_ssa_ctx_accept") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_accept_t* a"]
-    assert _declared(text, "ecdna_ssa_ctx_rescore_sized") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_rescore_t* r"]
+    assert declared("ecdna_ssa_ctx_accept") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_accept_t* a"]
+    assert declared("ecdna_ssa_ctx_rescore_sized") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_rescore_t* r"]
     for name in NEW_CALLS:
         assert hasattr(product_lib, name) and name in engine.EXPORTS, name
     assert product_lib.ecdna_ssa_ctx_accept_draws.argtypes == [C.c_void_p, C.POINTER(abi.AcceptDraws)]
@@ -57,24 +39,11 @@ def test_header_declares_and_library_exports_the_calls(product_lib):
 def test_layout_matches_header(tmp_path):
     """sizeof and the field offsets from a compiled C probe against the ctypes mirror; the older blocks did not move."""
     assert [f for f, _ in abi.AcceptDraws._fields_] == FIELDS
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("{\\"accept_draws\\": %zu", sizeof(ecdna_ssa_accept_draws_t));']
-    for f in FIELDS:
-        lines.append(f'printf(", \\"accept_draws.{f}\\": %zu", offsetof(ecdna_ssa_accept_draws_t, {f}));')
-    lines += ['printf(", \\"accept\\": %zu", sizeof(ecdna_ssa_accept_t));',
-              'printf(", \\"threshold\\": %zu", sizeof(ecdna_accept_threshold_t));',
-              'printf(", \\"select\\": %zu", sizeof(ecdna_ssa_select_t));',
-              'printf(", \\"rescore\\": %zu", sizeof(ecdna_ssa_rescore_t));',
-              'printf(", \\"keep\\": %zu", sizeof(ecdna_ssa_keep_t));',
-              'printf(", \\"keep_timepoints\\": %zu", sizeof(ecdna_ssa_keep_timepoints_t));',
-              'printf(", \\"cohort\\": %zu", sizeof(ecdna_ssa_cohort_t));',
-              'printf(", \\"stats\\": %zu", sizeof(ecdna_rep_stats_t));',
-              'printf(", \\"params\\": %zu}\\n", sizeof(ecdna_ssa_params_t));', "return 0;}"]
-    src = tmp_path / "accept_draws_layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "accept_draws_layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = json.loads(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
+    got = layout(tmp_path, {"accept_draws": ("ecdna_ssa_accept_draws_t", FIELDS), "accept": "ecdna_ssa_accept_t",
+                            "threshold": "ecdna_accept_threshold_t", "select": "ecdna_ssa_select_t",
+                            "rescore": "ecdna_ssa_rescore_t", "keep": "ecdna_ssa_keep_t",
+                            "keep_timepoints": "ecdna_ssa_keep_timepoints_t", "cohort": "ecdna_ssa_cohort_t",
+                            "stats": "ecdna_rep_stats_t", "params": "ecdna_ssa_params_t"})
     assert got["accept_draws"] == C.sizeof(abi.AcceptDraws) == 72
     for f in FIELDS:
         assert got[f"accept_draws.{f}"] == getattr(abi.AcceptDraws, f).offset, f

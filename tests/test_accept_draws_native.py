@@ -4,37 +4,24 @@ LDS plan at its limits and the byte counts.
 
 tests/native/accept_draws_check.cpp is a stand-alone program, built for the host alone with the address and
 undefined-behaviour sanitizers (any report ends it with an error); it is never loaded into Python."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import native
+from support.native import _want_keep, _want_timepoints
+
 PASS_LDS_MAX = 65536  # kPassLdsMax
 
-pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc absent")
+pytestmark = native.needs_hipcc
 
 
 @pytest.fixture(scope="module")
 def check(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp("accept_draws_check")), "accept_draws_check")
-    subprocess.run(["hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "ecdna-evo_amd", "csrc"),
-                    os.path.join(REPO, "tests", "native", "accept_draws_check.cpp"), "-o", exe], check=True)
-    return exe
-
-
-def _run(exe, *args):
-    out = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and out.stderr == "", out.stderr[-4000:]  # (no sanitizer report)
-    return out.stdout.splitlines()
+    return native.build(tmp_path_factory, "accept_draws_check")
 
 
 def _plan(exe, keep, timepoints, mask, sizes):
     """(slices, slice mask, max m', [(first group, end group)] per slice, [(m1, [targets])] per group) as printed."""
-    lines = [ln.split() for ln in _run(exe, "plan", keep, int(timepoints), "%x" % mask, *sizes)]
+    lines = [ln.split() for ln in native.run(exe, "plan", keep, int(timepoints), "%x" % mask, *sizes)]
     head = lines[0]
     assert head[0::2] == ["slices", "mask", "groups", "max_mp"]
     n_slices, n_groups = int(head[1]), int(head[5])
@@ -42,26 +29,6 @@ def _plan(exe, keep, timepoints, mask, sizes):
     slices = [(int(ln[3]), int(ln[4])) for ln in lines[1:1 + n_slices]]
     groups = [(int(ln[1]), [int(t) for t in ln[3:]]) for ln in lines[1 + n_slices:]]
     return n_slices, int(head[3], 16), int(head[7]), slices, groups
-
-
-def _want_keep(keep, mask, sizes):
-    """The keep store restated: one slice; the participating targets by distinct m1 in order of first appearance."""
-    take = [p for p in range(len(sizes)) if mask == 0 or (mask >> p) & 1]
-    order = list(dict.fromkeys(sizes[p] for p in take))
-    groups = [(m, [p for p in take if sizes[p] == m]) for m in order]
-    return 1, 1, max(min(m, keep - m) for m in order), [(0, len(groups))], groups
-
-
-def _want_timepoints(keep, mask, sizes):
-    """The timepoint store restated: slice t takes part when the mask names it, with one group of target t."""
-    T = len(sizes)
-    full = mask if mask else (1 << T) - 1
-    take = [t for t in range(T) if (full >> t) & 1]
-    slices, at = [], 0
-    for t in range(T):
-        slices.append((at, at + (t in take)))
-        at += t in take
-    return T, full, max(min(sizes[t], keep - sizes[t]) for t in take), slices, [(sizes[t], [t]) for t in take]
 
 
 def test_the_keep_store_groups_the_participating_targets(check):
@@ -98,7 +65,7 @@ def test_the_timepoint_store_has_one_group_per_participating_slice(check):
 
 
 def test_lds_plan_stays_within_the_pass_limit(check):
-    lines = _run(check, "lds")
+    lines = native.run(check, "lds")
     assert lines[0] == "lds ok"
     w = lines[1].split()
     assert w[0] == "limits"
@@ -110,7 +77,7 @@ def test_lds_plan_stays_within_the_pass_limit(check):
 
 
 def test_byte_counts(check):
-    w = _run(check, "bytes")[0].split()
+    w = native.run(check, "bytes")[0].split()
     got = dict(zip(w[0::2], map(int, w[1::2])))
     n = 4194304
     # the C4 sweep: the call keeps n x Q bytes where the loop's 64 draws take 64 records of 64 bytes per replicate
@@ -120,4 +87,4 @@ def test_byte_counts(check):
 
 
 def test_every_validation_branch(check):
-    assert _run(check, "validate") == ["validate ok"]
+    assert native.run(check, "validate") == ["validate ok"]

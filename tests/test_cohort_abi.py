@@ -3,43 +3,25 @@ header declares the block, its two entry points and the two acceptance sources, 
 mirror has the header's layout, the version is still 13 and the older blocks kept their sizes, the header states the
 mapping, ecdna_ssa_ctx_create_cohort validates the block before any device is touched, and RunSpec builds it."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
+from support.abi import HEADER, PARAMS_SIZE_V13, declared, header_text, layout, product_lib  # noqa: F401 (fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
-PARAMS_SIZE_V13 = 184  # sizeof(ecdna_ssa_params_t) as ABI v13 introduced it (LP64)
 BINS = 9
-
-
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
-
-
-def _declared(text, name):
-    m = re.search(r"int\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, f"include/ecdna_ssa.h does not declare {name}"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_header_declares_and_library_exports_the_calls(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert _declared(text, "ecdna_ssa_ctx_create_cohort") == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_create_cohort") == [
         "const ecdna_ssa_params_t* p", "const ecdna_ssa_ext_t* ext", "const ecdna_ssa_passages_t* passages",
         "const ecdna_ssa_cohort_t* cohort", "ecdna_ssa_ctx** out"]
-    assert _declared(text, "ecdna_ssa_ctx_download_cohort") == [
+    assert declared("ecdna_ssa_ctx_download_cohort") == [
         "ecdna_ssa_ctx* c", "ecdna_rep_stats_t* out_stats", "ecdna_rep_stats_t* out_sample_stats"]
     for name in ("ecdna_ssa_ctx_create_cohort", "ecdna_ssa_ctx_download_cohort"):
         assert hasattr(product_lib, name) and name in engine.EXPORTS
@@ -51,7 +33,7 @@ def test_header_declares_and_library_exports_the_calls(product_lib):
 
 
 def test_the_two_sources_are_8_and_9():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    text = header_text()
     assert re.search(r"\bECDNA_ACCEPT_COHORT\s*=\s*8\s*,", text)
     assert re.search(r"\bECDNA_ACCEPT_COHORT_SAMPLES\s*=\s*9\b", text)
     assert re.search(r"\bECDNA_ACCEPT_PASSAGE_SAMPLES\s*=\s*5\s*,", text)  # the older ones did not move
@@ -83,26 +65,13 @@ def test_cohort_layout_matches_header(tmp_path):
     """sizeof and the field offsets from a compiled C probe against the ctypes mirror; the older blocks did not move."""
     fields = [f for f, _ in abi.Cohort._fields_]
     assert fields == ["struct_size", "n_targets", "target_hists", "sample_cells", "reserved"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("{\\"size\\": %zu", sizeof(ecdna_ssa_cohort_t));']
+    got = layout(tmp_path, {"cohort": ("ecdna_ssa_cohort_t", fields), "select": "ecdna_ssa_select_t",
+                            "accept": "ecdna_ssa_accept_t", "passages": "ecdna_ssa_passages_t", "ext": "ecdna_ssa_ext_t",
+                            "stats": "ecdna_rep_stats_t", "params": "ecdna_ssa_params_t"},
+                 values={"cohort_source": "ECDNA_ACCEPT_COHORT", "cohort_samples_source": "ECDNA_ACCEPT_COHORT_SAMPLES"})
+    assert got["cohort"] == C.sizeof(abi.Cohort) == 32
     for f in fields:
-        lines.append(f'printf(", \\"{f}\\": %zu", offsetof(ecdna_ssa_cohort_t, {f}));')
-    lines += ['printf(", \\"cohort_source\\": %d", (int)ECDNA_ACCEPT_COHORT);',
-              'printf(", \\"cohort_samples_source\\": %d", (int)ECDNA_ACCEPT_COHORT_SAMPLES);',
-              'printf(", \\"select\\": %zu", sizeof(ecdna_ssa_select_t));',
-              'printf(", \\"accept\\": %zu", sizeof(ecdna_ssa_accept_t));',
-              'printf(", \\"passages\\": %zu", sizeof(ecdna_ssa_passages_t));',
-              'printf(", \\"ext\\": %zu", sizeof(ecdna_ssa_ext_t));',
-              'printf(", \\"stats\\": %zu", sizeof(ecdna_rep_stats_t));',
-              'printf(", \\"params\\": %zu}\\n", sizeof(ecdna_ssa_params_t));', "return 0;}"]
-    src = tmp_path / "cohort_layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "cohort_layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = json.loads(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
-    assert got["size"] == C.sizeof(abi.Cohort) == 32
-    for f in fields:
-        assert got[f] == getattr(abi.Cohort, f).offset, f
+        assert got[f"cohort.{f}"] == getattr(abi.Cohort, f).offset, f
     assert (got["cohort_source"], got["cohort_samples_source"]) == (abi.ACCEPT_COHORT, abi.ACCEPT_COHORT_SAMPLES)
     assert got["select"] == C.sizeof(abi.Select) == 40 and got["accept"] == C.sizeof(abi.Accept) == 48
     assert got["passages"] == C.sizeof(abi.Passages) == 24 and got["ext"] == C.sizeof(abi.Ext) == 24

@@ -3,37 +3,23 @@ distinct sample size, the LDS plan of the cohort pass at its limits, and every b
 
 tests/native/cohort_check.cpp is a stand-alone program, built for the host alone with the address and
 undefined-behaviour sanitizers (any report ends it with an error); it is never loaded into Python."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import native
+
 PASS_LDS_MAX = 65536  # kPassLdsMax
 
-pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc absent")
+pytestmark = native.needs_hipcc
 
 
 @pytest.fixture(scope="module")
 def cohort_check(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp("cohort_check")), "cohort_check")
-    subprocess.run(["hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "ecdna-evo_amd", "csrc"),
-                    os.path.join(REPO, "tests", "native", "cohort_check.cpp"), "-o", exe], check=True)
-    return exe
-
-
-def _run(exe, *args):
-    out = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and out.stderr == "", out.stderr[-4000:]  # (no sanitizer report)
-    return out.stdout.splitlines()
+    return native.build(tmp_path_factory, "cohort_check")
 
 
 def _groups(exe, sizes):
     """[(m, [targets])] and the largest m, as the program printed them."""
-    lines = [ln.split() for ln in _run(exe, "groups", *sizes)]
+    lines = [ln.split() for ln in native.run(exe, "groups", *sizes)]
     assert lines[0][0] == "groups" and lines[0][2] == "max" and int(lines[0][1]) == len(lines) - 1
     return [(int(ln[1]), [int(t) for t in ln[3:]]) for ln in lines[1:]], int(lines[0][3])
 
@@ -63,7 +49,7 @@ def test_groups_are_the_distinct_sizes_in_order_of_first_appearance(cohort_check
 
 
 def test_lds_plan_stays_within_the_pass_limit(cohort_check):
-    lines = _run(cohort_check, "lds")
+    lines = native.run(cohort_check, "lds")
     assert lines[0] == "lds ok"
     w = lines[1].split()
     assert w[0] == "limits"
@@ -76,4 +62,4 @@ def test_lds_plan_stays_within_the_pass_limit(cohort_check):
 
 
 def test_every_validation_branch(cohort_check):
-    assert _run(cohort_check, "validate") == ["validate ok"]
+    assert native.run(cohort_check, "validate") == ["validate ok"]

@@ -61,13 +61,6 @@ def run_oracle(oracle_mod, spec, store, want_rows=True):
     return oracle_mod.run(spec, mode="compat" if store == "ref" else "philox", want_rows=want_rows)
 
 
-def assert_laws(ps, label):
-    worst = min(ps, key=ps.get)
-    print(f"LAW {label} | {worst} | {ps[worst]:.3g}")
-    bad = {k: v for k, v in ps.items() if not v > X.P_MIN}
-    assert not bad, f"{label}: {bad}"
-
-
 def scenario_run(oracle_mod, name, store):
     """Joint-state runs are kept for the power tests (row store only) and otherwise dropped."""
     key = (name, store)
@@ -145,13 +138,13 @@ def test_enumerator_rejects_a_scenario_beyond_its_budget(monkeypatch):
 @pytest.mark.parametrize("name", sorted(X.SCENARIOS))
 def test_oracle_joint_state_law(name, store, oracle_mod):
     law = X.enumerate_law(X.SCENARIOS[name])
-    assert_laws(X.check_sets([law], scenario_run(oracle_mod, name, store)), f"{name}/{store}")
+    X.assert_laws(X.check_sets([law], scenario_run(oracle_mod, name, store)), f"{name}/{store}")
 
 
 @pytest.mark.parametrize("store", STORES)
 def test_oracle_multi_set_law(store, oracle_mod):
     laws = [X.enumerate_law(sc) for sc in X.MULTI_SET]
-    assert_laws(X.check_sets(laws, run_oracle(oracle_mod, X.scenario_spec(X.MULTI_SET, store), store)),
+    X.assert_laws(X.check_sets(laws, run_oracle(oracle_mod, X.scenario_spec(X.MULTI_SET, store), store)),
                 f"multi_set/{store}")
 
 
@@ -160,7 +153,7 @@ def test_oracle_multi_set_law(store, oracle_mod):
 def test_oracle_one_event_channel_and_time(store, f32, oracle_mod):
     for i in range(len(X.CHANNEL_POPS)):
         r = run_oracle(oracle_mod, X.channel_spec(i, store, f32), store, want_rows=False)
-        assert_laws(X.check_channel(r, i), f"channel{i}/{store}/f32={int(f32)}")
+        X.assert_laws(X.check_channel(r, i), f"channel{i}/{store}/f32={int(f32)}")
 
 
 @pytest.mark.parametrize("store", STORES)
@@ -170,7 +163,7 @@ def test_oracle_one_event_split(k, store, oracle_mod):
     r = run_oracle(oracle_mod, X.split_spec(k, store), store, want_rows=X.split_needs_rows(k, store))
     if store == "rows":
         _RUNS[("split", k)] = r
-    assert_laws(X.check_split(r, k, ordered_rows=ordered), f"split{k}/{store}")
+    X.assert_laws(X.check_split(r, k, ordered_rows=ordered), f"split{k}/{store}")
 
 
 @pytest.mark.parametrize("store", STORES)
@@ -178,7 +171,7 @@ def test_oracle_one_event_split(k, store, oracle_mod):
 def test_oracle_one_event_split_no_uneven(k, store, oracle_mod):
     ordered = store in ("rows", "ref")
     r = run_oracle(oracle_mod, X.split_spec(k, store, no_uneven=True), store, want_rows=ordered)
-    assert_laws(X.check_split(r, k, no_uneven=True, ordered_rows=ordered), f"split_no_uneven{k}/{store}")
+    X.assert_laws(X.check_split(r, k, no_uneven=True, ordered_rows=ordered), f"split_no_uneven{k}/{store}")
 
 
 @pytest.mark.parametrize("store", ["rows", "bins32", "bins64", "ref"])
@@ -186,7 +179,7 @@ def test_oracle_one_event_pick(store, oracle_mod):
     counts = [X.picked_counts(run_oracle(oracle_mod, spec, store)) for spec in X.pick_specs(store)]
     if store == "rows":
         _RUNS[("pick",)] = counts
-    assert_laws(X.check_pick(counts), f"pick/{store}")
+    X.assert_laws(X.check_pick(counts), f"pick/{store}")
 
 
 @pytest.mark.parametrize("f32", [False, True])
@@ -194,7 +187,7 @@ def test_oracle_one_event_pick(store, oracle_mod):
 def test_oracle_yule_time_stop(store, f32, oracle_mod):
     """Confirms the closed form's off-by-one (final cells = N(t) + 1) on every draw path before the GPU relies on it."""
     r = run_oracle(oracle_mod, X.yule_spec(store, f32), store, want_rows=False)
-    assert_laws(X.check_yule(r), f"yule/{store}/f32={int(f32)}")
+    X.assert_laws(X.check_yule(r), f"yule/{store}/f32={int(f32)}")
 
 
 # ------------------------------------------------------------------------------------------------ power self-tests

@@ -6,23 +6,15 @@ order, and the result must equal one single-process run of all ids byte for byte
 - torchrun with two ranks sharing cuda:0 over gloo (RCCL refuses two ranks on one device): the
   reordering of real interleaved shards."""
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
+from support.gpu import _free_port
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 @pytest.mark.gpu

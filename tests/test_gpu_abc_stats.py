@@ -5,17 +5,9 @@ import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
+from support.subsample_specs import _target
 
 RTOL, ATOL = 1e-12, 1e-14
-
-
-def _target(bins):
-    rng = np.random.default_rng(5)
-    t = np.zeros(bins, np.uint64)
-    t[0] = 400
-    t[1:40] = rng.integers(0, 90, 39)
-    t[bins - 1] = 3
-    return t
 
 
 @pytest.mark.gpu

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
-from test_gpu_parity import _compare
+from support.gpu import _compare
 
 H = abi.FLAG_EVENT_HASH
 BD_RATES = (1.0, 1.5, 0.3, 0.3)

@@ -11,23 +11,15 @@ Both reduced histograms must equal a single-process run of the same global ids b
 contract's fields."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 import pytest
+from support.gpu import _free_port
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N_TOTAL = 1 << 15
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _torchrun(nproc, reps_per_gpu, dump, extra_env, extra_args=()):

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
-from test_host import subsample_py
+from support.host_law import subsample_py
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(REPO, "ecdna-evo_amd", "bin", "ecdna-dynamics")

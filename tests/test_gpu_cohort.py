@@ -15,32 +15,14 @@ import pytest
 import abc_stats
 import subsample_law as sl
 from ecdna_evo_amd import abi
-from test_gpu_accept import _thresholds
-from test_gpu_subsample_stats import ATOL, BINS, FLOATS, RTOL, STORES, _abc_spec, _flags
+from support.cohort_specs import P, SAMPLE_CELLS, _targets
+from support.gpu import _flags, _launched, _same_accept, _same_select, _thresholds
+from support.subsample_specs import ATOL, BINS, FLOATS, RTOL, STORES, _abc_spec
 
 INF = np.inf
-# a shared size (64 twice), m = 1, the complement (1500 of up to 2,000), the whole population (4096), a 64-draw batch edge
-SAMPLE_CELLS = (64, 1500, 1, 64, 4096, 65)
-P = len(SAMPLE_CELLS)
 OWN_M = 200  # the cohort run's own params.subsample_cells: it keeps its meaning beside the block
 _PLAIN = {}
 _COHORT = {}
-
-
-def _targets(bins=BINS):
-    """Six distinct histograms: four random ones, one with mass only in bin 0, one only in the overflow bin."""
-    rng = np.random.default_rng(41)
-    t = np.zeros((P, bins), dtype=np.uint64)
-    for p in range(P):
-        t[p, 0] = rng.integers(50, 600)
-        t[p, 1:20 + 7 * p] = rng.integers(0, 90, 19 + 7 * p)
-        t[p, bins - 1] = p
-    t[2] = 0
-    t[2, 0] = 17
-    t[4] = 0
-    t[4, bins - 1] = 5
-    assert len({row.tobytes() for row in t}) == P
-    return t
 
 
 def _cohort_spec(store, kmax, sample_cells=SAMPLE_CELLS, block=True, **kw):
@@ -69,13 +51,6 @@ def _cohort(engine_mod, store, kmax):
     if key not in _COHORT:
         _COHORT[key] = engine_mod.run(_cohort_spec(store, kmax), want_rows=True)
     return _COHORT[key]
-
-
-def _launched(engine_mod, spec):
-    ctx = engine_mod.Context(spec)
-    ctx.launch()
-    ctx.sync()
-    return ctx
 
 
 @pytest.mark.gpu
@@ -148,20 +123,6 @@ def test_placement_independence(engine_mod, store, kmax, monkeypatch):
         chunked = ctx.download().cohort
     assert chunked.stats.tobytes() == whole.stats.tobytes()
     assert chunked.sample_stats.tobytes() == whole.sample_stats.tobytes()
-
-
-def _same_accept(got, want, tag):
-    np.testing.assert_array_equal(got.counts, want.counts, err_msg=tag)
-    np.testing.assert_array_equal(got.mask, want.mask, err_msg=tag)
-    assert got.n_accepted == want.n_accepted, tag
-    np.testing.assert_array_equal(got.ids, want.ids, err_msg=tag)
-
-
-def _same_select(got, want, tag):
-    assert got.population == want.population, tag
-    np.testing.assert_array_equal(got.ranks, want.ranks, err_msg=tag)
-    np.testing.assert_array_equal(got.values.view(np.uint64), want.values.view(np.uint64), err_msg=tag)
-    np.testing.assert_array_equal(got.counts_le, want.counts_le, err_msg=tag)
 
 
 @pytest.mark.gpu

@@ -108,14 +108,7 @@ def check_once(laws, res, label):
     ps = _MEMO.get(key)
     if ps is None or (res.rows is not None and not any(k.endswith("omnibus") for k in ps)):
         ps = _MEMO[key] = X.check_sets(laws, res)
-    assert_laws(ps, label)
-
-
-def assert_laws(ps, label):
-    worst = min(ps, key=ps.get)
-    print(f"LAW {label} | {worst} | {ps[worst]:.3g}")
-    bad = {k: v for k, v in ps.items() if not v > X.P_MIN}
-    assert not bad, f"{label}: {bad}"
+    X.assert_laws(ps, label)
 
 
 @pytest.mark.gpu
@@ -151,7 +144,7 @@ def test_gpu_one_event_channel_and_time(variant, f32, engine_mod, monkeypatch):
     for i in range(len(X.CHANNEL_POPS)):
         res = run_variant(engine_mod, monkeypatch, lambda store, **kw: X.channel_spec(i, store, f32, **kw),
                           replace(var, rows=False))
-        assert_laws(X.check_channel(res, i), f"channel{i}/{variant}/f32={int(f32)}")
+        X.assert_laws(X.check_channel(res, i), f"channel{i}/{variant}/f32={int(f32)}")
 
 
 @pytest.mark.gpu
@@ -163,7 +156,7 @@ def test_gpu_one_event_split(k, variant, engine_mod, monkeypatch):
     unfolded (k1 is the first daughter of the final row) in the row store and the reference-draws stepper."""
     var = replace(VARIANTS[variant], rows=X.split_needs_rows(k, VARIANTS[variant].store))
     res = run_variant(engine_mod, monkeypatch, lambda store, **kw: X.split_spec(k, store, **kw), var)
-    assert_laws(X.check_split(res, k, ordered_rows=var.store in ("rows", "ref")), f"split{k}/{variant}")
+    X.assert_laws(X.check_split(res, k, ordered_rows=var.store in ("rows", "ref")), f"split{k}/{variant}")
 
 
 @pytest.mark.gpu
@@ -173,7 +166,7 @@ def test_gpu_one_event_split_no_uneven(k, variant, engine_mod, monkeypatch):
     """The no-uneven rule at k = 1, 2, 3, where redraws dominate (a draw is rejected with probability 2^(1-2k))."""
     var = replace(VARIANTS[variant], rows=X.split_needs_rows(k, VARIANTS[variant].store))
     res = run_variant(engine_mod, monkeypatch, lambda store, **kw: X.split_spec(k, store, no_uneven=True, **kw), var)
-    assert_laws(X.check_split(res, k, no_uneven=True, ordered_rows=var.store in ("rows", "ref")),
+    X.assert_laws(X.check_split(res, k, no_uneven=True, ordered_rows=var.store in ("rows", "ref")),
                 f"split_no_uneven{k}/{variant}")
 
 
@@ -185,7 +178,7 @@ def test_gpu_one_event_pick(variant, engine_mod, monkeypatch):
     var = VARIANTS[variant]
     counts = [X.picked_counts(engine_mod.run(spec, want_rows=True))
               for spec in X.pick_specs(var.store, flags=var.flags)]
-    assert_laws(X.check_pick(counts), f"pick/{variant}")
+    X.assert_laws(X.check_pick(counts), f"pick/{variant}")
 
 
 @pytest.mark.gpu
@@ -197,7 +190,7 @@ def test_gpu_yule_time_stop(variant, f32, engine_mod, monkeypatch):
     var = VARIANTS[variant]
     res = run_variant(engine_mod, monkeypatch, lambda store, **kw: X.yule_spec(store, f32, **kw),
                       replace(var, rows=False))
-    assert_laws(X.check_yule(res), f"yule/{variant}/f32={int(f32)}")
+    X.assert_laws(X.check_yule(res), f"yule/{variant}/f32={int(f32)}")
 
 
 @pytest.mark.gpu

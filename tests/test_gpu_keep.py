@@ -8,8 +8,6 @@ tests/test_gpu_subsample_stats.py pin to the restatements) as bytes; accept and 
 tests/accept_law.py and tests/select_law.py on the downloaded records; the pooled histogram with keep_law.pooled of the
 downloaded kept samples and mask. The spec is that of tests/test_gpu_subsample_stats.py (birth-death, two sets of 300
 replicates to 2,000 cells, a 300-copy cell, 257 bins)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
@@ -17,12 +15,12 @@ import accept_law as al
 import keep_law as kl
 import select_law as slw
 from ecdna_evo_amd import abi
-from test_gpu_accept import ALL_INF_ROW, _thresholds
-from test_gpu_cohort import _same_accept, _same_select, _targets
-from test_gpu_subsample_stats import BINS, STORES, _abc_spec, _flags
+from support.cohort_specs import _targets
+from support.gpu import ALL_INF_ROW, _canon, _flags, _launched, _same_accept, _same_select, _source_codes, _thresholds
+from support.subsample_specs import BINS, STORES, _abc_spec
 
 INF = np.inf
-P = 6  # test_gpu_cohort._targets()
+P = 6  # support.cohort_specs._targets()
 OWN_M = 200  # the run's own params.subsample_cells: it keeps its meaning beside the block
 SEED = 4  # _abc_spec's
 TWO_STORES = [("rows", 0), ("bins", 64)]
@@ -43,13 +41,6 @@ def _keep_spec(store, kmax, m, cohort_m=None, **kw):
     return spec
 
 
-def _launched(engine_mod, spec):
-    ctx = engine_mod.Context(spec)
-    ctx.launch()
-    ctx.sync()
-    return ctx
-
-
 def _plain(engine_mod, store, kmax, p, m):
     """The plain run against target p with subsample_cells = m: one per key, shared and left unchanged."""
     key = (store, kmax, p, m)
@@ -58,15 +49,6 @@ def _plain(engine_mod, store, kmax, p, m):
         spec.stats_target = _targets()[p]
         _PLAIN[key] = engine_mod.run(spec)
     return _PLAIN[key]
-
-
-def _canon(headers, cells):
-    """Headers and cell prefixes as bytes: entries past nplus are unspecified and set to zero here."""
-    c = cells.copy()
-    guard = headers["nplus"] == kl.GUARD
-    nplus = np.where(guard, 0, headers["nplus"]).astype(np.int64)
-    c[np.arange(c.shape[1])[None, :] >= nplus[:, None]] = 0
-    return headers.tobytes() + c.tobytes()
 
 
 def _hard_cases_occur(summaries):
@@ -339,18 +321,6 @@ def _raw_calls(L, h, n, m):
     return (L.ecdna_ssa_ctx_rescore(h, 1, hists.ctypes.data), L.ecdna_ssa_ctx_download_rescored(h, rec.ctypes.data),
             L.ecdna_ssa_ctx_pool_accepted(h, 0, pool.ctypes.data),
             L.ecdna_ssa_ctx_download_kept(h, n, None, kh.ctypes.data, kc.ctypes.data))
-
-
-def _source_codes(L, h, source):
-    thr = np.asarray([[INF] * 4])
-    a = abi.Accept(struct_size=C.sizeof(abi.Accept), source=source, n_thresholds=1)
-    a.thresholds = thr.ctypes.data_as(C.POINTER(abi.AcceptThreshold))
-    rk = (C.c_uint64 * 1)(1)
-    s = abi.Select(struct_size=C.sizeof(abi.Select), source=source, n_ranks=1)
-    s.ranks = C.cast(rk, C.POINTER(C.c_uint64))
-    pre, hist = np.zeros((4, 1), dtype=np.uint64), np.zeros((4, 1, 256), dtype=np.uint64)
-    return (L.ecdna_ssa_ctx_accept(h, C.byref(a)), L.ecdna_ssa_ctx_select(h, C.byref(s), None, None, None, None),
-            L.ecdna_ssa_ctx_select_digits(h, source, 0, 0, 1, pre.ctypes.data, hist.ctypes.data))
 
 
 @pytest.mark.gpu

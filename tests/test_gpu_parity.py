@@ -9,34 +9,12 @@ import pytest
 
 from cases import bin_cases, cases
 from ecdna_evo_amd import abi
+from support.gpu import _compare
 
 H = abi.FLAG_EVENT_HASH
 
 CASES = cases()
 BIN_CASES = bin_cases()
-
-
-def _compare(gpu, cpu, name):
-    gs, cs = gpu.summaries, cpu.summaries
-    for f in gs.dtype.names:
-        if f == "time":
-            np.testing.assert_array_equal(gs[f].view(np.uint64), cs[f].view(np.uint64), err_msg=f"{name}: {f}")
-        else:
-            np.testing.assert_array_equal(gs[f], cs[f], err_msg=f"{name}: {f}")
-    for i in range(len(gs)):
-        np.testing.assert_array_equal(gpu.row(i), cpu.row(i), err_msg=f"{name}: row {i}")
-    np.testing.assert_array_equal(gpu.hist, cpu.hist, err_msg=f"{name}: hist")
-    for f in gpu.totals.dtype.names:
-        np.testing.assert_array_equal(gpu.totals[f], cpu.totals[f], err_msg=f"{name}: totals.{f}")
-    if cpu.snapshots is not None:
-        for f in ("nminus", "nplus", "taken"):
-            np.testing.assert_array_equal(gpu.snapshots[f], cpu.snapshots[f], err_msg=f"{name}: snapshots.{f}")
-        np.testing.assert_array_equal(gpu.snapshots["time"].view(np.uint64), cpu.snapshots["time"].view(np.uint64))
-        if cpu.snapshot_rows is not None:
-            for i in range(len(gs)):
-                for s in range(cpu.snapshots.shape[1]):
-                    np.testing.assert_array_equal(gpu.snapshot_row(i, s), cpu.snapshot_row(i, s),
-                                                  err_msg=f"{name}: snapshot row {i}/{s}")
 
 
 @pytest.mark.gpu

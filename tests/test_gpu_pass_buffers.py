@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
-from test_gpu_select_draws import KEEP, N, _launched, _spec, _targets
+from support.draws_specs import KEEP, N, _spec, _targets
+from support.gpu import _launched
 
 INF = np.inf
 BINS = 9

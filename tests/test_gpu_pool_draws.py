@@ -16,8 +16,9 @@ import keep_law as kl
 import pool_draws_law as pdl
 import thin_law as tl
 from ecdna_evo_amd import abi
-from test_gpu_accept_draws import (FRACTIONS, INF, KEEP, N, PER_SET, SEED, SETS, SIZES, TWO_STORES, _block,
-                                   _gap_thresholds, _launched, _nk, _rows, _spec, _targets)
+from support.draws_specs import (FRACTIONS, INF, KEEP, N, PER_SET, SEED, SETS, SIZES, TWO_STORES, _block,
+                                 _gap_thresholds, _nk, _rows, _spec, _targets)
+from support.gpu import _flags, _launched
 
 
 def _sets(ids, per_set=PER_SET):
@@ -268,7 +269,6 @@ def test_passage_timepoints(engine_mod, store, kmax):
 
 def _limit_case(store, kmax, case):
     """(spec, bins, m1, seed, per_set, n_sets) of eight replicates at a limit of the LDS plan."""
-    from test_gpu_accept_draws import _flags
 
     if case == "largest":  # pure birth to 8,200 cells: every kept sample is full
         spec = abi.RunSpec(seed=3, process=abi.PURE_BIRTH, n_replicates=8, max_cells=8200, hist_bins=2048,

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
-from test_gpu_parity import _compare
+from support.gpu import _compare
 
 
 def random_spec(i):

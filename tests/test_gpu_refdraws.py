@@ -10,22 +10,16 @@ histograms, totals and snapshots must be identical. The oracle's compat mode is 
 reconstructed from the pinned crates; its outputs are also committed
 (tests/golden/refdraws_cases.npz) and the engine must reproduce them without the oracle.
 """
-import dataclasses
 import os
 
 import numpy as np
 import pytest
 
-from cases import cases
 from ecdna_evo_amd import abi
-from test_gpu_parity import _compare
+from support.gpu import _compare, refdraws_cases
 
 R = abi.FLAG_REFERENCE_DRAWS
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def refdraws_cases():
-    return {name: dataclasses.replace(spec, flags=spec.flags | R, _keep=[]) for name, spec in cases().items()}
 
 
 REF_CASES = refdraws_cases()

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
-from test_gpu_parity import _compare
+from support.gpu import _compare
 
 H = abi.FLAG_EVENT_HASH
 B = abi.FLAG_BIN_STORE

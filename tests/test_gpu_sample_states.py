@@ -20,14 +20,13 @@ import pytest
 
 import subsample_law as sl
 from ecdna_evo_amd import abi
+from support.state_specs import E2E_BINS, RID0, RID_STRIDE, SEED, _e2e_spec, _target
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(REPO, "ecdna-evo_amd", "bin", "sample_state_check")
 MAGIC = 0x4B43485353
 RTOL, ATOL = 1e-12, 1e-14
 FLOATS = ("mean", "entropy", "frequency", "ks", "mean_rel", "entropy_rel", "frequency_diff")
-SEED = 2027
-RID0, RID_STRIDE = 2**40 + 5, 3
 RPS = RID0 + 4 * RID_STRIDE  # populations 0..3 fall into parameter set 0, the others into set 1
 N_SETS = 2
 SUBSAMPLE, PASSAGE, PASSAGE_LAST, KEEP = 0, 1, 2, 3
@@ -37,15 +36,6 @@ P31 = 2**31
 
 def rid(q):
     return RID0 + q * RID_STRIDE
-
-
-def _target(bins):
-    rng = np.random.default_rng(5)
-    t = np.zeros(bins, np.uint64)
-    t[0] = 400
-    t[1:30] = rng.integers(0, 90, 29)
-    t[bins - 1] = 3
-    return t
 
 
 class Pop:
@@ -455,19 +445,7 @@ def test_small_anchors_and_the_sort_edges(results):
 
 # --- end to end at large N through the C ABI -------------------------------------------------------------------------
 
-E2E_BINS = 33
 E2E_INIT = {0: 3 * 2**30 - 10**6, 1: 600_000, 3: 400_000}
-
-
-def _e2e_spec(store, init, **kw):
-    """64 replicates under ids with a high word and a stride, the sample, the keep block and a cohort of two targets
-    with sample sizes (200, 4096)."""
-    t = _target(E2E_BINS)
-    flags = abi.FLAG_REP_STATS | (abi.FLAG_BIN_STORE if store == "bins" else 0)
-    return abi.RunSpec(seed=SEED, process=abi.BIRTH_DEATH, rates=((1.0, 1.4, 0.3, 0.3),), n_replicates=64,
-                       first_replicate=RID0, replicate_stride=RID_STRIDE, hist_bins=E2E_BINS, init=init, flags=flags,
-                       bin_kmax=64 if store == "bins" else 0, stats_target=t, subsample_cells=4096, keep_cells=4096,
-                       cohort_targets=np.stack([t[::-1].copy(), t]), cohort_sample_cells=(200, 4096), **kw)
 
 
 def _e2e_run(engine_mod, oracle_mod, spec):

@@ -4,8 +4,8 @@ DESIGN.md §5 and §11).
 Every comparison is exact: the population, the ranks, the values (as f64 bit patterns) and counts_le must equal the
 numpy restatement (tests/select_law.py) applied to the same context's downloaded records, and ecdna_ssa_ctx_accept with
 a selected value as its one threshold must accept exactly counts_le replicates — and fewer than the rank with the next
-smaller double. The shapes are those of tests/test_gpu_accept.py (its spec builders are copied here): 3,000 or 192
-replicates grown to 300 cells.
+smaller double. The shapes are those of tests/test_gpu_accept.py (both take their spec builders from
+tests/support/accept_specs.py): 3,000 or 192 replicates grown to 300 cells.
 
 Each case first asserts its preconditions on the restatement: the population has at least two replicates and at least
 two of the selected ks values differ, so no case is trivial; the passage case also selects a rank whose counts_le exceeds
@@ -28,83 +28,10 @@ import pytest
 
 import select_law as sl
 from ecdna_evo_amd import abi, shard
+from support.accept_specs import _final_spec, _passage_spec, _small_spec, _snapshot_spec, _source
+from support.gpu import _bytes_of, _run
 
 INF = np.inf
-BINS = 65
-C3 = (1.0, 1.5, 0.3, 0.3)
-BD_RATES = (C3, (1.0, 1.2, 0.2, 0.4))
-DYING = ((1.0, 1.0, 1.1, 1.1), (0.8, 1.0, 1.0, 1.3))  # tests/test_gpu_passages.py: d > b, extinctions
-
-
-def _targets(rows, bins=BINS):
-    rng = np.random.default_rng(23)
-    t = rng.integers(0, 60, (rows, bins)).astype(np.uint64)
-    t[:, 0] += 100
-    t[:, 40:] = 0
-    t[:, bins - 1] = 2
-    return t
-
-
-def _flags(store):
-    return abi.FLAG_REP_STATS | abi.FLAG_EVENT_HASH | (abi.FLAG_BIN_STORE if store == "bins" else 0)
-
-
-def _final_spec(store="rows", **kw):
-    """Birth-death replicates scored at the end of the run and on a 40-cell sample; three sets, the middle one with an
-    empty initial distribution (all its replicates end with ECDNA_REP_ERR_EMPTY)."""
-    d = dict(seed=7, process=abi.BIRTH_DEATH, segregation=abi.SEG_BINOMIAL, rates=BD_RATES + (C3,), reps_per_set=1000,
-             n_replicates=3000, max_cells=300, hist_bins=BINS, flags=_flags(store), bin_kmax=32,
-             init_per_set=[{1: 1}, {}, {0: 1, 2: 2}], stats_target=_targets(1)[0], subsample_cells=40)
-    d.update(kw)
-    return abi.RunSpec(**d)
-
-
-def _small_spec(n, store="rows", **kw):
-    """One or two sets of error-free and extinct replicates, no per-set initial distributions."""
-    d = dict(seed=9, process=abi.BIRTH_DEATH, segregation=abi.SEG_BINOMIAL, rates=BD_RATES, reps_per_set=max(1, (n + 1) // 2),
-             n_replicates=n, max_cells=300, hist_bins=BINS, flags=_flags(store), bin_kmax=32, init={0: 1, 1: 2},
-             stats_target=_targets(1)[0], subsample_cells=40)
-    d.update(kw)
-    return abi.RunSpec(**d)
-
-
-def _snapshot_spec(**kw):
-    d = dict(seed=4, process=abi.BIRTH_DEATH, rates=((1.0, 1.4, 0.3, 0.3), (1.0, 2.0, 0.5, 0.2)), reps_per_set=96,
-             n_replicates=192, max_cells=300, hist_bins=BINS, init={1: 3, 70: 1}, snapshots=(8, 60, 200),
-             flags=_flags("bins"), bin_kmax=32, snapshot_stats=True, snapshot_targets=_targets(3),
-             snapshot_subsample_cells=40)
-    d.update(kw)
-    return abi.RunSpec(**d)
-
-
-def _passage_spec(**kw):
-    d = dict(seed=11, process=abi.BIRTH_DEATH, segregation=abi.SEG_BINOMIAL, rates=DYING, reps_per_set=96,
-             n_replicates=192, max_cells=300, hist_bins=BINS, cell_cap=4096, flags=_flags("rows"), init={0: 10, 1: 10},
-             n_passages=3, passage_cells=40, passage_targets=_targets(3))
-    d.update(kw)
-    return abi.RunSpec(**d)
-
-
-def _source(res, source):
-    """(records [n][T], summaries [n] or [n][T]) of a source, from the context's ordinary downloads."""
-    if source == abi.ACCEPT_FINAL:
-        return res.stats[:, None], res.summaries
-    if source == abi.ACCEPT_SAMPLE:
-        return res.sample_stats[:, None], res.summaries
-    if source == abi.ACCEPT_SNAPSHOTS:
-        return res.snapshot_stats, res.summaries
-    if source == abi.ACCEPT_SNAPSHOT_SAMPLES:
-        return res.snapshot_sample_stats, res.summaries
-    ps = res.passages
-    stats = ps.stats if source == abi.ACCEPT_PASSAGES else ps.sample_stats
-    return np.ascontiguousarray(stats.T), np.ascontiguousarray(ps.summaries.T)
-
-
-def _run(engine_mod, spec):
-    ctx = engine_mod.Context(spec)
-    ctx.launch()
-    ctx.sync()
-    return ctx, ctx.download()
 
 
 def _tmask(timepoints):
@@ -262,8 +189,6 @@ def test_passage_sources(engine_mod, source, timepoints):
 
 
 # ----------------------------------------------------------------------------------------------------- chunks, shards
-def _bytes_of(r):
-    return (r.population, r.ranks.tobytes(), r.values.tobytes(), r.counts_le.tobytes())
 
 
 @pytest.mark.gpu

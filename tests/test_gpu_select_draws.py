@@ -13,48 +13,10 @@ import pytest
 
 import select_draws_law as sdl
 from ecdna_evo_amd import abi, shard
+from support.draws_specs import FRACTIONS, KEEP, N, PER_SET, SIZES, TWO_STORES, _nk, _spec, _targets
+from support.gpu import _bytes_of, _launched
 
 INF = np.inf
-TWO_STORES = [("rows", 0), ("bins", 64)]
-SEED = 31
-KEEP = 199
-N, SETS, PER_SET = 258, 3, 86  # set and workgroup boundaries fall inside waves; 258 x 64 and 258 x 3 are no multiples of 256
-RATES = ((1.0, 1.3, 0.4, 0.4), (1.0, 1.5, 0.4, 0.3), (1.1, 1.2, 0.5, 0.4))
-SIZES = (90, 130, 90)  # picks over two batches, a complement, and a shared sample
-FRACTIONS = (0.02, 0.1, 0.25, 0.4, 0.55, 0.7, 0.85, 1.0)
-
-
-def _flags(store):
-    return abi.FLAG_REP_STATS | abi.FLAG_EVENT_HASH | (abi.FLAG_BIN_STORE if store == "bins" else 0)
-
-
-def _targets(bins, n=3):
-    rng = np.random.default_rng(23)
-    t = rng.integers(0, 70, (n, bins)).astype(np.uint64)
-    t[:, 0] += 40
-    t[:, bins - 1] = np.arange(n) % 4
-    return t
-
-
-def _spec(store, kmax, bins, **kw):
-    """258 birth-death replicates in three parameter sets from three cells to 600 cells or time 6: some go extinct, some
-    end small, most end above the kept sample's size."""
-    base = dict(seed=SEED, process=abi.BIRTH_DEATH, rates=RATES, reps_per_set=PER_SET, n_replicates=N, max_cells=600,
-                max_time=6.0, hist_bins=bins, init={0: 1, 1: 1, 12: 1}, flags=_flags(store), bin_kmax=kmax,
-                keep_cells=KEEP)
-    base.update(kw)
-    return abi.RunSpec(**base)
-
-
-def _launched(engine_mod, spec):
-    ctx = engine_mod.Context(spec)
-    ctx.launch()
-    ctx.sync()
-    return ctx
-
-
-def _nk(headers):
-    return headers["nminus"].astype(np.int64) + headers["nplus"]
 
 
 def _mask(tp):
@@ -76,10 +38,6 @@ def _same(got, want, tag=""):
     np.testing.assert_array_equal(got.ranks, want.ranks, err_msg=f"{tag}: ranks")
     np.testing.assert_array_equal(got.values.view(np.uint64), want.values.view(np.uint64), err_msg=f"{tag}: values")
     np.testing.assert_array_equal(got.counts_le, want.counts_le, err_msg=f"{tag}: counts_le")
-
-
-def _bytes_of(r):
-    return (r.population, r.ranks.tobytes(), r.values.tobytes(), r.counts_le.tobytes())
 
 
 def _walked(digits, K, law_digits=None, tag="", **kw):
@@ -288,7 +246,7 @@ def test_error_replicates_are_in_no_histogram_row(engine_mod, store, kmax):
 def test_guard_headers_contribute_the_key_of_zero(engine_mod):
     """The state of tests/test_gpu_sample_states.py::test_end_to_end_at_the_size_guard: every kept header is the
     guard's, every record all zero — every key is key(0.0)."""
-    from test_gpu_sample_states import E2E_BINS, _e2e_spec
+    from support.state_specs import E2E_BINS, _e2e_spec
 
     spec = _e2e_spec("bins", {0: 2**32 - 3, 1: 2}, max_cells=10, cell_cap=64)
     t = _targets(E2E_BINS, 2)

@@ -12,44 +12,16 @@ import pytest
 import snapshot_stats_law as ssl
 from ecdna_evo_amd import abi
 from exact_law import chi2_lumped
+from support.snapshot_specs import BINS, SNAPS, _spec, _store_flags
 
 RTOL, ATOL = 1e-12, 1e-14
 FLOATS = ("mean", "entropy", "frequency", "ks", "mean_rel", "entropy_rel", "frequency_diff")
 # rows, the bin store at every K (the 300-copy cell lies in the large-k row of each), and the reference draws
 STORES = [("rows", 0), ("bins", 32), ("bins", 64), ("bins", 256), ("refdraws", 0)]
-BINS = 257
-SNAPS = (4, 40, 300, 1000, 2000)
 # (999: the complement with m' = 1 at the 1000-cell snapshot, beside the sizes the ABC tests use)
 SAMPLE_SIZES = (1, 63, 64, 65, 700, 999, 1500, 1999, 2000, 4096)
 _ORACLE = {}
 _FULL = {}
-
-
-def _targets(bins, n):
-    """One target per snapshot, each its own."""
-    rng = np.random.default_rng(5)
-    t = np.zeros((n, bins), np.uint64)
-    for s in range(n):
-        t[s, 0] = 400 - 50 * s
-        t[s, 1:40 + 10 * s] = rng.integers(0, 90, 39 + 10 * s)
-        t[s, bins - 1] = 3 + s
-    return t
-
-
-def _store_flags(store):
-    return {"rows": 0, "bins": abi.FLAG_BIN_STORE, "refdraws": abi.FLAG_REFERENCE_DRAWS}[store]
-
-
-def _spec(store, kmax, with_target, m, flags=abi.FLAG_SNAPSHOT_ROWS | abi.FLAG_EVENT_HASH, **kw):
-    """The shape of the ABC-statistics tests: the 300-copy cell reaches the overflow bin; extinct replicates, and the
-    snapshot at max_cells (the stop check comes before the snapshot rule), are not taken; the snapshot
-    at 4 cells is the initial state."""
-    base = dict(seed=4, process=abi.BIRTH_DEATH, rates=((1.0, 1.4, 0.3, 0.3), (1.0, 2.0, 0.5, 0.2)), reps_per_set=300,
-                n_replicates=600, max_cells=2000, hist_bins=BINS, init={1: 3, 300: 1}, snapshots=SNAPS,
-                flags=abi.FLAG_REP_STATS | flags | _store_flags(store), bin_kmax=kmax, snapshot_stats=True,
-                snapshot_targets=_targets(BINS, len(SNAPS)) if with_target else None, snapshot_subsample_cells=m)
-    base.update(kw)
-    return abi.RunSpec(**base)
 
 
 def dataclass_replace(spec, **kw):

@@ -18,7 +18,7 @@ import select_law as slw
 import thin_law as tl
 from ecdna_evo_amd import abi
 from exact_law import chi2_lumped
-from test_gpu_cohort import _same_accept, _same_select
+from support.gpu import _flags, _launched, _same_accept, _same_select
 
 RTOL, ATOL = 1e-12, 1e-14
 FLOATS = ("mean", "entropy", "frequency", "ks", "mean_rel", "entropy_rel", "frequency_diff")
@@ -31,10 +31,6 @@ SIZES = (199, 90, 130, 1, 198, 60)
 DRAWS = (0, 0, 0, 3, 0, 63)
 P = len(SIZES)
 _RUNS = {}
-
-
-def _flags(store):
-    return abi.FLAG_REP_STATS | abi.FLAG_EVENT_HASH | (abi.FLAG_BIN_STORE if store == "bins" else 0)
 
 
 def _targets(bins, n=P):
@@ -53,13 +49,6 @@ def _spec(store, kmax, bins, **kw):
                 keep_cells=KEEP)
     base.update(kw)
     return abi.RunSpec(**base)
-
-
-def _launched(engine_mod, spec):
-    ctx = engine_mod.Context(spec)
-    ctx.launch()
-    ctx.sync()
-    return ctx
 
 
 def _same_record(got, want, tag):
@@ -239,7 +228,7 @@ def test_limits(engine_mod, store, kmax):
 def test_guard_headers_give_all_zero_records(engine_mod, store):
     """The state of tests/test_gpu_sample_states.py::test_end_to_end_at_the_size_guard (n- + n+ = 2^32 - 1): every kept
     header is the guard's, and every (m1, d) gives the all-zero record."""
-    from test_gpu_sample_states import E2E_BINS, _e2e_spec
+    from support.state_specs import E2E_BINS, _e2e_spec
 
     spec = _e2e_spec(store, {0: 2**32 - 3, 1: 2}, max_cells=10, cell_cap=64)
     t = _targets(E2E_BINS, 4)

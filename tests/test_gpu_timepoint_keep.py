@@ -13,17 +13,15 @@ import pytest
 
 import timepoint_keep_law as tl
 from ecdna_evo_amd import abi
-from test_gpu_accept import ALL_INF_ROW, _thresholds
-from test_gpu_cohort import _same_accept, _same_select
-from test_gpu_keep import _canon, _source_codes
-from test_gpu_passages import BINS as PBINS
-from test_gpu_passages import CASES, G, N, _base, _chain, _passage_spec
-from test_gpu_passages import SEED as PSEED
-from test_gpu_passages import _targets as _pas_targets
-from test_gpu_snapshot_stats import BINS as SBINS
-from test_gpu_snapshot_stats import SNAPS
-from test_gpu_snapshot_stats import _spec as _snap_spec
-from test_gpu_snapshot_stats import _targets as _snap_targets
+from support.gpu import ALL_INF_ROW, _canon, _launched, _same_accept, _same_select, _source_codes, _thresholds
+from support.passage_specs import BINS as PBINS
+from support.passage_specs import CASES, G, N, _base, _chain, _passage_spec
+from support.passage_specs import SEED as PSEED
+from support.passage_specs import _targets as _pas_targets
+from support.snapshot_specs import BINS as SBINS
+from support.snapshot_specs import SNAPS
+from support.snapshot_specs import _spec as _snap_spec
+from support.snapshot_specs import _targets as _snap_targets
 
 INF = np.inf
 S = len(SNAPS)
@@ -34,19 +32,12 @@ FRACTIONS, RANKS = (0.01, 0.1, 0.5, 1.0), (1, 2, 50, 191, 192, 193)
 SOURCE = abi.ACCEPT_RESCORED_TIMEPOINTS
 
 
-def _launched(engine_mod, spec):
-    ctx = engine_mod.Context(spec)
-    ctx.launch()
-    ctx.sync()
-    return ctx
-
-
 def _canon_t(headers, cells):
     return b"".join(_canon(headers[t], cells[t]) for t in range(headers.shape[0]))
 
 
 def _thresholds_at(rec, summaries, t):
-    """test_gpu_accept._thresholds from the records of timepoint t alone (rec: [T][n]): rows that tell replicates apart
+    """support.gpu._thresholds from the records of timepoint t alone (rec: [T][n]): rows that tell replicates apart
     there, whatever the other timepoints hold (a snapshot that was not taken has ks = 1.0 in every replicate)."""
     return _thresholds(np.ascontiguousarray(rec[t][:, None]), summaries)
 

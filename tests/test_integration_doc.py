@@ -171,7 +171,7 @@ def test_cli_extra_flag_table_matches_help():
     assert "ChaCha8" in ref_row and "Philox side stream" not in ref_row
 
 
-def test_knob_table_names_the_planner_knobs(tmp_path):
+def test_knob_table_names_the_planner_knobs(tmp_path_factory):
     """INTEGRATION.md §6 lists exactly the ECDNA_SSA_* variables the library reads (the planner's knob table,
     ecdna-evo_amd/csrc/ssa_plan.hpp, printed by tests/native/plan_check.cpp), both ways."""
     import shutil
@@ -181,9 +181,10 @@ def test_knob_table_names_the_planner_knobs(tmp_path):
 
     if shutil.which("hipcc") is None:
         pytest.skip("hipcc absent")
-    from test_launch_plan import build_plan_check
+    from support import native
 
-    out = subprocess.run([build_plan_check(tmp_path), "knobs"], capture_output=True, text=True, check=True)
+    out = subprocess.run([native.build(tmp_path_factory, "plan_check"), "knobs"], capture_output=True, text=True,
+                         check=True)
     knobs = set(out.stdout.split())
     assert len(knobs) == 14 and all(k.startswith("ECDNA_SSA_") for k in knobs), knobs
     with open(DOC) as f:

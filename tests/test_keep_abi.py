@@ -4,50 +4,32 @@ exports the calls, the ctypes mirrors have the header's layout, the version is s
 sizes, the header states the mapping, ecdna_ssa_ctx_create_keep validates the block before any device is touched, and
 RunSpec builds it."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
+from support.abi import HEADER, PARAMS_SIZE_V13, declared, header_text, layout, product_lib  # noqa: F401 (fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
-PARAMS_SIZE_V13 = 184  # sizeof(ecdna_ssa_params_t) as ABI v13 introduced it (LP64)
 BINS = 9
 NEW_CALLS = ("ecdna_ssa_ctx_create_keep", "ecdna_ssa_ctx_rescore", "ecdna_ssa_ctx_download_rescored",
              "ecdna_ssa_ctx_pool_accepted", "ecdna_ssa_ctx_download_kept")
 
 
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
-
-
-def _declared(text, name):
-    m = re.search(r"int\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, f"include/ecdna_ssa.h does not declare {name}"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
-
-
 def test_header_declares_and_library_exports_the_calls(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert _declared(text, "ecdna_ssa_ctx_create_keep") == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_create_keep") == [
         "const ecdna_ssa_params_t* p", "const ecdna_ssa_ext_t* ext", "const ecdna_ssa_passages_t* passages",
         "const ecdna_ssa_cohort_t* cohort", "const ecdna_ssa_keep_t* keep", "ecdna_ssa_ctx** out"]
-    assert _declared(text, "ecdna_ssa_ctx_rescore") == [
+    assert declared("ecdna_ssa_ctx_rescore") == [
         "ecdna_ssa_ctx* c", "uint32_t n_targets", "const uint64_t* target_hists"]
-    assert _declared(text, "ecdna_ssa_ctx_download_rescored") == ["ecdna_ssa_ctx* c", "ecdna_rep_stats_t* out"]
-    assert _declared(text, "ecdna_ssa_ctx_pool_accepted") == [
+    assert declared("ecdna_ssa_ctx_download_rescored") == ["ecdna_ssa_ctx* c", "ecdna_rep_stats_t* out"]
+    assert declared("ecdna_ssa_ctx_pool_accepted") == [
         "ecdna_ssa_ctx* c", "uint32_t threshold", "uint64_t* out_hist"]
-    assert _declared(text, "ecdna_ssa_ctx_download_kept") == [
+    assert declared("ecdna_ssa_ctx_download_kept") == [
         "ecdna_ssa_ctx* c", "uint64_t n_ids", "const uint64_t* ids", "ecdna_kept_t* out_headers", "uint16_t* out_cells"]
     for name in NEW_CALLS:
         assert hasattr(product_lib, name) and name in engine.EXPORTS, name
@@ -67,7 +49,7 @@ def test_null_context_calls_are_invalid(product_lib):
 
 
 def test_the_source_is_12():
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    text = header_text()
     assert re.search(r"\bECDNA_ACCEPT_RESCORED\s*=\s*12\b", text) and abi.ACCEPT_RESCORED == 12
     assert re.search(r"\bECDNA_ACCEPT_COHORT_SAMPLES\s*=\s*9\s*,", text)  # the older ones did not move
     assert re.search(r"\bECDNA_ACCEPT_COHORT\s*=\s*8\s*,", text)
@@ -114,31 +96,13 @@ def test_keep_layout_matches_header(tmp_path):
     keep_fields = [f for f, _ in abi.Keep._fields_]
     kept_fields = [f for f, _ in abi.Kept._fields_]
     assert keep_fields == ["struct_size", "keep_cells", "reserved"] and kept_fields == ["nminus", "nplus"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("{\\"keep\\": %zu, \\"kept\\": %zu", sizeof(ecdna_ssa_keep_t), sizeof(ecdna_kept_t));']
-    for f in keep_fields:
-        lines.append(f'printf(", \\"keep.{f}\\": %zu", offsetof(ecdna_ssa_keep_t, {f}));')
-    for f in kept_fields:
-        lines.append(f'printf(", \\"kept.{f}\\": %zu", offsetof(ecdna_kept_t, {f}));')
-    lines += ['printf(", \\"rescored_source\\": %d", (int)ECDNA_ACCEPT_RESCORED);',
-              'printf(", \\"cohort_samples_source\\": %d", (int)ECDNA_ACCEPT_COHORT_SAMPLES);',
-              'printf(", \\"cohort\\": %zu", sizeof(ecdna_ssa_cohort_t));',
-              'printf(", \\"cohort.reserved\\": %zu", offsetof(ecdna_ssa_cohort_t, reserved));',
-              'printf(", \\"select\\": %zu", sizeof(ecdna_ssa_select_t));',
-              'printf(", \\"accept\\": %zu", sizeof(ecdna_ssa_accept_t));',
-              'printf(", \\"accept.reserved\\": %zu", offsetof(ecdna_ssa_accept_t, reserved));',
-              'printf(", \\"passages\\": %zu", sizeof(ecdna_ssa_passages_t));',
-              'printf(", \\"ext\\": %zu", sizeof(ecdna_ssa_ext_t));',
-              'printf(", \\"stats\\": %zu", sizeof(ecdna_rep_stats_t));',
-              'printf(", \\"summary\\": %zu", sizeof(ecdna_rep_summary_t));',
-              'printf(", \\"instance\\": %zu", sizeof(ecdna_ssa_instance_t));',
-              'printf(", \\"params.subsample_cells\\": %zu", offsetof(ecdna_ssa_params_t, subsample_cells));',
-              'printf(", \\"params\\": %zu}\\n", sizeof(ecdna_ssa_params_t));', "return 0;}"]
-    src = tmp_path / "keep_layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "keep_layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = json.loads(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
+    got = layout(tmp_path, {"keep": ("ecdna_ssa_keep_t", keep_fields), "kept": ("ecdna_kept_t", kept_fields),
+                            "cohort": ("ecdna_ssa_cohort_t", ["reserved"]), "select": "ecdna_ssa_select_t",
+                            "accept": ("ecdna_ssa_accept_t", ["reserved"]), "passages": "ecdna_ssa_passages_t",
+                            "ext": "ecdna_ssa_ext_t", "stats": "ecdna_rep_stats_t", "summary": "ecdna_rep_summary_t",
+                            "instance": "ecdna_ssa_instance_t", "params": ("ecdna_ssa_params_t", ["subsample_cells"])},
+                 values={"rescored_source": "ECDNA_ACCEPT_RESCORED",
+                         "cohort_samples_source": "ECDNA_ACCEPT_COHORT_SAMPLES"})
     assert got["keep"] == C.sizeof(abi.Keep) == 16 and got["kept"] == C.sizeof(abi.Kept) == abi.KEPT_DTYPE.itemsize == 8
     for f in keep_fields:
         assert got[f"keep.{f}"] == getattr(abi.Keep, f).offset, f

@@ -4,31 +4,16 @@ validation.
 
 tests/native/keep_check.cpp is a stand-alone program, built for the host alone with the address and
 undefined-behaviour sanitizers (any report ends it with an error); it is never loaded into Python."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import native
 
-pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc absent")
+pytestmark = native.needs_hipcc
 
 
 @pytest.fixture(scope="module")
 def keep_check(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp("keep_check")), "keep_check")
-    subprocess.run(["hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "ecdna-evo_amd", "csrc"),
-                    os.path.join(REPO, "tests", "native", "keep_check.cpp"), "-o", exe], check=True)
-    return exe
-
-
-def _run(exe, *args):
-    out = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and out.stderr == "", out.stderr[-4000:]  # (no sanitizer report)
-    return out.stdout.splitlines()
+    return native.build(tmp_path_factory, "keep_check")
 
 
 def _want(first, stride, n, rid):
@@ -48,19 +33,19 @@ def test_ids_map_to_their_index_in_the_call(keep_check):
         (10, 1, 1, [9, 10, 11]),
     ]
     for first, stride, n, ids in cases:
-        got = _run(keep_check, "index", first, stride, n, *ids)
+        got = native.run(keep_check, "index", first, stride, n, *ids)
         assert got == [_want(first, stride, n, r) for r in ids], (first, stride, n)
-    assert _run(keep_check, "index", 1, 2, 300, 1, 3, 599) == ["0", "1", "299"]
+    assert native.run(keep_check, "index", 1, 2, 300, 1, 3, 599) == ["0", "1", "299"]
     # (the ABI reads a stride of 0 as 1 before it asks; the map itself takes no id under a stride of 0)
-    assert _run(keep_check, "index", 0, 0, 5, 0, 3) == ["no", "no"]
+    assert native.run(keep_check, "index", 0, 0, 5, 0, 3) == ["no", "no"]
 
 
 def test_bytes_of_the_kept_samples(keep_check):
     # the C4 sweep at m = 200: n x m x 2 bytes of cells (1.7 GB) and 8 bytes of header per replicate
-    assert _run(keep_check, "bytes", 4194304, 200) == [f"cells {4194304 * 200 * 2} headers {4194304 * 8}"]
-    assert _run(keep_check, "bytes", (1 << 32) - 1, 4096) == [f"cells {((1 << 32) - 1) * 8192} headers {((1 << 32) - 1) * 8}"]
-    assert _run(keep_check, "bytes", 0, 64) == ["cells 128 headers 8"]  # an empty call still holds one replicate's
+    assert native.run(keep_check, "bytes", 4194304, 200) == [f"cells {4194304 * 200 * 2} headers {4194304 * 8}"]
+    assert native.run(keep_check, "bytes", (1 << 32) - 1, 4096) == [f"cells {((1 << 32) - 1) * 8192} headers {((1 << 32) - 1) * 8}"]
+    assert native.run(keep_check, "bytes", 0, 64) == ["cells 128 headers 8"]  # an empty call still holds one replicate's
 
 
 def test_every_validation_branch(keep_check):
-    assert _run(keep_check, "validate") == ["validate ok"]
+    assert native.run(keep_check, "validate") == ["validate ok"]

@@ -8,16 +8,12 @@ the plan of each case it reads. The bench shapes are bench.workload_spec's own; 
 measurements: 256 CUs, 8 XCCs, 256 GiB free, the occupancies of tests/test_instance_rules.py's table (and 4 workgroups
 per CU for the 128-VGPR build). Every expected value below is worked out from the rules by hand, in the comment beside
 it; tests/test_gpu_bench_instances.py asserts the same instances on hardware."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
 import bench
 from ecdna_evo_amd import abi, shard
+from support import native
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GIB = 1 << 30
 OFF = 0xFFFFFFFF  # admit_slot of a chunk without the drain control
 FACTS = dict(cus=256, xccs=8, free=256 * GIB)
@@ -29,31 +25,19 @@ OCC_K64_U32 = dict(occ0=2, occ1=2, occ3=2)  # LDS bounds both builds at 2
 OCC_K64_U16 = dict(occ0=4, occ1=3, occ2=4, occ3=2)
 
 
-def build_plan_check(directory):
-    """tests/native/plan_check.cpp for the host, with ASan and UBSan (any report ends the program with an error)."""
-    exe = os.path.join(str(directory), "plan_check")
-    subprocess.run(["hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "ecdna-evo_amd", "csrc"),
-                    os.path.join(REPO, "tests", "native", "plan_check.cpp"), "-o", exe], check=True)
-    return exe
-
-
-pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc absent")
+pytestmark = native.needs_hipcc
 
 
 @pytest.fixture(scope="module")
 def plans(tmp_path_factory):
-    exe = build_plan_check(tmp_path_factory.mktemp("plan_check"))
+    exe = native.build(tmp_path_factory, "plan_check")
 
     def run(cases):
         """cases: dicts of plan_check's words. Returns per case (plan fields, [chunk fields]), all integers but
         rot_parts (a list of them)."""
         text = "".join(" ".join(f"{k}={v}" for k, v in c.items()) + "\n" for c in cases)
-        out = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120)
-        assert out.returncode == 0 and out.stderr == "", out.stderr[-4000:]  # (no sanitizer report)
         res = []
-        for line in out.stdout.splitlines():
+        for line in native.run(exe, stdin=text):
             kind, *words = line.split()
             d = dict(w.split("=") for w in words)
             d = {k: [int(x) for x in v.split(",")] if k == "rot_parts" else int(v) for k, v in d.items()}

@@ -19,12 +19,13 @@ any discretization, so it does not measure the draw; the KS distance does.) The 
 ziggurat from 64-bit words and casts to f32 (rand_distr 0.4.3)."""
 import math
 import os
-import shutil
 import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
+
+from support import native
 
 f32 = np.float32
 TWO32 = 1 << 32
@@ -151,20 +152,17 @@ def test_v6_channel_bias_that_v7_removes(oracle_mod):
     assert abs((b[2] - b[1]) / TWO32 - p_dm) <= 2.0**-32
 
 
-@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc absent")
-def test_kernel_header_channel_matches_the_oracle(tmp_path, oracle_mod):
+@native.needs_hipcc
+def test_kernel_header_channel_matches_the_oracle(tmp_path_factory, oracle_mod):
     """The stepper header's chan_target (ecdna-evo_amd/csrc/ssa_device.hpp, host-callable) with the steppers'
     propensity sequence, compiled for the host and compared with oracle_channel over 1.7M cases: random rates in
     the accepted range (and zeros), populations 0 .. 2^32 - 1, and the words either side of every boundary
     (tests/native/device_math_check.cpp). Guards the kernels' channel arithmetic on a machine without a GPU. Then the
     header's rcp_newton (the time step's reciprocal, draw mapping v8) against RN32(1 / d)."""
-    exe = tmp_path / "device_math_check"
-    subprocess.run(["hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-I",
-                    os.path.join(REPO, "ecdna-evo_amd", "csrc"), os.path.join(REPO, "tests", "native",
-                                                                              "device_math_check.cpp"),
-                    "-L", os.path.join(REPO, "oracle", "_build"), "-lecdna_oracle",
-                    "-Wl,-rpath," + os.path.join(REPO, "oracle", "_build"), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    exe = native.build(tmp_path_factory, "device_math_check", sanitize=False,
+                       extra=["-L", os.path.join(REPO, "oracle", "_build"), "-lecdna_oracle",
+                              "-Wl,-rpath," + os.path.join(REPO, "oracle", "_build")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert out.stdout.strip().endswith("mismatches=0")
     # the time step's reciprocal (draw mapping v8): the Newton step gives RN32(1 / d) from either faithful start, for

@@ -3,7 +3,6 @@ oracle as the per-rank engine. Each rank runs its contiguous global-id shard; on
 histograms and totals; the result must be bit-identical to a single-process run of all replicates
 (the 1-GPU == N-GPU identity)."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from ecdna_evo_amd import abi, shard
+from support.gpu import _free_port
 
 
 def _spec(first, n, total, stride=1):
@@ -19,14 +19,6 @@ def _spec(first, n, total, stride=1):
                        rates=((1.0, 1.0, 0.1, 0.1), (1.0, 1.5, 0.3, 0.3), (1.0, 2.0, 0.5, 0.2)),
                        reps_per_set=total // 3, first_replicate=first, n_replicates=n, replicate_stride=stride,
                        max_cells=500, hist_bins=129, flags=abi.FLAG_EVENT_HASH)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, total, port, outdir, mode):

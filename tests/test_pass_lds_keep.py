@@ -7,8 +7,8 @@ K and m of tests/test_pass_lds.py. The formulas are restated here:
  - ssa_pool_accepted: one u64 histogram per workgroup of four waves.
 The selectors 0 .. 2 keep their meaning (tests/test_pass_lds.py)."""
 import itertools
+from support.pass_lds import BAG_K, BINS, LDS_MAX, M, PASSAGE, passage_plan, plan, waves_within  # noqa: F401 (plan: fixture)
 
-from test_pass_lds import BAG_K, BINS, LDS_MAX, M, PASSAGE, passage_plan, plan, waves_within  # noqa: F401 (plan: fixture)
 
 KEEP, RESCORE, POOL = 3, 4, 5
 

@@ -4,8 +4,8 @@ row only, so it takes the passage pass's plan with bag_k = 0: no workgroup histo
 table of drawn positions (u32) and the kept cells while they are sorted (u16); 1, 2 or 4 waves, the most that keep the
 workgroup within 64 KiB. The selectors 0 .. 5 keep their meaning (tests/test_pass_lds.py, tests/test_pass_lds_keep.py)."""
 import itertools
+from support.pass_lds import LDS_MAX, PASSAGE, passage_plan, plan, sort_slots, table_slots  # noqa: F401 (plan: fixture)
 
-from test_pass_lds import LDS_MAX, PASSAGE, passage_plan, plan, sort_slots, table_slots  # noqa: F401 (plan: fixture)
 
 KEEP_SNAPSHOTS = 6
 BINS = (2, 257, 2048)

@@ -3,42 +3,23 @@ passage block and its two entry points, the library exports them, the ctypes mir
 is still 13 and the older blocks kept their sizes, and ecdna_ssa_ctx_create_passages validates the block before any
 device is touched."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
-PARAMS_SIZE_V13 = 184  # sizeof(ecdna_ssa_params_t) as ABI v13 introduced it (LP64)
-
-
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
-
-
-def _declared(text, name):
-    m = re.search(r"int\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, f"include/ecdna_ssa.h does not declare {name}"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
+from support.abi import PARAMS_SIZE_V13, declared, header_text, layout, product_lib  # noqa: F401 (fixture)
 
 
 def test_header_declares_and_library_exports_the_calls(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert _declared(text, "ecdna_ssa_ctx_create_passages") == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_create_passages") == [
         "const ecdna_ssa_params_t* p", "const ecdna_ssa_ext_t* ext", "const ecdna_ssa_passages_t* passages",
         "ecdna_ssa_ctx** out"]
-    assert _declared(text, "ecdna_ssa_ctx_download_passages") == [
+    assert declared("ecdna_ssa_ctx_download_passages") == [
         "ecdna_ssa_ctx* c", "ecdna_rep_summary_t* out_summaries", "ecdna_totals_t* out_totals",
         "ecdna_rep_stats_t* out_stats", "ecdna_rep_stats_t* out_sample_stats", "uint64_t* out_hist",
         "uint64_t* out_sample_hist"]
@@ -55,20 +36,11 @@ def test_passages_layout_matches_header(tmp_path):
     """sizeof and the field offsets from a compiled C probe against the ctypes mirror; the older blocks did not move."""
     fields = [f for f, _ in abi.Passages._fields_]
     assert fields == ["struct_size", "n_passages", "passage_cells", "reserved", "passage_target_hists"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("{\\"size\\": %zu", sizeof(ecdna_ssa_passages_t));']
+    got = layout(tmp_path, {"passages": ("ecdna_ssa_passages_t", fields), "ext": "ecdna_ssa_ext_t",
+                            "params": "ecdna_ssa_params_t"})
+    assert got["passages"] == C.sizeof(abi.Passages) == 24
     for f in fields:
-        lines.append(f'printf(", \\"{f}\\": %zu", offsetof(ecdna_ssa_passages_t, {f}));')
-    lines += ['printf(", \\"ext\\": %zu", sizeof(ecdna_ssa_ext_t));',
-              'printf(", \\"params\\": %zu}\\n", sizeof(ecdna_ssa_params_t));', "return 0;}"]
-    src = tmp_path / "passages_layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "passages_layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = json.loads(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
-    assert got["size"] == C.sizeof(abi.Passages) == 24
-    for f in fields:
-        assert got[f] == getattr(abi.Passages, f).offset, f
+        assert got[f"passages.{f}"] == getattr(abi.Passages, f).offset, f
     assert got["ext"] == C.sizeof(abi.Ext) == 24
     assert got["params"] == C.sizeof(abi.Params) == PARAMS_SIZE_V13  # ecdna_ssa_params_t did not grow
 

@@ -3,43 +3,29 @@
 version is still 13, the header states the mapping, a bad call is ECDNA_E_INVALID with the field named before a device
 is touched, and engine.Context.pool_draws checks its arguments."""
 import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
+from support.abi import HEADER, declared, header_text, layout, product_lib  # noqa: F401 (fixture)
+from support.draws_specs import _block
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
 BINS = 9
 INF = np.inf
-
-
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
-
-
-def _declared(text, name):
-    m = re.search(r"int\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, f"include/ecdna_ssa.h does not declare {name}"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_header_declares_and_library_exports_the_call(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert _declared(text, "ecdna_ssa_ctx_pool_draws") == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_pool_draws") == [
         "ecdna_ssa_ctx* c", "const ecdna_ssa_accept_draws_t* a", "uint32_t threshold", "uint64_t* out_thinned",
         "uint64_t* out_kept"]
     # the calls it stands beside did not change
-    assert _declared(text, "ecdna_ssa_ctx_accept_draws") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_accept_draws_t* a"]
-    assert _declared(text, "ecdna_ssa_ctx_pool_accepted") == ["ecdna_ssa_ctx* c", "uint32_t threshold",
+    assert declared("ecdna_ssa_ctx_accept_draws") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_accept_draws_t* a"]
+    assert declared("ecdna_ssa_ctx_pool_accepted") == ["ecdna_ssa_ctx* c", "uint32_t threshold",
                                                               "uint64_t* out_hist"]
     assert hasattr(product_lib, "ecdna_ssa_ctx_pool_draws") and "ecdna_ssa_ctx_pool_draws" in engine.EXPORTS
     want = [C.c_void_p, C.POINTER(abi.AcceptDraws), C.c_uint32, C.c_void_p, C.c_void_p]
@@ -49,20 +35,6 @@ def test_header_declares_and_library_exports_the_call(product_lib):
     # additive: the version is v13's and the block kept its size
     assert re.search(r"#define ECDNA_SSA_ABI_VERSION 13\b", text) and abi.ABI_VERSION == 13
     assert product_lib.ecdna_ssa_abi_version() == 13 and C.sizeof(abi.AcceptDraws) == 72
-
-
-def _block(hists, cells, thr, **kw):
-    thr = np.ascontiguousarray(thr, dtype=np.float64).reshape(-1, 4)
-    cells = None if cells is None else np.ascontiguousarray(cells, dtype=np.uint32)
-    a = abi.AcceptDraws(struct_size=C.sizeof(abi.AcceptDraws), n_targets=hists.shape[0], n_draws=64,
-                        n_thresholds=thr.shape[0])
-    a.target_hists = hists.ctypes.data_as(C.POINTER(C.c_uint64))
-    if cells is not None:
-        a.sample_cells = cells.ctypes.data_as(C.POINTER(C.c_uint32))
-    a.thresholds = thr.ctypes.data_as(C.POINTER(abi.AcceptThreshold))
-    for k, v in kw.items():
-        setattr(a, k, v)
-    return a, (hists, cells, thr)
 
 
 def test_null_arguments_are_invalid_as_accept_draws_says(product_lib):

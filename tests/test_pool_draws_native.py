@@ -4,32 +4,19 @@ plan at its limits, the byte counts, and the launches' check of the group tables
 
 tests/native/pool_draws_check.cpp is a stand-alone program, built for the host alone with the address and
 undefined-behaviour sanitizers (any report ends it with an error); it is never loaded into Python."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import native
+from support.native import _want_keep, _want_timepoints
+
 PASS_LDS_MAX = 65536  # kPassLdsMax
 
-pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc absent")
+pytestmark = native.needs_hipcc
 
 
 @pytest.fixture(scope="module")
 def check(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp("pool_draws_check")), "pool_draws_check")
-    subprocess.run(["hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "ecdna-evo_amd", "csrc"),
-                    os.path.join(REPO, "tests", "native", "pool_draws_check.cpp"), "-o", exe], check=True)
-    return exe
-
-
-def _run(exe, *args):
-    out = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and out.stderr == "", out.stderr[-4000:]  # (no sanitizer report)
-    return out.stdout.splitlines()
+    return native.build(tmp_path_factory, "pool_draws_check")
 
 
 def _grouping(lines, name):
@@ -45,31 +32,11 @@ def _grouping(lines, name):
 
 def _plan(exe, keep, timepoints, mask, sizes):
     """(the verdict's grouping, the pooling's, the max m' the LDS plan is sized for)."""
-    lines = [ln.split() for ln in _run(exe, "plan", keep, int(timepoints), "%x" % mask, *sizes)]
+    lines = [ln.split() for ln in native.run(exe, "plan", keep, int(timepoints), "%x" % mask, *sizes)]
     verdict, rest = _grouping(lines, "verdict")
     pool, rest = _grouping(rest, "pool")
     assert len(rest) == 1 and rest[0][:2] == ["lds", "max_mp"]
     return verdict, pool, int(rest[0][2])
-
-
-def _want_keep(keep, mask, sizes):
-    """The keep store restated: one slice; the participating targets by distinct m1 in order of first appearance."""
-    take = [p for p in range(len(sizes)) if mask == 0 or (mask >> p) & 1]
-    order = list(dict.fromkeys(sizes[p] for p in take))
-    groups = [(m, [p for p in take if sizes[p] == m]) for m in order]
-    return 1, 1, max(min(m, keep - m) for m in order), [(0, len(groups))], groups
-
-
-def _want_timepoints(keep, mask, sizes):
-    """The timepoint store restated: slice t takes part when the mask names it, with one group of target t."""
-    T = len(sizes)
-    full = mask if mask else (1 << T) - 1
-    take = [t for t in range(T) if (full >> t) & 1]
-    slices, at = [], 0
-    for t in range(T):
-        slices.append((at, at + (t in take)))
-        at += t in take
-    return T, full, max(min(sizes[t], keep - sizes[t]) for t in take), slices, [(sizes[t], [t]) for t in take]
 
 
 def test_the_keep_store_pools_held_out_targets_too(check):
@@ -114,7 +81,7 @@ def test_the_timepoint_store_pools_one_group_per_slice_whatever_the_mask(check):
 
 
 def test_lds_plan_stays_within_the_pass_limit(check):
-    lines = _run(check, "lds")
+    lines = native.run(check, "lds")
     assert lines[0] == "lds ok"
     got = {}
     for ln in lines[1:]:
@@ -138,7 +105,7 @@ def test_lds_plan_stays_within_the_pass_limit(check):
 
 
 def test_byte_counts(check):
-    lines = _run(check, "bytes")
+    lines = native.run(check, "bytes")
     got = [dict(zip(w[0::2], map(int, w[1::2]))) for w in (ln.split() for ln in lines)]
     # (n_targets + n_slices) x n_param_sets x hist_bins x 8 bytes
     assert got[0] == {"thinned": 2 * 1024 * 1025, "kept": 1024 * 1025, "pooled": (2 + 1) * 1024 * 1025 * 8,
@@ -148,11 +115,11 @@ def test_byte_counts(check):
 
 
 def test_every_validation_branch(check):
-    assert _run(check, "validate") == ["validate ok"]
+    assert native.run(check, "validate") == ["validate ok"]
 
 
 def test_the_launch_check_takes_every_planned_grouping_and_refuses_each_broken_table(check):
-    lines = _run(check, "grouping")
+    lines = native.run(check, "grouping")
     # 8 bins x 8 keep sizes x 2 stores x 3 masks, and per case the verdict's, the pooling's and accept_draws' own plan
     assert lines[0] == "accepted %d" % (8 * 8 * 2 * 3 * 3)
     # one refusal per clause of the conditions launch_accept_draws and launch_pool_draws had spelled out

@@ -3,41 +3,20 @@ without a GPU: the header declares both calls with their argument lists, the lib
 the header's layout, the older blocks kept their sizes, the version is still 13, both calls refuse a NULL context with a
 message, and the header states select mapping v1 and its consequence for ecdna_ssa_ctx_accept."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
-
-import pytest
 
 from ecdna_evo_amd import abi
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
-PARAMS_SIZE_V13 = 184  # sizeof(ecdna_ssa_params_t) as ABI v13 introduced it (LP64)
-
-
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
-
-
-def _declared(text, name):
-    m = re.search(r"int\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, f"include/ecdna_ssa.h does not declare {name}"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
+from support.abi import HEADER, PARAMS_SIZE_V13, declared, header_text, layout, product_lib  # noqa: F401 (fixture)
 
 
 def test_header_declares_and_library_exports_the_calls(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert _declared(text, "ecdna_ssa_ctx_select") == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_select") == [
         "ecdna_ssa_ctx* c", "const ecdna_ssa_select_t* s", "uint64_t* out_population", "uint64_t* out_ranks",
         "double* out_values", "uint64_t* out_counts_le"]
-    assert _declared(text, "ecdna_ssa_ctx_select_digits") == [
+    assert declared("ecdna_ssa_ctx_select_digits") == [
         "ecdna_ssa_ctx* c", "uint32_t source", "uint64_t timepoint_mask", "uint32_t pass", "uint32_t n_prefixes",
         "const uint64_t* prefixes", "uint64_t* out_hist"]
     for name in ("ecdna_ssa_ctx_select", "ecdna_ssa_ctx_select_digits"):
@@ -61,22 +40,10 @@ def test_select_layout_matches_header(tmp_path):
     """sizeof and the field offsets from a compiled C probe against the ctypes mirror; the older blocks did not move."""
     assert [f for f, _ in abi.Select._fields_] == ["struct_size", "source", "timepoint_mask", "n_ranks", "reserved",
                                                    "ranks", "fractions"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){", 'printf("{");',
-             'printf("\\"select\\": %zu, ", sizeof(ecdna_ssa_select_t));']
-    for f, _ in abi.Select._fields_:
-        lines.append(f'printf("\\"select.{f}\\": %zu, ", offsetof(ecdna_ssa_select_t, {f}));')
-    lines += ['printf("\\"accept\\": %zu, ", sizeof(ecdna_ssa_accept_t));',
-              'printf("\\"threshold\\": %zu, ", sizeof(ecdna_accept_threshold_t));',
-              'printf("\\"passages\\": %zu, ", sizeof(ecdna_ssa_passages_t));',
-              'printf("\\"ext\\": %zu, ", sizeof(ecdna_ssa_ext_t));',
-              'printf("\\"stats\\": %zu, ", sizeof(ecdna_rep_stats_t));',
-              'printf("\\"summary\\": %zu, ", sizeof(ecdna_rep_summary_t));',
-              'printf("\\"params\\": %zu}\\n", sizeof(ecdna_ssa_params_t));', "return 0;}"]
-    src = tmp_path / "select_layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "select_layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = json.loads(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
+    got = layout(tmp_path, {"select": ("ecdna_ssa_select_t", [f for f, _ in abi.Select._fields_]),
+                            "accept": "ecdna_ssa_accept_t", "threshold": "ecdna_accept_threshold_t",
+                            "passages": "ecdna_ssa_passages_t", "ext": "ecdna_ssa_ext_t", "stats": "ecdna_rep_stats_t",
+                            "summary": "ecdna_rep_summary_t", "params": "ecdna_ssa_params_t"})
     assert got["select"] == C.sizeof(abi.Select) == 40
     for f, _ in abi.Select._fields_:
         assert got[f"select.{f}"] == getattr(abi.Select, f).offset, f

@@ -3,52 +3,34 @@ select mapping v1) without a GPU: the header declares the two c
 ctypes argtypes match, the version is still 13 and the older blocks kept their sizes, the header states the mapping and
 its contracts, and without a context the calls answer ECDNA_E_INVALID."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
-import pytest
 
 from ecdna_evo_amd import abi
+from support.abi import HEADER, declared, header_text, layout, product_lib  # noqa: F401 (fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
 BINS = 9
 NEW_CALLS = ("ecdna_ssa_ctx_select_draws", "ecdna_ssa_ctx_select_draws_digits")
-
-
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
-
-
-def _declared(text, name):
-    m = re.search(r"int\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, f"include/ecdna_ssa.h does not declare {name}"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_header_declares_and_library_exports_the_calls(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert _declared(text, "ecdna_ssa_ctx_select_draws") == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_select_draws") == [
         "ecdna_ssa_ctx* c", "const ecdna_ssa_accept_draws_t* a", "uint32_t n_ranks", "const uint64_t* ranks",
         "const double* fractions", "uint64_t* out_population", "uint64_t* out_ranks", "double* out_values",
         "uint64_t* out_counts_le"]
-    assert _declared(text, "ecdna_ssa_ctx_select_draws_digits") == [
+    assert declared("ecdna_ssa_ctx_select_draws_digits") == [
         "ecdna_ssa_ctx* c", "const ecdna_ssa_accept_draws_t* a", "uint32_t pass", "uint32_t n_prefixes",
         "const uint64_t* prefixes", "uint64_t* out_hist"]
     # the calls they stand beside did not change
-    assert _declared(text, "ecdna_ssa_ctx_accept_draws") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_accept_draws_t* a"]
-    assert _declared(text, "ecdna_ssa_ctx_pool_draws") == [
+    assert declared("ecdna_ssa_ctx_accept_draws") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_accept_draws_t* a"]
+    assert declared("ecdna_ssa_ctx_pool_draws") == [
         "ecdna_ssa_ctx* c", "const ecdna_ssa_accept_draws_t* a", "uint32_t threshold", "uint64_t* out_thinned",
         "uint64_t* out_kept"]
-    assert _declared(text, "ecdna_ssa_ctx_select_digits") == [
+    assert declared("ecdna_ssa_ctx_select_digits") == [
         "ecdna_ssa_ctx* c", "uint32_t source", "uint64_t timepoint_mask", "uint32_t pass", "uint32_t n_prefixes",
         "const uint64_t* prefixes", "uint64_t* out_hist"]
     for name in NEW_CALLS:
@@ -66,22 +48,11 @@ def test_header_declares_and_library_exports_the_calls(product_lib):
 
 
 def test_the_older_blocks_kept_their_sizes(tmp_path):
-    lines = ["#include <stdio.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("{\\"accept_draws\\": %zu", sizeof(ecdna_ssa_accept_draws_t));',
-             'printf(", \\"accept\\": %zu", sizeof(ecdna_ssa_accept_t));',
-             'printf(", \\"threshold\\": %zu", sizeof(ecdna_accept_threshold_t));',
-             'printf(", \\"select\\": %zu", sizeof(ecdna_ssa_select_t));',
-             'printf(", \\"rescore\\": %zu", sizeof(ecdna_ssa_rescore_t));',
-             'printf(", \\"keep\\": %zu", sizeof(ecdna_ssa_keep_t));',
-             'printf(", \\"keep_timepoints\\": %zu", sizeof(ecdna_ssa_keep_timepoints_t));',
-             'printf(", \\"cohort\\": %zu", sizeof(ecdna_ssa_cohort_t));',
-             'printf(", \\"stats\\": %zu", sizeof(ecdna_rep_stats_t));',
-             'printf(", \\"params\\": %zu}\\n", sizeof(ecdna_ssa_params_t));', "return 0;}"]
-    src = tmp_path / "select_draws_layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "select_draws_layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = json.loads(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
+    got = layout(tmp_path, {"accept_draws": "ecdna_ssa_accept_draws_t", "accept": "ecdna_ssa_accept_t",
+                            "threshold": "ecdna_accept_threshold_t", "select": "ecdna_ssa_select_t",
+                            "rescore": "ecdna_ssa_rescore_t", "keep": "ecdna_ssa_keep_t",
+                            "keep_timepoints": "ecdna_ssa_keep_timepoints_t", "cohort": "ecdna_ssa_cohort_t",
+                            "stats": "ecdna_rep_stats_t", "params": "ecdna_ssa_params_t"})
     assert got["accept_draws"] == C.sizeof(abi.AcceptDraws) == 72
     assert got["accept"] == C.sizeof(abi.Accept) == 48 and got["threshold"] == C.sizeof(abi.AcceptThreshold) == 32
     assert got["select"] == C.sizeof(abi.Select) == 40 and got["rescore"] == C.sizeof(abi.Rescore) == 40

@@ -5,39 +5,24 @@ answers as before, the byte counts, and the comparison "same block as the cached
 
 tests/native/select_draws_check.cpp is a stand-alone program, built for the host alone with the address and
 undefined-behaviour sanitizers (any report ends it with an error); it is never loaded into Python."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import native
 
-pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc absent")
+pytestmark = native.needs_hipcc
 
 
 @pytest.fixture(scope="module")
 def check(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp("select_draws_check")), "select_draws_check")
-    subprocess.run(["hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "ecdna-evo_amd", "csrc"),
-                    os.path.join(REPO, "tests", "native", "select_draws_check.cpp"), "-o", exe], check=True)
-    return exe
-
-
-def _run(exe, *args):
-    out = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and out.stderr == "", out.stderr[-4000:]  # (no sanitizer report)
-    return out.stdout.splitlines()
+    return native.build(tmp_path_factory, "select_draws_check")
 
 
 def test_every_validation_branch(check):
-    assert _run(check, "validate") == ["validate ok"]
+    assert native.run(check, "validate") == ["validate ok"]
 
 
 def test_byte_counts_and_the_bound_of_the_keys(check):
-    got = [dict(zip(w[0::2], map(int, w[1::2]))) for w in (ln.split() for ln in _run(check, "bytes"))]
+    got = [dict(zip(w[0::2], map(int, w[1::2]))) for w in (ln.split() for ln in native.run(check, "bytes"))]
     hist = 4 * 32 * 256 * 8  # one pass: [4][32 groups][256] u64
     small = {"hist": hist, "cdf": 4 * 1025 * 8, "scalars": 4 * 3 * 8}
     # 32 bytes per (replicate, draw): 2.1 GB at the keep shape of the measurement
@@ -51,4 +36,4 @@ def test_byte_counts_and_the_bound_of_the_keys(check):
 
 
 def test_the_same_block_comparison(check):
-    assert _run(check, "same") == ["same ok"]
+    assert native.run(check, "same") == ["same ok"]

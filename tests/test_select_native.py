@@ -5,29 +5,22 @@ kernels of ssa_select.hip call, NaN branch included, which no run reaches — an
 
 tests/native/select_check.cpp is a stand-alone program, built for the host alone with the address and
 undefined-behaviour sanitizers (any report ends it with an error); it is never loaded into Python."""
-import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import select_law as sl
+from support import native
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF, NAN = np.inf, np.nan
 
-pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc absent")
+pytestmark = native.needs_hipcc
 
 
 @pytest.fixture(scope="module")
 def select_check(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp("select_check")), "select_check")
-    subprocess.run(["hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "ecdna-evo_amd", "csrc"),
-                    os.path.join(REPO, "tests", "native", "select_check.cpp"), "-o", exe], check=True)
-    return exe
+    return native.build(tmp_path_factory, "select_check")
 
 
 def _run(exe, values, ranks=None, fractions=None):
@@ -36,9 +29,7 @@ def _run(exe, values, ranks=None, fractions=None):
         "fractions " + " ".join(repr(float(f)) for f in fractions)
     bits = np.ascontiguousarray(values, dtype=np.float64).view(np.uint64)
     text = head + "\n" + "".join("bits " + " ".join(f"{int(b):016x}" for b in row) + "\n" for row in bits)
-    out = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and out.stderr == "", out.stderr[-4000:]  # (no sanitizer report)
-    lines = [ln.split() for ln in out.stdout.splitlines()]
+    lines = [ln.split() for ln in native.run(exe, stdin=text)]
     assert [ln[0] for ln in lines] == ["population", "ranks"] + ["values", "counts"] * 4
     vals = np.array([[int(w, 16) for w in ln[1:]] for ln in lines[2::2]], dtype=np.uint64).view(np.float64)
     counts = np.array([[int(w) for w in ln[1:]] for ln in lines[3::2]], dtype=np.uint64)

@@ -4,10 +4,7 @@ layout, the version is still 13, and ecdna_ssa_ctx_create_ext validates the bloc
 numpy restatement the GPU tests compare against (tests/snapshot_stats_law.py) differs from the end-of-run sample's in
 the stream field only."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,31 +12,16 @@ import pytest
 import snapshot_stats_law as ssl
 import subsample_law as sl
 from ecdna_evo_amd import abi
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
-
-
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
-
-
-def _declared(text, name):
-    m = re.search(r"int\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, f"include/ecdna_ssa.h does not declare {name}"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
+from support.abi import HEADER, declared, header_text, layout, product_lib  # noqa: F401 (fixture)
 
 
 def test_header_declares_and_library_exports_the_calls(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert _declared(text, "ecdna_ssa_ctx_create_ext") == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_create_ext") == [
         "const ecdna_ssa_params_t* p", "const ecdna_ssa_ext_t* ext", "ecdna_ssa_ctx** out"]
-    assert _declared(text, "ecdna_ssa_ctx_download_snapshot_stats") == [
+    assert declared("ecdna_ssa_ctx_download_snapshot_stats") == [
         "ecdna_ssa_ctx* c", "ecdna_rep_stats_t* out_stats", "ecdna_rep_stats_t* out_sample_stats", "uint64_t* out_hist",
         "uint64_t* out_sample_hist"]
     for name in ("ecdna_ssa_ctx_create_ext", "ecdna_ssa_ctx_download_snapshot_stats"):
@@ -57,19 +39,10 @@ def test_ext_layout_matches_header(tmp_path):
     """sizeof and the field offsets from a compiled C probe against the ctypes mirror (as tests/test_abi.py)."""
     fields = [f for f, _ in abi.Ext._fields_]
     assert fields == ["struct_size", "snapshot_stats", "snapshot_target_hists", "snapshot_subsample_cells", "reserved"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("{\\"size\\": %zu", sizeof(ecdna_ssa_ext_t));']
+    got = layout(tmp_path, {"ext": ("ecdna_ssa_ext_t", fields), "params": "ecdna_ssa_params_t"})
+    assert got["ext"] == C.sizeof(abi.Ext) == 24
     for f in fields:
-        lines.append(f'printf(", \\"{f}\\": %zu", offsetof(ecdna_ssa_ext_t, {f}));')
-    lines += ['printf(", \\"params\\": %zu}\\n", sizeof(ecdna_ssa_params_t));', "return 0;}"]
-    src = tmp_path / "ext_layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "ext_layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = json.loads(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
-    assert got["size"] == C.sizeof(abi.Ext) == 24
-    for f in fields:
-        assert got[f] == getattr(abi.Ext, f).offset, f
+        assert got[f"ext.{f}"] == getattr(abi.Ext, f).offset, f
     assert got["params"] == C.sizeof(abi.Params)  # ecdna_ssa_params_t did not grow
 
 

@@ -3,7 +3,6 @@ and validates it, and the numpy restatement the GPU tests compare against (tests
 mapping says and draws uniformly."""
 import ctypes as C
 import itertools
-import os
 import re
 
 import numpy as np
@@ -12,25 +11,14 @@ import pytest
 import subsample_law as sl
 from ecdna_evo_amd import abi
 from exact_law import chi2_lumped
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
-
-
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
+from support.abi import declared, header_text, product_lib  # noqa: F401 (fixture)
 
 
 def test_header_declares_and_library_exports_the_call(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    m = re.search(r"int\s+ecdna_ssa_ctx_download_sample\s*\(([^;]*)\)\s*;", text)
-    assert m, "include/ecdna_ssa.h does not declare ecdna_ssa_ctx_download_sample"
-    assert [" ".join(a.split()) for a in m.group(1).split(",")] == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_download_sample") == [
         "ecdna_ssa_ctx* c", "ecdna_rep_stats_t* out_stats", "uint64_t* out_sample_hist"]
     assert hasattr(product_lib, "ecdna_ssa_ctx_download_sample")
     assert "ecdna_ssa_ctx_download_sample" in engine.EXPORTS
@@ -100,7 +88,7 @@ def test_create_refuses_initial_populations_of_2_to_32_cells(product_lib):
 
 
 def test_vector_philox_is_the_scalar_model():
-    from test_host import _philox
+    from support.host_law import _philox
 
     rng = np.random.default_rng(3)
     ctr = rng.integers(0, 2**32, (50, 4), dtype=np.uint64)
@@ -115,7 +103,7 @@ def test_vector_philox_is_the_scalar_model():
 def test_draws_follow_the_mapping_word_by_word():
     """Draw i: the four words of block (i, 0xC0000000 | t, rid) in order, Lemire's rejection, then block t + 1. N just
     above 2^31 rejects almost every second word, so later words and later blocks are reached."""
-    from test_host import _philox
+    from support.host_law import _philox
 
     seed, rid = 0x5EED0000ABCD, (7 << 32) | 9
     for N in (1, 2, 6, 40, 1000, 2**31 + 12345, 2**32 - 2):

@@ -3,46 +3,28 @@ v13; thinning mapping v1) without a GPU: the header declares th
 exports them, the ctypes mirror has the header's layout, the version is still 13 and the older blocks kept their sizes,
 the header states the mapping, and without a context the calls answer as their siblings do."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
-import pytest
 
 from ecdna_evo_amd import abi
+from support.abi import HEADER, declared, header_text, layout, product_lib  # noqa: F401 (fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
 BINS = 9
 NEW_CALLS = ("ecdna_ssa_ctx_rescore_sized", "ecdna_ssa_ctx_rescore_timepoints_sized")
-
-
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
-
-
-def _declared(text, name):
-    m = re.search(r"int\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, f"include/ecdna_ssa.h does not declare {name}"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_header_declares_and_library_exports_the_calls(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert _declared(text, "ecdna_ssa_ctx_rescore_sized") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_rescore_t* r"]
-    assert _declared(text, "ecdna_ssa_ctx_rescore_timepoints_sized") == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_rescore_sized") == ["ecdna_ssa_ctx* c", "const ecdna_ssa_rescore_t* r"]
+    assert declared("ecdna_ssa_ctx_rescore_timepoints_sized") == [
         "ecdna_ssa_ctx* c", "const uint64_t* target_hists", "const uint32_t* sample_cells", "uint32_t draw"]
     # the unsized calls did not change
-    assert _declared(text, "ecdna_ssa_ctx_rescore") == [
+    assert declared("ecdna_ssa_ctx_rescore") == [
         "ecdna_ssa_ctx* c", "uint32_t n_targets", "const uint64_t* target_hists"]
-    assert _declared(text, "ecdna_ssa_ctx_rescore_timepoints") == ["ecdna_ssa_ctx* c", "const uint64_t* target_hists"]
+    assert declared("ecdna_ssa_ctx_rescore_timepoints") == ["ecdna_ssa_ctx* c", "const uint64_t* target_hists"]
     for name in NEW_CALLS:
         assert hasattr(product_lib, name) and name in engine.EXPORTS, name
     assert product_lib.ecdna_ssa_ctx_rescore_sized.argtypes == [C.c_void_p, C.POINTER(abi.Rescore)]
@@ -57,22 +39,11 @@ def test_layout_matches_header(tmp_path):
     """sizeof and the field offsets from a compiled C probe against the ctypes mirror; the older blocks did not move."""
     fields = [f for f, _ in abi.Rescore._fields_]
     assert fields == ["struct_size", "n_targets", "target_hists", "sample_cells", "sample_draws", "reserved"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("{\\"rescore\\": %zu", sizeof(ecdna_ssa_rescore_t));']
-    for f in fields:
-        lines.append(f'printf(", \\"rescore.{f}\\": %zu", offsetof(ecdna_ssa_rescore_t, {f}));')
-    lines += ['printf(", \\"keep\\": %zu", sizeof(ecdna_ssa_keep_t));',
-              'printf(", \\"keep_timepoints\\": %zu", sizeof(ecdna_ssa_keep_timepoints_t));',
-              'printf(", \\"cohort\\": %zu", sizeof(ecdna_ssa_cohort_t));',
-              'printf(", \\"stats\\": %zu", sizeof(ecdna_rep_stats_t));',
-              'printf(", \\"rescored_source\\": %d", (int)ECDNA_ACCEPT_RESCORED);',
-              'printf(", \\"rescored_timepoints_source\\": %d", (int)ECDNA_ACCEPT_RESCORED_TIMEPOINTS);',
-              'printf(", \\"params\\": %zu}\\n", sizeof(ecdna_ssa_params_t));', "return 0;}"]
-    src = tmp_path / "thin_layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "thin_layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = json.loads(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
+    got = layout(tmp_path, {"rescore": ("ecdna_ssa_rescore_t", fields), "keep": "ecdna_ssa_keep_t",
+                            "keep_timepoints": "ecdna_ssa_keep_timepoints_t", "cohort": "ecdna_ssa_cohort_t",
+                            "stats": "ecdna_rep_stats_t", "params": "ecdna_ssa_params_t"},
+                 values={"rescored_source": "ECDNA_ACCEPT_RESCORED",
+                         "rescored_timepoints_source": "ECDNA_ACCEPT_RESCORED_TIMEPOINTS"})
     assert got["rescore"] == C.sizeof(abi.Rescore) == 40
     for f in fields:
         assert got[f"rescore.{f}"] == getattr(abi.Rescore, f).offset, f

@@ -4,38 +4,24 @@ and every branch of the two calls' validation.
 
 tests/native/thin_check.cpp is a stand-alone program, built for the host alone with the address and
 undefined-behaviour sanitizers (any report ends it with an error); it is never loaded into Python."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import native
+
 PASS_LDS_MAX = 65536  # kPassLdsMax
 
-pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc absent")
+pytestmark = native.needs_hipcc
 
 
 @pytest.fixture(scope="module")
 def thin_check(tmp_path_factory):
-    exe = os.path.join(str(tmp_path_factory.mktemp("thin_check")), "thin_check")
-    subprocess.run(["hipcc", "-x", "hip", "--offload-host-only", "-std=c++17", "-O1",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(REPO, "ecdna-evo_amd", "csrc"),
-                    os.path.join(REPO, "tests", "native", "thin_check.cpp"), "-o", exe], check=True)
-    return exe
-
-
-def _run(exe, *args):
-    out = subprocess.run([exe, *map(str, args)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and out.stderr == "", out.stderr[-4000:]  # (no sanitizer report)
-    return out.stdout.splitlines()
+    return native.build(tmp_path_factory, "thin_check")
 
 
 def _groups(exe, keep, pairs, with_draws=True):
     """[((m1, d), [targets])] and the largest m', as the program printed them."""
     words = [f"{m}:{d}" if with_draws else str(m) for m, d in pairs]
-    lines = [ln.split() for ln in _run(exe, "groups", keep, *words)]
+    lines = [ln.split() for ln in native.run(exe, "groups", keep, *words)]
     assert lines[0][0] == "groups" and lines[0][2] == "max_mp" and int(lines[0][1]) == len(lines) - 1
     return [((int(ln[1]), int(ln[3])), [int(t) for t in ln[5:]]) for ln in lines[1:]], int(lines[0][3])
 
@@ -73,14 +59,14 @@ def test_groups_are_the_distinct_pairs_in_order_of_first_appearance(thin_check):
 
 
 def test_tag_fields_stay_disjoint(thin_check):
-    lines = _run(thin_check, "tag")
+    lines = native.run(thin_check, "tag")
     assert lines[0] == "tag ok"
     # s = 63, d = 63, t = 1023: tag | snapshot field | thinning flag | draw | block
     assert lines[1] == "top 0x%08x" % (0xC0000000 | (64 << 16) | 0x20000000 | (63 << 10) | 1023)
 
 
 def test_lds_plan_stays_within_the_pass_limit(thin_check):
-    lines = _run(thin_check, "lds")
+    lines = native.run(thin_check, "lds")
     assert lines[0] == "lds ok"
     w = lines[1].split()
     assert w[0] == "limits"
@@ -93,4 +79,4 @@ def test_lds_plan_stays_within_the_pass_limit(thin_check):
 
 
 def test_every_validation_branch(thin_check):
-    assert _run(thin_check, "validate") == ["validate ok"]
+    assert native.run(thin_check, "validate") == ["validate ok"]

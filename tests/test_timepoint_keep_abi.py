@@ -4,57 +4,40 @@ the acceptance source 13, the library exports the calls, the ctypes mirror has t
 still 13 and the older blocks kept their sizes, the header states the mapping, ecdna_ssa_ctx_create_keep_timepoints
 validates the block before any device is touched, and RunSpec builds it."""
 import ctypes as C
-import json
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from ecdna_evo_amd import abi
+from support.abi import HEADER, declared, header_text, layout, product_lib  # noqa: F401 (fixture)
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "include", "ecdna_ssa.h")
 BINS = 9
 NEW_CALLS = ("ecdna_ssa_ctx_create_keep_timepoints", "ecdna_ssa_ctx_rescore_timepoints",
              "ecdna_ssa_ctx_download_rescored_timepoints", "ecdna_ssa_ctx_pool_accepted_timepoints",
              "ecdna_ssa_ctx_download_kept_timepoints")
 
 
-@pytest.fixture(scope="module")
-def product_lib():
-    from ecdna_evo_amd import engine
-
-    return engine.lib()
-
-
-def _declared(text, name):
-    m = re.search(r"int\s+" + name + r"\s*\(([^;]*)\)\s*;", text)
-    assert m, f"include/ecdna_ssa.h does not declare {name}"
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
-
-
 def test_header_declares_and_library_exports_the_calls(product_lib):
     from ecdna_evo_amd import engine
 
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert _declared(text, "ecdna_ssa_ctx_create_keep_timepoints") == [
+    text = header_text()
+    assert declared("ecdna_ssa_ctx_create_keep_timepoints") == [
         "const ecdna_ssa_params_t* p", "const ecdna_ssa_ext_t* ext", "const ecdna_ssa_passages_t* passages",
         "const ecdna_ssa_cohort_t* cohort", "const ecdna_ssa_keep_t* keep",
         "const ecdna_ssa_keep_timepoints_t* keep_timepoints", "ecdna_ssa_ctx** out"]
-    assert _declared(text, "ecdna_ssa_ctx_rescore_timepoints") == ["ecdna_ssa_ctx* c", "const uint64_t* target_hists"]
-    assert _declared(text, "ecdna_ssa_ctx_download_rescored_timepoints") == ["ecdna_ssa_ctx* c", "ecdna_rep_stats_t* out"]
-    assert _declared(text, "ecdna_ssa_ctx_pool_accepted_timepoints") == [
+    assert declared("ecdna_ssa_ctx_rescore_timepoints") == ["ecdna_ssa_ctx* c", "const uint64_t* target_hists"]
+    assert declared("ecdna_ssa_ctx_download_rescored_timepoints") == ["ecdna_ssa_ctx* c", "ecdna_rep_stats_t* out"]
+    assert declared("ecdna_ssa_ctx_pool_accepted_timepoints") == [
         "ecdna_ssa_ctx* c", "uint32_t threshold", "uint64_t* out_hist"]
-    assert _declared(text, "ecdna_ssa_ctx_download_kept_timepoints") == [
+    assert declared("ecdna_ssa_ctx_download_kept_timepoints") == [
         "ecdna_ssa_ctx* c", "uint64_t n_ids", "const uint64_t* ids", "ecdna_kept_t* out_headers", "uint16_t* out_cells"]
     for name in NEW_CALLS:
         assert hasattr(product_lib, name) and name in engine.EXPORTS, name
     # additive: the version is v13's, and the keep block's create call is still declared as it was
     assert re.search(r"#define ECDNA_SSA_ABI_VERSION 13\b", text) and abi.ABI_VERSION == 13
     assert product_lib.ecdna_ssa_abi_version() == 13
-    assert _declared(text, "ecdna_ssa_ctx_create_keep")[-2:] == ["const ecdna_ssa_keep_t* keep", "ecdna_ssa_ctx** out"]
+    assert declared("ecdna_ssa_ctx_create_keep")[-2:] == ["const ecdna_ssa_keep_t* keep", "ecdna_ssa_ctx** out"]
 
 
 def test_null_context_calls_are_invalid(product_lib):
@@ -110,28 +93,13 @@ def test_layout_and_source_match_header(tmp_path):
     blocks and sources did not move."""
     fields = [f for f, _ in abi.KeepTimepoints._fields_]
     assert fields == ["struct_size", "keep_cells", "reserved"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("{\\"kt\\": %zu", sizeof(ecdna_ssa_keep_timepoints_t));']
-    for f in fields:
-        lines.append(f'printf(", \\"kt.{f}\\": %zu", offsetof(ecdna_ssa_keep_timepoints_t, {f}));')
-    lines += ['printf(", \\"source\\": %d", (int)ECDNA_ACCEPT_RESCORED_TIMEPOINTS);',
-              'printf(", \\"rescored\\": %d", (int)ECDNA_ACCEPT_RESCORED);',
-              'printf(", \\"cohort_samples\\": %d", (int)ECDNA_ACCEPT_COHORT_SAMPLES);',
-              'printf(", \\"passage_samples\\": %d", (int)ECDNA_ACCEPT_PASSAGE_SAMPLES);',
-              'printf(", \\"keep\\": %zu", sizeof(ecdna_ssa_keep_t));',
-              'printf(", \\"kept\\": %zu", sizeof(ecdna_kept_t));',
-              'printf(", \\"cohort\\": %zu", sizeof(ecdna_ssa_cohort_t));',
-              'printf(", \\"accept\\": %zu", sizeof(ecdna_ssa_accept_t));',
-              'printf(", \\"select\\": %zu", sizeof(ecdna_ssa_select_t));',
-              'printf(", \\"passages\\": %zu", sizeof(ecdna_ssa_passages_t));',
-              'printf(", \\"ext\\": %zu", sizeof(ecdna_ssa_ext_t));',
-              'printf(", \\"instance\\": %zu", sizeof(ecdna_ssa_instance_t));',
-              'printf(", \\"params\\": %zu}\\n", sizeof(ecdna_ssa_params_t));', "return 0;}"]
-    src = tmp_path / "kt_layout.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "kt_layout"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    got = json.loads(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
+    got = layout(tmp_path, {"kt": ("ecdna_ssa_keep_timepoints_t", fields), "keep": "ecdna_ssa_keep_t",
+                            "kept": "ecdna_kept_t", "cohort": "ecdna_ssa_cohort_t", "accept": "ecdna_ssa_accept_t",
+                            "select": "ecdna_ssa_select_t", "passages": "ecdna_ssa_passages_t", "ext": "ecdna_ssa_ext_t",
+                            "instance": "ecdna_ssa_instance_t", "params": "ecdna_ssa_params_t"},
+                 values={"source": "ECDNA_ACCEPT_RESCORED_TIMEPOINTS", "rescored": "ECDNA_ACCEPT_RESCORED",
+                         "cohort_samples": "ECDNA_ACCEPT_COHORT_SAMPLES",
+                         "passage_samples": "ECDNA_ACCEPT_PASSAGE_SAMPLES"})
     assert got["kt"] == C.sizeof(abi.KeepTimepoints) == 16
     for f in fields:
         assert got[f"kt.{f}"] == getattr(abi.KeepTimepoints, f).offset, f
